@@ -11,9 +11,18 @@ process).
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task description), with
+Prints ONE JSON line on rank 0 (contract in the task description).  A plain run
+measures the headline figure only.  ``--full`` adds what takes runs of its own:
 ``roofline`` for the dominant hand-written kernel (timed with device events on
-the launch stream inside the timed region) and ``cpu_baseline`` (N=1 only).
+the launch stream in instrumented eager steps before the timed region), the
+other per-kernel figures, ``unpipelined`` and ``cpu_baseline`` (N=1 only).
+
+``--dump-outputs DIR`` writes what the last timed step returned (loss, logits)
+and the parameters after its optimizer update as ``DIR/<name>.npy`` (fp32).
+The synthetic batches and the initial weights are seeded, so two builds run
+with the same arguments can be compared output for output.  The first step is
+bitwise reproducible; later ones are not (one build, two runs of 5 warm-up +
+20 timed steps: loss 3e-5, parameters 2e-3, logits 2e-2 apart in relative L2).
 """
 from __future__ import annotations
 
@@ -122,6 +131,24 @@ class KernelTimer:
         return out
 
 
+# --dump-outputs: at most this many fp32 values per array (48 MiB in all); a larger array is replaced by a fixed, seeded
+# sample of its elements (sorted flat indices drawn with replacement from a generator seeded with 0)
+DUMP_MAX_NUMEL = {"loss": 1, "logits": 4 << 20, "params": 8 << 20}
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().float()
+        cap = DUMP_MAX_NUMEL[name]
+        if t.numel() > cap:
+            g = torch.Generator(device="cpu").manual_seed(0)
+            idx = torch.randint(t.numel(), (cap,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.cpu().numpy())
+
+
 def _free_port() -> int:
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as sock:
@@ -194,14 +221,19 @@ def main():
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2", help="BASELINE.json configuration (default: c2, "
                     "the one the metric is quoted on)")
     ap.add_argument("--batch", type=int, default=None, help="images per GPU (default: the configuration's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: per-kernel "
+                    "device-event timings (roofline objects), the unpipelined schedule and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the loss and logits of the last timed step "
+                    "and the parameters after it as DIR/<name>.npy (fp32; a seeded sample of arrays above the size cap)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-batch", type=int, default=256, help="batch of the CPU baseline sample (default: the metric's 256 images: one warm-up + one timed CPU step, ~40 s each on 16 cores)")
     ap.add_argument("--global-batch", type=int, default=None, help="STRONG scaling: fix the global batch (e.g. 256) and give every rank global / world images; default: weak scaling, --batch images per GPU")
     ap.add_argument("--grad-checkpointing", action="store_true")
     ap.add_argument("--set", action="append", default=[], metavar="KEY=VALUE", help="further config overrides (A/B "
                     "experiments, e.g. --set basd.gemm_tile_run=0); the default line uses none")
     ap.add_argument("--eager", action="store_true", help="do not capture the step into a hipGraph")
-    ap.add_argument("--no-ab", action="store_true", help="skip the second, unpipelined measurement (profiling runs)")
+    ap.add_argument("--no-ab", action="store_true", help="with --full: skip the second, unpipelined measurement "
+                    "(profiling runs)")
     ap.add_argument("--no-pipeline", action="store_true", help="do not overlap the teacher forward of batch k + 1 with "
                     "loss / backward of batch k (every step then starts with its own teacher forward)")
     args = ap.parse_args()
@@ -271,13 +303,15 @@ def main():
     timer = KernelTimer(native, ["jacobi_svd", "pchol", "trinv", "bgemm_f64", "token_gram", "mix_tokens",
                                  "mix_grad_dots", "procrustes_prep", "wgrad_bf16", "sf_adamw_step", "mp_rank",
                                  "gemm_bf16", "gemm_gelu_fwd", "gemm_gelu_bwd", "add_layernorm_fwd"])
-    timer.install()
+    if args.full:
+        timer.install()
 
-    # a few eager steps first: rank sanity check + (events cannot be recorded inside a captured graph)
-    # the per-kernel device-event timings used for the roofline object
+    # a few eager steps first: rank sanity check + (--full; events cannot be recorded inside a captured graph)
+    # the per-kernel device-event timings used for the roofline object.  A plain run takes the same steps
+    # uninstrumented, so that its timed steps start from the same training state as those of a --full run.
     eager_probe = 3
-    timer.active = True
-    timer.launch_procrustes_entry_by_entry(True)
+    timer.active = args.full
+    timer.launch_procrustes_entry_by_entry(args.full)
     for i in range(eager_probe):
         loss, _ = trainer.train_step(batch)
         torch.cuda.synchronize()
@@ -294,7 +328,7 @@ def main():
             for n_ in timer.records:          # drop the first (cold) step from the statistics
                 timer.records[n_].clear()
                 timer.meta[n_].clear()
-            timer.active = True
+            timer.active = args.full
     torch.cuda.synchronize()
     timer.active = False
     trainer.overlap_teacher_stats, trainer.overlap_teacher_forward = stream_flags       # product schedule from here on
@@ -328,7 +362,7 @@ def main():
     host_s = 0.0
     for i in range(args.steps):
         th = time.perf_counter()
-        loss, _ = trainer.train_step(batch_at(args.warmup + i), batch_at(args.warmup + i + 1))
+        loss, logits = trainer.train_step(batch_at(args.warmup + i), batch_at(args.warmup + i + 1))
         host_s += time.perf_counter() - th      # time to ENQUEUE a step (no device sync inside)
     barrier()
     elapsed = time.perf_counter() - t0
@@ -340,9 +374,14 @@ def main():
     ms_per_step = 1e3 * elapsed / args.steps
     global_batch = args.batch * world
     value = global_batch * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        # before anything else runs on the trainer: the parameters are those the last timed step left
+        dump_outputs(args.dump_outputs, {"loss": loss, "logits": logits, "params": trainer.flat.data})
+        progress(f"outputs of the last timed step written to {args.dump_outputs}")
+    loss_value = float(loss)
     pipelined = trainer._pipe is not None
     unpipelined = None
-    if pipelined and world == 1 and not args.no_ab:
+    if args.full and pipelined and world == 1 and not args.no_ab:
         # the same K steps with every step waiting for its own teacher forward (the schedule of rounds 1 - 2), for
         # reference: re-capture without the pipeline, re-warm, time
         if trainer.enable_graph(batch, pipeline=False):
@@ -466,7 +505,7 @@ def main():
                                 "measured_in": "device events in the single-stream instrumented probe steps"}
         vit_flops = global_batch * ((4 if args.grad_checkpointing else 3) * F_STUDENT + F_TEACHER)
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle.cpu_step import cpu_step_images_per_sec
             print("[bench] GPU timing done; timing the CPU baseline sample", file=sys.stderr, flush=True)
             # the metric's own batch (256): one warm-up step + one timed step (~2 x 40 s of CPU work on the 16-core share)
@@ -477,21 +516,21 @@ def main():
                        f"images/sec BASD train step, {student_preset} student / {teacher_preset} teacher"),
             "value": value, "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
-            "dtype": "bf16", "data": "synthetic",
+            "dtype": "bf16", "data": "synthetic", "full": args.full,
             "config": {"workload": f"{workload} (random init), {img_size}x{img_size}, E=4 extraction points, "
                                    "loss linalg fp32/fp64",
                        "global_batch": global_batch, "per_gpu_batch": args.batch, "parallelism": f"dp{world}",
                        "grad_checkpointing": bool(args.grad_checkpointing)},
             "roofline": roof,
             "roofline_top_by_total_time": gemm,
-            "roofline_streaming": streaming,
+            "roofline_streaming": streaming if args.full else None,
             "rccl_ranks": dist.get_world_size() if world > 1 else 1,
             "launcher": os.environ.get("BASD_BENCH_LAUNCHER", "torchrun" if "TORCHELASTIC_RUN_ID" in os.environ else "none"),
             "cpu_baseline": cpu,
             "library_fallbacks": dict(__import__("basd_amd.losses._ops", fromlist=["FALLBACKS"]).FALLBACKS),
             "vit_gemm": {"algorithmic_tflop_per_step": vit_flops / 1e12,
                          "tflops_if_whole_step": vit_flops / (ms_per_step / 1e3) / 1e12, "peak_bf16": 2500.0},
-            "kernel_ms_per_step": {k: v["total_ms"] / probe_steps for k, v in ks.items()},
+            "kernel_ms_per_step": {k: v["total_ms"] / probe_steps for k, v in ks.items()} if args.full else None,
             "hip_graph": graphed, "hip_graph_error": trainer.graph_error, "pipeline_error": trainer.pipeline_error,
             "schedule": ("teacher forward + selector statistics of batch k+1 on a side stream under loss / backward of "
                          "batch k (software pipelining across steps; every timed step still runs one teacher forward, one "
@@ -501,7 +540,7 @@ def main():
             "unpipelined": unpipelined,
             "peak_hbm_gb": torch.cuda.max_memory_allocated(dev) / 2**30,
             "host_enqueue_ms_per_step": 1e3 * host_s / args.steps,
-            "loss": float(loss),
+            "loss": loss_value,
             "teacher_ranks": list(trainer.basd_loss.layer_selector.subspace_ranks.values()),
         }
         print(json.dumps(line))

@@ -6,7 +6,7 @@ mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
 for mode in pipelined unpipelined; do
   extra=""; [ $mode = unpipelined ] && extra="--no-pipeline"
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$mode -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-ab $extra > $O/bench_line_under_rocprof_$mode.json 2> $O/trace_$mode.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$mode -- python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-ab $extra > $O/bench_line_under_rocprof_$mode.json 2> $O/trace_$mode.err
   echo "trace $mode rc=$?"
   ks=$(find $O/trace_$mode -name "*kernel_stats.csv" | head -1); kt=$(find $O/trace_$mode -name "*kernel_trace.csv" | head -1)
   cp $ks $O/kernel_stats_$mode.csv
@@ -15,7 +15,7 @@ for mode in pipelined unpipelined; do
   rm -rf $O/trace_$mode
 done
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --output-format csv -d $O/pmc_$c -- python3 $R/bench.py --eager --steps 2 --warmup 1 --no-cpu-baseline --no-ab > /dev/null 2> $O/pmc_$c.err
+  rocprofv3 --pmc $c --output-format csv -d $O/pmc_$c -- python3 $R/bench.py --full --eager --steps 2 --warmup 1 --no-cpu-baseline --no-ab > /dev/null 2> $O/pmc_$c.err
   echo "pmc $c rc=$?"
   cp $(find $O/pmc_$c -name "*counter_collection.csv" | head -1) $O/pmc_$c.csv
   rm -rf $O/pmc_$c

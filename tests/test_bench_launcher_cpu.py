@@ -52,3 +52,29 @@ def test_a_failing_rank_fails_the_launcher():
         pytest.skip("needs a box without a GPU")
     res = _run(["--gpus", "2", "--steps", "1", "--warmup", "0"], timeout=300)
     assert res.returncode != 0
+
+
+def test_full_and_dump_outputs_options_exist():
+    res = _run(["--help"])
+    assert res.returncode == 0, res.stderr
+    assert "--full" in res.stdout and "--dump-outputs" in res.stdout
+
+
+def test_dump_outputs_writes_fp32_and_samples_large_arrays_reproducibly(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+
+    import bench
+    assert sum(bench.DUMP_MAX_NUMEL.values()) * 4 <= 64 * 10**6      # fp32 values: within the 64 MB of a dump
+    monkeypatch.setitem(bench.DUMP_MAX_NUMEL, "params", 1000)
+    arrays = {"loss": torch.tensor(1.5), "logits": torch.randn(8, 10).bfloat16(),
+              "params": torch.arange(5000, dtype=torch.float32)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    for name in arrays:
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+    assert float(np.load(tmp_path / "a" / "loss.npy")) == 1.5
+    assert np.array_equal(np.load(tmp_path / "a" / "logits.npy"), arrays["logits"].float().numpy())
+    p = np.load(tmp_path / "a" / "params.npy")
+    assert p.shape == (1000,) and np.all(np.diff(p) >= 0) and p.min() >= 0 and p.max() < 5000   # sorted sample of the values
