@@ -49,6 +49,12 @@
  *   basd_layernorm_fwd_bf16 / _bwd_bf16, basd_add_layernorm_fwd_bf16
  *                          timm nn.LayerNorm of the ViT blocks (student: with backward; frozen teacher: fused with
  *                          the residual add in front of it)
+ *   basd_split_bf16x2_table, basd_split_patches_bf16x2, basd_gemm_f32x3, basd_attention_fwd_f32x3,
+ *   basd_add_layernorm_fwd_f32
+ *                          the fp32 evaluation forward of a ViT under torch.set_float32_matmul_precision("high")
+ *                          (src/training/trainer.py:183-188, src/train.py:153-160, src/eval.py:16): nn.Linear,
+ *                          Attention, nn.LayerNorm and the patch-embedding convolution on split-bf16 (bf16x3) MFMA
+ *                          products, fp32 everywhere else
  */
 #ifndef BASD_HIP_H
 #define BASD_HIP_H
@@ -419,6 +425,39 @@ int basd_lerp(float* y, const float* z, int64_t n, float w, void* stream);
  * table: HOST array of n_entries x {src offset, dst offset, rows, cols} (int64, offsets in elements):
  * out[dst + c * rows + r] = bf16(master[src + r * cols + c]). */
 int basd_transpose_bf16_table(const float* master, void* out, const int64_t* table, int n_entries, void* stream);
+
+/* ---- fp32 evaluation forward on split-bf16 products (torch.set_float32_matmul_precision("high"); reference
+ * src/training/trainer.py:183-188, src/train.py:153-160, src/eval.py:16).  A SPLIT IMAGE of fp32 values v [rows, k] is
+ * a bf16 [rows, 2 k_pad] array: columns [0, k) hold hi = bf16_rne(v), columns [k_pad, k_pad + k) hold
+ * lo = bf16_rne(v - hi), the columns up to k_pad of either half are zero.  A product of two images is
+ * x_hi w_hi + x_hi w_lo + x_lo w_hi with fp32 accumulation (~16 significand bits). */
+
+/* Images of n_entries fp32 weight matrices in one launch (the nn.Linear / patch-embedding weights of the model, rebuilt
+ * every forward).  table: HOST array of n_entries x {src address, dst address, rows, k, k_pad} (int64; addresses of
+ * DEVICE memory): dst [rows, 2 k_pad] bf16 = image of src [rows, k] fp32. */
+int basd_split_bf16x2_table(const int64_t* table, int n_entries, void* stream);
+
+/* Image of the unfolded patches of x [B, C, H, W] fp32 (non-overlapping p x p; the stride-p Conv2d of the patch
+ * embedding as a GEMM): out [B (H/p) (W/p), 2 k_pad] with k = c p p + i p + j, k_pad >= C p p, k_pad % 32 == 0. */
+int basd_split_patches_bf16x2(const float* x, int B, int C, int H, int W, int p, int k_pad, void* out, void* stream);
+
+/* nn.Linear in fp32 "high": y = epi(x w^T + bias) from the images x [M, 2 k_pad] and w [N, 2 k_pad] (bf16), bias fp32
+ * [N] or NULL.  epilogue 0: y fp32 [M, N]; 1: y = GELU (exact erf) fp32; 2 / 3: the same written as the image
+ * y [M, 2 N] bf16 (the next GEMM's input, k_pad = N).  Any M >= 1; N % 16 == 0, k_pad % 32 == 0; 16-byte aligned. */
+int basd_gemm_f32x3(const void* x_img, const void* w_img, const float* bias, void* y, int64_t M, int N, int k_pad,
+                    int epilogue, void* stream);
+
+/* timm Attention.forward in fp32 "high": softmax(q k^T scale) v from the packed projection qkv [B, T, 3, H, hd] fp32,
+ * logits and softmax in fp32, both products on images; out = the image [B T, 2 H hd] of the [B, T, H hd] output (the
+ * proj GEMM's input).  hd in {64, 80}, 1 <= T <= 272. */
+int basd_attention_fwd_f32x3(const float* qkv, int B, int T, int H, int hd, float scale, void* out_img, void* stream);
+
+/* nn.LayerNorm in fp32 with the residual step in front of it: s = residual + xscale * x (residual / xscale NULL: no
+ * add / no LayerScale gamma [D]), y = LayerNorm(s) with fp32 statistics.  Outputs (NULL: not written): s_out fp32
+ * [rows, D] (may alias residual), y fp32 [rows, D], y_img [rows, 2 D] bf16.  D % 4 == 0, D <= 2048. */
+int basd_add_layernorm_fwd_f32(const float* x, const float* residual, const float* xscale, const float* gamma,
+                               const float* beta, int64_t rows, int D, float eps, float* s_out, float* y, void* y_img,
+                               void* stream);
 
 #ifdef __cplusplus
 }

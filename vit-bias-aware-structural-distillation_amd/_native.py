@@ -29,6 +29,8 @@ EXPORTS = (
     "basd_sf_adamw_step", "basd_lerp", "basd_transpose_bf16_table", "basd_bgemm_f64", "basd_trinv_f64", "basd_bgemm_f64_masked", "basd_trinv_f64_masked", "basd_pchol_f64_masked", "basd_wgrad_bf16", "basd_wgrad_workspace_bytes", "basd_wgrad_bf16_ws", "basd_gemm_bf16",
     "basd_gemm_bf16_gelu_fwd", "basd_gemm_bf16_gelu_bwd", "basd_gemm_bf16x3_f32", "basd_layernorm_fwd_bf16", "basd_layernorm_bwd_bf16",
     "basd_cls_importance_bf16", "basd_add_layernorm_fwd_bf16", "basd_procrustes_bwd_rows", "basd_attention_fwd_bf16", "basd_attention_fwd_qmean_bf16", "basd_attention_bwd_bf16",
+    "basd_split_bf16x2_table", "basd_split_patches_bf16x2", "basd_gemm_f32x3", "basd_attention_fwd_f32x3",
+    "basd_add_layernorm_fwd_f32",
 )
 
 
@@ -79,6 +81,11 @@ _SIGNATURES = {
     "basd_attention_bwd_bf16": (_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P),
     "basd_sf_adamw_step": (_P, _P, _P, _P, _I64, _D, _D, _D, _D, _D, _D, _D, _P),
     "basd_lerp": (_P, _P, _I64, _F, _P),
+    "basd_split_bf16x2_table": (_P, _I, _P),
+    "basd_split_patches_bf16x2": (_P, _I, _I, _I, _I, _I, _I, _P, _P),
+    "basd_gemm_f32x3": (_P, _P, _P, _P, _I64, _I, _I, _I, _P),
+    "basd_attention_fwd_f32x3": (_P, _I, _I, _I, _I, _F, _P, _P),
+    "basd_add_layernorm_fwd_f32": (_P, _P, _P, _P, _P, _I64, _I, _F, _P, _P, _P, _P),
 }
 
 
@@ -993,3 +1000,106 @@ def layernorm_bwd(dy: torch.Tensor, x: torch.Tensor, gamma: torch.Tensor, mean: 
                                          ctypes.c_int64(rows), d, _ptr(dx), _ptr(dgamma), _ptr(dbeta), _ptr(dres),
                                          _ptr(dbranch), _ptr(row_scale), rps, _stream()), "basd_layernorm_bwd_bf16")
     return (dx, dbranch) if want_branch else dx
+
+
+# ---- fp32 evaluation forward on split-bf16 (bf16x3) products: torch.set_float32_matmul_precision("high") --------------
+# A split image of fp32 values [rows, k] is bf16 [rows, 2 k_pad]: (hi | lo), zero columns up to k_pad (include/basd_hip.h).
+
+def f32x3_gemm_supported(n: int, k_pad: int) -> bool:
+    return n >= 16 and n % 16 == 0 and k_pad >= 32 and k_pad % 32 == 0
+
+
+def f32x3_layernorm_supported(d: int) -> bool:
+    return d % 4 == 0 and 4 <= d <= 2048
+
+
+def split_table(entries) -> list[torch.Tensor]:
+    """entries: list of (fp32 matrix [rows, k] (any contiguous view), k_pad) -> their images [rows, 2 k_pad] bf16, carved
+    from ONE allocation and written by one launch (per 64 entries)."""
+    if not entries:
+        return []
+    dev = entries[0][0].device
+    sizes = [w.shape[0] * 2 * kp for w, kp in entries]
+    offs, total = [], 0
+    for n in sizes:
+        offs.append(total)
+        total += (n + 7) // 8 * 8                       # 16-byte aligned images
+    buf = torch.empty(total, dtype=torch.bfloat16, device=dev)
+    flat, out = [], []
+    for (w, kp), off, n in zip(entries, offs, sizes):
+        _need_cuda(w)
+        assert w.dtype == torch.float32 and w.dim() == 2 and w.is_contiguous() and kp >= w.shape[1] and w.device == dev
+        img = buf[off:off + n].view(w.shape[0], 2 * kp)
+        out.append(img)
+        flat += [w.data_ptr(), img.data_ptr(), w.shape[0], w.shape[1], kp]
+    arr = (ctypes.c_int64 * len(flat))(*[int(v) for v in flat])
+    _check(lib().basd_split_bf16x2_table(ctypes.cast(arr, ctypes.c_void_p), len(entries), _stream()),
+           "basd_split_bf16x2_table")
+    return out
+
+
+def split_patches(x: torch.Tensor, patch: int, k_pad: int) -> torch.Tensor:
+    """x [B, C, H, W] fp32 -> image [B (H/p) (W/p), 2 k_pad] of the unfolded non-overlapping patches."""
+    _need_cuda(x)
+    assert x.dtype == torch.float32 and x.dim() == 4
+    x = x.contiguous()
+    b, c, h, w = x.shape
+    out = torch.empty(b * (h // patch) * (w // patch), 2 * k_pad, dtype=torch.bfloat16, device=x.device)
+    _check(lib().basd_split_patches_bf16x2(_ptr(x), b, c, h, w, patch, k_pad, _ptr(out), _stream()),
+           "basd_split_patches_bf16x2")
+    return out
+
+
+def gemm_f32x3(x_img: torch.Tensor, w_img: torch.Tensor, bias: torch.Tensor | None = None, gelu: bool = False,
+               split_out: bool = False) -> torch.Tensor:
+    """x_img [M, 2 k_pad], w_img [N, 2 k_pad] (images), bias fp32 [N] -> epi(x w^T + bias): fp32 [M, N] or, with
+    ``split_out``, its image [M, 2 N]."""
+    _need_cuda(x_img, w_img)
+    assert x_img.dtype == torch.bfloat16 and w_img.dtype == torch.bfloat16
+    assert x_img.is_contiguous() and w_img.is_contiguous() and x_img.shape[-1] == w_img.shape[-1]
+    m, n, kp = x_img.shape[0], w_img.shape[0], w_img.shape[1] // 2
+    if bias is not None:
+        assert bias.dtype == torch.float32 and bias.numel() == n
+        bias = bias.contiguous()
+    y = (torch.empty(m, 2 * n, dtype=torch.bfloat16, device=x_img.device) if split_out
+         else torch.empty(m, n, dtype=torch.float32, device=x_img.device))
+    _check(lib().basd_gemm_f32x3(_ptr(x_img), _ptr(w_img), _ptr(bias), _ptr(y), ctypes.c_int64(m), n, kp,
+                                 int(gelu) + 2 * int(split_out), _stream()), "basd_gemm_f32x3")
+    return y
+
+
+def attention_fwd_f32x3(qkv: torch.Tensor, heads: int, head_dim: int, scale: float) -> torch.Tensor:
+    """qkv [B, T, 3 * heads * head_dim] fp32 -> the image [B T, 2 heads head_dim] of softmax(q k^T scale) v."""
+    _need_cuda(qkv)
+    assert qkv.dtype == torch.float32 and qkv.shape[-1] == 3 * heads * head_dim
+    qkv = qkv.contiguous()
+    b, t = qkv.shape[0], qkv.shape[1]
+    out = torch.empty(b * t, 2 * heads * head_dim, dtype=torch.bfloat16, device=qkv.device)
+    _check(lib().basd_attention_fwd_f32x3(_ptr(qkv), b, t, heads, head_dim, ctypes.c_float(scale), _ptr(out), _stream()),
+           "basd_attention_fwd_f32x3")
+    return out
+
+
+def add_layernorm_f32(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float,
+                      residual: torch.Tensor | None = None, xscale: torch.Tensor | None = None, want_s: bool = False,
+                      want_y: bool = False, want_img: bool = True):
+    """s = residual + xscale * x (no residual: s = x), y = LayerNorm(s), all fp32 -> tuple of the requested outputs in
+    the order (s [..., D] fp32, y [..., D] fp32, image [rows, 2 D] bf16)."""
+    _need_cuda(x, gamma, beta)
+    assert x.dtype == torch.float32 and gamma.dtype == torch.float32 and beta.dtype == torch.float32
+    x = x.contiguous()
+    d = x.shape[-1]
+    rows = x.numel() // d
+    if residual is not None:
+        assert residual.dtype == torch.float32 and residual.shape == x.shape
+        residual = residual.contiguous()
+    if xscale is not None:
+        xscale = xscale.detach().float().contiguous()
+        assert xscale.numel() == d
+    s = torch.empty_like(x) if want_s else None
+    y = torch.empty_like(x) if want_y else None
+    img = torch.empty(rows, 2 * d, dtype=torch.bfloat16, device=x.device) if want_img else None
+    _check(lib().basd_add_layernorm_fwd_f32(_ptr(x), _ptr(residual), _ptr(xscale), _ptr(gamma.contiguous()),
+                                            _ptr(beta.contiguous()), ctypes.c_int64(rows), d, ctypes.c_float(eps),
+                                            _ptr(s), _ptr(y), _ptr(img), _stream()), "basd_add_layernorm_fwd_f32")
+    return tuple(t for t in (s, y, img) if t is not None)

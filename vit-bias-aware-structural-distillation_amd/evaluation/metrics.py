@@ -63,12 +63,15 @@ def evaluate_model(model: nn.Module, data_loader, criterion: nn.Module, *, num_c
 @torch.no_grad()
 def measure_efficiency(model: nn.Module, *, image_size: int, in_channels: int = 3, batch_size: int = 64,
                        num_warmup: int = 50, num_batches: int = 200) -> dict[str, float]:
-    """Parameter count, forward GFLOPs of one image (``FlopCounterMode``: the evaluation forward of the student runs
-    on library ops, which the counter sees) and inference throughput at ``batch_size``."""
+    """Parameter count, forward GFLOPs of one image (``FlopCounterMode``) and inference throughput at ``batch_size``.
+    The counter sees library ops only, not the HIP kernels: the counting forward runs under "highest" (library fp32),
+    so the figure does not depend on the precision the caller set; the timed loops run under the caller's."""
+    from ..losses._ops import declared_library_calls
+    from .precision import matmul_precision
     model.eval()
     dev = _device_of(model)
     params = sum(p.numel() for p in model.parameters())
-    with FlopCounterMode(display=False) as counter:
+    with matmul_precision("highest"), declared_library_calls(), FlopCounterMode(display=False) as counter:
         model(torch.randn(1, in_channels, image_size, image_size, device=dev))
     gflops = counter.get_total_flops() / 1e9
     x = torch.randn(batch_size, in_channels, image_size, image_size, device=dev)

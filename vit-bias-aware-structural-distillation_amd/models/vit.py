@@ -321,6 +321,7 @@ class Block(nn.Module):
 
         self._next_norm = []            # [norm that consumes this block's output]; set by the model, not a submodule
         self.fuse_training = True       # cleared under activation checkpointing (tensor attributes do not survive it)
+        self._f32x3 = None              # (weight images, final norm) while the model runs its fp32 "high" forward
 
     def _fused_inference(self, x) -> bool:
         """frozen pre-norm block on bf16 activations: the residual adds fuse into the following norms"""
@@ -335,7 +336,57 @@ class Block(nn.Module):
                 and get_ops().handles(x) and isinstance(self.ls1, nn.Identity) and isinstance(self.ls2, nn.Identity)
                 and self.norm2.elementwise_affine and self.fuse_training and get_ops().layernorm_supported(x.shape[-1]))
 
+    def _f32x3_supported(self, t: int) -> bool:
+        """every layer of this block has a kernel of the fp32 split-bf16 evaluation forward (T tokens)"""
+        ops = get_ops()
+        a, d = self.attn, self.attn.qkv.in_features
+        lins = (a.qkv, a.proj, self.mlp.fc1, self.mlp.fc2)
+        return (type(self.mlp) is Mlp and isinstance(self.mlp.act, nn.GELU) and self.mlp.act.approximate == "none"
+                and a.tap is None and ops.attention_fwd_supported(t, a.head_dim) and ops.f32x3_layernorm_supported(d)
+                and all(l.bias is not None and l.weight.dtype == torch.float32 and l.bias.dtype == torch.float32
+                        and ops.f32x3_gemm_supported(l.out_features, l.in_features) for l in lins)
+                and all(isinstance(m, (nn.Identity, LayerScale)) for m in (self.ls1, self.ls2))
+                and self.norm1.elementwise_affine and self.norm2.elementwise_affine
+                and (not self.training or (self.drop_path1.p == 0.0 and self.drop_path2.p == 0.0)))
+
+    def _forward_f32x3(self, x, images, final_norm):
+        """fp32 evaluation forward on split-bf16 products (csrc/eval_f32x3.hip): LayerNorm -> qkv -> attention -> proj ->
+        residual add + LayerNorm -> fc1 + GELU -> fc2 -> residual add, with the add fused into the NEXT norm as in
+        _fused_inference.  Between the kernels the GEMM inputs travel as split images; the block output is an ordinary
+        fp32 [B, T, D] tensor."""
+        ops = get_ops()
+        b, t, d = x.shape
+        a, n1, n2 = self.attn, self.norm1, self.norm2
+        w_qkv, w_proj, w_fc1, w_fc2 = images
+        pre = getattr(x, "_basd_prenorm_img", None)
+        if pre is not None and pre[0] is n1:
+            z = pre[1]
+        else:
+            (z,) = ops.add_layernorm_f32(x, n1.weight.detach().float(), n1.bias.detach().float(), n1.eps)
+        qkv = ops.gemm_f32x3(z, w_qkv, a.qkv.bias.detach())
+        o = ops.attention_fwd_f32x3(qkv.view(b, t, -1), a.num_heads, a.head_dim, a.scale)
+        y = ops.gemm_f32x3(o, w_proj, a.proj.bias.detach()).view(b, t, d)
+        g1 = self.ls1.gamma.detach() if isinstance(self.ls1, LayerScale) else None
+        g2 = self.ls2.gamma.detach() if isinstance(self.ls2, LayerScale) else None
+        x, z = ops.add_layernorm_f32(y, n2.weight.detach().float(), n2.bias.detach().float(), n2.eps, residual=x,
+                                     xscale=g1, want_s=True)
+        h = ops.gemm_f32x3(z, w_fc1, self.mlp.fc1.bias.detach(), gelu=True, split_out=True)
+        m = ops.gemm_f32x3(h, w_fc2, self.mlp.fc2.bias.detach()).view(b, t, d)
+        nxt = self._next_norm[0] if self._next_norm else None
+        if nxt is None or not nxt.elementwise_affine or not ops.f32x3_layernorm_supported(d):
+            return x + (m * g2 if g2 is not None else m)
+        final = nxt is final_norm
+        out, zn = ops.add_layernorm_f32(m, nxt.weight.detach().float(), nxt.bias.detach().float(), nxt.eps, residual=x,
+                                        xscale=g2, want_s=True, want_y=final, want_img=not final)
+        if final:
+            out._basd_prenorm = (nxt, zn)            # the model's final norm returns it (fp32 [B, T, D])
+        else:
+            out._basd_prenorm_img = (nxt, zn)        # the next block's norm1 as the image its qkv GEMM reads
+        return out
+
     def forward(self, x, dp_masks=None):
+        if self._f32x3 is not None and x.dtype == torch.float32 and not torch.is_grad_enabled():
+            return self._forward_f32x3(x, *self._f32x3)
         if self._fused_training(x):
             # (bf16 mask, bf16 mask, fp32 per-sample scale, fp32 per-sample scale): the model draws all of them at once
             m1, m2, sc1, sc2 = dp_masks if dp_masks is not None else (None, None, None, None)
@@ -448,6 +499,13 @@ class _PaddedPatchFn(torch.autograd.Function):
         return None, gw[:, :ctx.k].contiguous(), gb
 
 
+F32X3_PRECISIONS = ("high", "medium")
+
+
+def _pad32(k: int) -> int:
+    return (k + 31) // 32 * 32
+
+
 def _matrix_view(weight: torch.Tensor) -> torch.Tensor:
     """[D, C, p, p] convolution weight as the [D, C p p] matrix of the GEMM; the bf16 image, the gradient slot in the
     flat buffer and the data-parallel hook of the parameter (trainer attributes) follow the view"""
@@ -488,7 +546,55 @@ class VisionTransformer(nn.Module):
         for blk in self.blocks:
             blk.fuse_training = not enable
 
+    def _f32x3_ok(self, x) -> bool:
+        """The fp32 evaluation route: no grad, fp32 device activations, no autocast and
+        torch.get_float32_matmul_precision() "high" or "medium" (the reference evaluates under "high": src/eval.py:16,
+        src/training/trainer.py:183-188) -- every fp32 product on split-bf16 (bf16x3) MFMAs.  Under "highest" (torch's
+        default) every path stays as it was."""
+        ops = get_ops()
+        if (torch.is_grad_enabled() or x.dtype != torch.float32 or x.dim() != 4 or not ops.handles(x)
+                or not hasattr(ops, "gemm_f32x3") or torch.get_float32_matmul_precision() not in F32X3_PRECISIONS
+                or torch.is_autocast_enabled(x.device.type)):
+            return False
+        pe, p = self.patch_embed, self.patch_embed.patch_size
+        w = pe.proj.weight
+        t = self.pos_embed.shape[1]
+        return (pe.proj.bias is not None and w.dtype == torch.float32 and pe.proj.bias.dtype == torch.float32
+                and w.is_contiguous() and x.shape[2] % p == 0 and x.shape[3] % p == 0
+                and (x.shape[2] // p) * (x.shape[3] // p) + int(self.cls_token is not None) == t
+                and ops.f32x3_gemm_supported(self.embed_dim, _pad32(w[0].numel()))
+                and isinstance(self.norm, MixedLayerNorm) and self.norm.elementwise_affine
+                and all(isinstance(blk, Block) and blk._f32x3_supported(t) for blk in self.blocks))
+
+    def _forward_features_f32x3(self, x):
+        ops = get_ops()
+        pe, p, d = self.patch_embed, self.patch_embed.patch_size, self.embed_dim
+        b = x.shape[0]
+        w = pe.proj.weight.detach().reshape(d, -1)
+        kp = _pad32(w.shape[1])
+        blocks = list(self.blocks)
+        # the images of ALL weights, rebuilt every forward in one launch: the Schedule-Free eval / train switch rewrites
+        # the parameters in place (training/optim.py) without moving their _version, so nothing is cached
+        entries = [(w, kp)] + [(lin.weight.detach(), lin.in_features) for blk in blocks
+                               for lin in (blk.attn.qkv, blk.attn.proj, blk.mlp.fc1, blk.mlp.fc2)]
+        images = ops.split_table(entries)
+        x = ops.gemm_f32x3(ops.split_patches(x, p, kp), images[0], pe.proj.bias.detach()).view(b, -1, d)
+        if self.cls_token is not None:
+            x = torch.cat([self.cls_token.expand(b, -1, -1), x], dim=1)
+        x = x + self.pos_embed
+        for i, blk in enumerate(blocks):
+            blk._f32x3 = (images[1 + 4 * i:5 + 4 * i], self.norm)
+        try:
+            for blk in blocks:
+                x = blk(x)              # module calls: forward hooks see the fp32 [B, T, D] block outputs
+        finally:
+            for blk in blocks:
+                blk._f32x3 = None
+        return self.norm(x)
+
     def forward_features(self, x):
+        if self._f32x3_ok(x):
+            return self._forward_features_f32x3(x)
         x = self.patch_embed(x)
         if self.cls_token is not None:
             x = torch.cat([self.cls_token.expand(x.shape[0], -1, -1).to(x.dtype), x], dim=1)

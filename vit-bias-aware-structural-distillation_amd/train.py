@@ -133,6 +133,12 @@ def build(config, device="cuda"):
     return trainer, student_info
 
 
+def _evaluate_high(model, loader, criterion, num_classes):
+    from .evaluation import evaluate_model, matmul_precision
+    with matmul_precision("high"):
+        return evaluate_model(model, loader, criterion, num_classes=num_classes)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default=os.path.join(os.path.dirname(__file__), "configs", "config.yaml"))
@@ -141,7 +147,11 @@ def main(argv=None):
     ap.add_argument("overrides", nargs="*")
     args = ap.parse_args(argv)
     config = load_config(args.config, args.experiment, args.overrides)
-    trainer, info = build(config)
+    from .evaluation import matmul_precision, run_eval_suite, save_metrics
+    # start-up (both fp32 probes) and every evaluation under the reference's "high" fp32 matmul precision
+    # (src/train.py, src/training/trainer.py:183-188): the split-bf16 kernels; the training step keeps the default
+    with matmul_precision("high"):
+        trainer, info = build(config)
     print(f"student_probed embed_dim={info['embed_dim']} depth={info['depth']} num_tokens={info['num_tokens']}")
     from .data import create_dataloaders, is_local_dataset
     local = is_local_dataset(config.data.dataset)
@@ -164,17 +174,17 @@ def main(argv=None):
     if config.checkpoint.get("resume_from"):            # reference src/train.py:147-149
         start_epoch = trainer.load_checkpoint(config.checkpoint.resume_from)
         print(f"resumed_from={config.checkpoint.resume_from} start_epoch={start_epoch}")
-    from .evaluation import evaluate_model, run_eval_suite, save_metrics
     if not local:
         val = SyntheticEvalLoader(config.data.batch_size, config.model.vit.img_size, config.model.num_classes, 2,
                                   trainer.device)
     crit = nn.CrossEntropyLoss()
     trainer.train(loader, val, start_epoch=start_epoch,
-                  evaluate_fn=lambda m, l: evaluate_model(m, l, crit, num_classes=config.model.num_classes))
+                  evaluate_fn=lambda m, l: _evaluate_high(m, l, crit, config.model.num_classes))
     # reference src/train.py:153-160: evaluation weights (optimizer.eval()), eval suite, metrics.json
     trainer.optimizer.eval()
-    results = run_eval_suite(trainer.model, config, config_path=args.config, loaders={config.data.dataset: val},
-                             efficiency_kwargs=dict(num_warmup=5, num_batches=20))
+    with matmul_precision("high"):
+        results = run_eval_suite(trainer.model, config, config_path=args.config, loaders={config.data.dataset: val},
+                                 efficiency_kwargs=dict(num_warmup=5, num_batches=20))
     out_dir = os.path.join(config.run.output_dir, config.run.name)
     os.makedirs(out_dir, exist_ok=True)
     print(f"metrics_json={save_metrics(results, out_dir)}")
