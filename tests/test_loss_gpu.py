@@ -203,3 +203,46 @@ def test_whole_loss_is_invariant_to_the_order_of_the_batch_at_c2_size():
     for l in g0:
         assert rel_l2(g1[l], g0[l][perm]) < 3e-4, (l, rel_l2(g1[l], g0[l][perm]))
     assert rel_l2(gl1, gl0[perm]) < 2e-5
+
+
+def _with_dominant_mean(inputs, seed):
+    """the fixture with one constant row vector c_l added to every student token of extraction point l (fp32): c_l is
+    O(1) x the column std on most channels and 1e2 / 1e3 x on four "massive" ones (ViT activations have such channels)"""
+    g = torch.Generator().manual_seed(seed)
+    out = dict(inputs)
+    out["student_tokens"] = {}
+    for l, s in inputs["student_tokens"].items():
+        d = s.shape[-1]
+        std = s.reshape(-1, d).double().std(dim=0)
+        r = torch.randn(d, generator=g, dtype=torch.float64)
+        sign = torch.where(torch.rand(4, generator=g) < 0.5, -1.0, 1.0).double()
+        r[torch.randperm(d, generator=g)[:4]] = sign * torch.tensor([1e2, 1e2, 1e3, 1e3], dtype=torch.float64)
+        out["student_tokens"][l] = (s.double() + r * std).float()
+    return out
+
+
+@pytest.mark.parametrize("name", ["c2_b8", "c4_b8"])
+def test_student_tokens_with_a_dominant_mean_leave_loss_and_gradients_unchanged(name):
+    """The loss is exactly invariant to one constant row vector added to all student tokens of an extraction point (the
+    student frame is column-centred, Procrustes centres every sample with weights that sum to 1, the rank reads teacher
+    tokens only), hence so is its gradient: a metamorphic check of every place that centres in fp32 where a channel's
+    mean dominates its spread (ViT activations have such channels).  c2_b8: small-Jacobi selector path, c4_b8: the
+    blocked one.  Against the run on the un-offset tokens (itself pinned to the goldens), at the golden tolerances except
+    for the student gradients.
+    Storing s + c in fp32 rounds every token by ~6e-8 |c|: the fp64 oracle on the offset against the un-offset fp32
+    tokens puts that floor at student gradients rel-L2 5.9e-5 (c2_b8) / 1.0e-5 (c4_b8), weights 5e-9, loss 3e-11,
+    temperature gradient 1e-7.  The HIP path measured student gradients at 2.6e-4 - 3.0e-4 over runs (c2_b8, last
+    extraction point) / 1.5e-4 (c4_b8): above that floor and the 2e-4 golden tolerance.  Centring the selector
+    backward's GEMM operand instead of folding the mean into its bias row did not lower it (3.3e-4), so the excess comes
+    from elsewhere; the bound sits at about 3x the measured value and pins what the path does today."""
+    shape, inputs, gold = load(name)
+    base = run_basd_loss(shape, inputs, gold, "hard", device="cuda")
+    res = run_basd_loss(shape, _with_dominant_mean(inputs, 5), gold, "hard", device="cuda")
+    assert res["ranks"].tolist() == base["ranks"].tolist()
+    torch.testing.assert_close(res["weights"], base["weights"], atol=2e-6, rtol=0)
+    torch.testing.assert_close(res["loss"], base["loss"], atol=0, rtol=2e-5)
+    torch.testing.assert_close(res["grad_log_temperatures"], base["grad_log_temperatures"], atol=1e-7, rtol=5e-4)
+    for l in inputs["token_layers"]:
+        err = rel_l2(res[f"grad_student_{l}"], base[f"grad_student_{l}"])
+        print(f"  {name} grad_student_{l}: rel-L2 offset vs plain {err:.2e}")
+        assert err < 1e-3, (l, err)     # measured <= 3.0e-4, fp64 floor <= 5.9e-5 (docstring)

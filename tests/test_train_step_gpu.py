@@ -212,6 +212,69 @@ def test_graph_mode_runs_a_ragged_last_batch_eagerly():
     assert logits2.shape[0] == 32 and torch.isfinite(loss2) and trainer.optimizer.k == 3
 
 
+def _make_checkpointed(batch, ckpt, drop=0.1):
+    """c1 with stochastic depth; ``ckpt``: activation checkpointing (model.grad_checkpointing), else the plain step with
+    ``fuse_training`` cleared on every block -- the same unfused block arithmetic without the recomputation"""
+    trainer, b = _make(batch, [f"model.drop_path_rate={drop}", f"model.grad_checkpointing={str(ckpt).lower()}"])
+    assert trainer.model.grad_checkpointing == ckpt
+    for blk in trainer.model.blocks:
+        assert blk.fuse_training != ckpt
+        blk.fuse_training = False
+    return trainer, b
+
+
+def test_checkpointed_eager_step_equals_the_unfused_step():
+    """model.grad_checkpointing (the reference turns it on unconditionally) against the same step without it: identical
+    weights and drop-path masks (same device RNG state); gradients in the flat buffer -- written through the kernels'
+    gradient sinks -- agree per tensor up to atomics, loss and ranks are equal, the health word is clean"""
+    plain, batch = _make_checkpointed(32, False)
+    ckpt, _ = _make_checkpointed(32, True)
+    assert ckpt._segment_spec() is None                  # no two-stage backward under checkpointing
+    torch.testing.assert_close(plain.flat.data, ckpt.flat.data, rtol=0, atol=0)
+    out = {}
+    for name, t in (("plain", plain), ("ckpt", ckpt)):
+        t.flat.zero_grad()
+        torch.manual_seed(7)
+        loss, _ = t._forward_backward(batch["clean"], batch["augmented"], batch["label"])
+        torch.cuda.synchronize()
+        t.check_health()
+        out[name] = (loss, dict(t.basd_loss.layer_selector.subspace_ranks), t.flat.grad.clone())
+    assert out["ckpt"][1] == out["plain"][1]
+    torch.testing.assert_close(out["ckpt"][0], out["plain"][0], rtol=0, atol=0)
+    names = {id(p): n for n, p in list(plain.model.named_parameters()) + list(plain.basd_loss.named_parameters())}
+    diff = {}
+    for p, o in zip(plain.flat.params, plain.flat.offsets):
+        a, b = out["plain"][2][o:o + p.numel()], out["ckpt"][2][o:o + p.numel()]
+        assert float(a.norm()) > 0, names[id(p)]
+        diff[names[id(p)]] = float((a - b).norm() / a.norm())
+    worst = max(diff, key=diff.get)
+    print(f"checkpointed vs plain step: worst per-tensor rel-L2 {diff[worst]:.2e} ({worst})")
+    # not bitwise: the weight-gradient kernels accumulate with fp32 atomics (measured <= 2e-7 per tensor)
+    assert diff[worst] < 1e-5, (worst, diff[worst])
+
+
+@pytest.mark.parametrize("drop", [0.0, 0.1])
+def test_captured_checkpointed_step(drop):
+    """the checkpointed step captures into a hipGraph; without stochastic depth its replays reproduce the eager steps
+    (as test_graph_replay_matches_eager), with it (masks drawn inside the graph) they run clean"""
+    eager, batch = _make_checkpointed(32, True, drop)
+    graphed, _ = _make_checkpointed(32, True, drop)
+    assert graphed.enable_graph(batch), graphed.graph_error
+    assert graphed.pipeline_error is None, graphed.pipeline_error
+    for step in range(3):
+        le, _ = eager.train_step(batch)
+        lg, _ = graphed.train_step(batch)
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(lg))
+        if drop == 0.0:
+            torch.testing.assert_close(lg, le, rtol=1e-5 if step == 0 else 5e-3, atol=0)
+    graphed.check_health()
+    eager.check_health()
+    if drop == 0.0:
+        rel = float((eager.flat.data - graphed.flat.data).norm() / eager.flat.data.norm())
+        assert rel < 2e-3, rel
+
+
 def test_eager_step_is_deterministic_up_to_atomics():
     a, batch = _make(16)
     b, _ = _make(16)
@@ -352,17 +415,26 @@ def _make_preset(student, teacher, batch, img=224, patch=16, extra=()):
     return trainer, b
 
 
-@pytest.mark.parametrize("student,teacher,batch,img,patch", [
-    ("deit_tiny_patch16_224", "vit_base_patch16_224", 8, 224, 16),
-    ("vit_base_patch16_224", "vit_huge_patch14_224", 2, 224, 16),
-    ("deit_tiny_patch16_224", "vit_small_patch16_224", 16, 32, 4)])
-def test_a_train_step_has_no_library_fallback_in_strict_mode(student, teacher, batch, img, patch):
+@pytest.mark.parametrize("student,teacher,batch,img,patch,ckpt", [
+    pytest.param("deit_tiny_patch16_224", "vit_base_patch16_224", 8, 224, 16, False,
+                 id="deit_tiny_patch16_224-vit_base_patch16_224-8-224-16"),
+    pytest.param("vit_base_patch16_224", "vit_huge_patch14_224", 2, 224, 16, False,
+                 id="vit_base_patch16_224-vit_huge_patch14_224-2-224-16"),
+    pytest.param("deit_tiny_patch16_224", "vit_small_patch16_224", 16, 32, 4, False,
+                 id="deit_tiny_patch16_224-vit_small_patch16_224-16-32-4"),
+    pytest.param("deit_tiny_patch16_224", "vit_small_patch16_224", 16, 32, 4, True,
+                 id="deit_tiny_patch16_224-vit_small_patch16_224-16-32-4-checkpointing")])
+def test_a_train_step_has_no_library_fallback_in_strict_mode(student, teacher, batch, img, patch, ckpt):
     """BASELINE configs[1], configs[4] and configs[0] (32 x 32 images, 48-value patches) model pairs at a small batch,
     BASD_STRICT semantics: no ViT block, patch embedding or attention of either model leaves the hand-written kernels
-    during a whole step (the 1000-class head is the one declared library call)"""
+    during a whole step (the 1000-class head is the one declared library call).  ``ckpt``: activation checkpointing with
+    stochastic depth, where every student block takes the unfused branch (own LayerNorm, attention and GEMM kernels)"""
     import basd_amd.losses._ops as O
-    trainer, b = _make_preset(student, teacher, batch, img, patch,
-                              extra=[f"basd.teacher_patch_size={patch}"] if img == 32 else ())
+    extra = [f"basd.teacher_patch_size={patch}"] if img == 32 else []
+    if ckpt:
+        extra += ["model.grad_checkpointing=true", "model.drop_path_rate=0.1"]
+    trainer, b = _make_preset(student, teacher, batch, img, patch, extra=extra)
+    assert trainer.model.grad_checkpointing == ckpt
     O.FALLBACKS.clear()
     O.set_strict(True)
     try:
