@@ -21,6 +21,10 @@
  *   basd_mp_rank           layer_selector.py:17-20 (.median/.sum, on device, no .item())
  *   basd_angle_weights     layer_selector.py:100-108 (acos / spectral weighting / softmax over teacher layers)
  *   basd_angle_weights_bwd autograd of layer_selector.py:86-108 (student frame, angles, softmax, temperatures)
+ *   basd_selector_frames   layer_selector.py:69-74, 133-138 (teacher: MP rank, PCA frame cut at the rank) and
+ *                          :84-92 (student PCA frame), from the Gram statistics of basd_token_gram
+ *   basd_selector_weights  layer_selector.py:93-108 (principal angles between the frames -> mixing weights), plus
+ *                          the seeds basd_angle_weights_bwd takes
  *   basd_mix_tokens        layer_selector.py:110-112 (+ torch.stack :128-129 eliminated)
  *   basd_procrustes_prep   src/losses/relational.py:29-46, src/losses/combined.py:9-14
  *   basd_mix_grad_dots     autograd of layer_selector.py:111-112 w.r.t. the mixing weights
@@ -216,6 +220,37 @@ int basd_angle_weights_bwd(const float* g_w, const float* g_pre_out, const float
                            const float* log_temp, const float* t_seed, const float* v_s, const double* lam_s,
                            const float* proj_s, int E, int L, int D, int D_s, float* g_log_temp, float* w_tok,
                            void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Selector frames of one side from its Gram statistics (reference src/losses/layer_selector.py:69-74, 133-138 for the
+ * teacher, :84-92 for the student).  unc [n, D, D] fp64: uncentred Grams (lower triangles, as
+ * basd_token_gram(..., mirror = False) writes them), csum [n, D] fp64: their column sums, m_rows: tokens per layer.
+ * Centred Gram unc - csum csum^T / m_rows -> eigen-decomposition (basd_pchol_f64 + basd_jacobi_svd) ->
+ *   sigma [n, D] fp32 descending (square roots of the eigenvalues), lam [n, D] fp64 = sigma^2 (nullable),
+ *   v [n, D, D] fp32: row m = unit eigenvector m (zero rows beyond the numerical rank).
+ * with_ranks != 0 (the teacher half): the uncentred Grams are decomposed in the same launches and give
+ *   ranks [n] int32 (basd_mp_rank, capped at D - 1); v rows and sigma entries m >= ranks[b] are then zeroed (the
+ *   reference's frame cut at the rank and the spectral weights sw); lam stays unmasked.
+ * status (nullable device word): BASD_STATUS_* OR-ed in by the Jacobi and the rank count.  D <= 192 (BASD_ERR_SHAPE
+ * otherwise).  workspace: >= basd_selector_frames_workspace_bytes(n, D) bytes of scratch (BASD_ERR_WORKSPACE).  The
+ * shapes and the workspace are checked before anything is enqueued. */
+int64_t basd_selector_frames_workspace_bytes(int n, int D);
+int basd_selector_frames(const double* unc, const double* csum, int n, int64_t m_rows, int D, int with_ranks,
+                         int32_t* ranks, float* sigma, double* lam, float* v, int32_t* status, void* workspace,
+                         int64_t workspace_bytes, void* stream);
+
+/* Selector mixing weights from the two frames (reference src/losses/layer_selector.py:93-108): v_s [E, D, D] fp32
+ * (student frames, basd_selector_frames with_ranks = 0), ranks [L] int32, vm_t [L, D, D] fp32, sw [L, D] fp32 (teacher
+ * frames, with_ranks != 0), log_temp [E] fp32 ->
+ *   weights, pre, d2 [E, L] fp32 as basd_angle_weights, and t_seed [E, L, D, D] fp32: the backward seeds
+ *   A_full A_bar^T Phi (rows b >= k_j only) with A_full = V_s V_t^T, A_bar its rows b < k_j and Phi the coefficient
+ *   form of basd_angle_weights -- exactly the inputs of basd_angle_weights_bwd.
+ * The four products run on the fp32-input matrix cores, one launch each over the E L pairs; the principal angles come
+ * from the rank-masked basd_jacobi_svd.  status as above.  L <= 64, D <= 192 (BASD_ERR_SHAPE otherwise).
+ * workspace: >= basd_selector_weights_workspace_bytes(E, L, D) bytes (BASD_ERR_WORKSPACE). */
+int64_t basd_selector_weights_workspace_bytes(int E, int L, int D);
+int basd_selector_weights(const float* v_s, const int32_t* ranks, const float* vm_t, const float* sw,
+                          const float* log_temp, int E, int L, int D, float* weights, float* pre, float* d2,
+                          float* t_seed, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* mixed[i] = sum_j w[i, j] * x_j   (all E mixes from ONE pass over the teacher layers)
  * x_layers: HOST array of L device pointers to [elems] tensors (dtype code; the pointers are

@@ -30,7 +30,8 @@ EXPORTS = (
     "basd_gemm_bf16_gelu_fwd", "basd_gemm_bf16_gelu_bwd", "basd_gemm_bf16x3_f32", "basd_layernorm_fwd_bf16", "basd_layernorm_bwd_bf16",
     "basd_cls_importance_bf16", "basd_add_layernorm_fwd_bf16", "basd_procrustes_bwd_rows", "basd_attention_fwd_bf16", "basd_attention_fwd_qmean_bf16", "basd_attention_bwd_bf16",
     "basd_split_bf16x2_table", "basd_split_patches_bf16x2", "basd_gemm_f32x3", "basd_attention_fwd_f32x3",
-    "basd_add_layernorm_fwd_f32",
+    "basd_add_layernorm_fwd_f32", "basd_selector_frames_workspace_bytes", "basd_selector_frames",
+    "basd_selector_weights_workspace_bytes", "basd_selector_weights",
 )
 
 
@@ -59,6 +60,10 @@ _SIGNATURES = {
     "basd_procrustes_bwd_workspace_bytes": (_I, _I),
     "basd_angle_weights_bwd_workspace_bytes": (_I, _I, _I),
     "basd_angle_weights_bwd": (_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I64, _P),
+    "basd_selector_frames_workspace_bytes": (_I, _I),
+    "basd_selector_frames": (_P, _P, _I, _I64, _I, _I, _P, _P, _P, _P, _P, _P, _I64, _P),
+    "basd_selector_weights_workspace_bytes": (_I, _I, _I),
+    "basd_selector_weights": (_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I64, _P),
     "basd_procrustes_bwd": (_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I64, _P),
     "basd_ce_uwso": (_P, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P),
     "basd_transpose_bf16_table": (_P, _P, _P, _I, _P),
@@ -475,6 +480,53 @@ def angle_weights_bwd(g_w, g_pre_out, wts, d2, log_temp, t_seed, v_s, lam_s, pro
                                         _ptr(v_s), _ptr(lam_s), _ptr(proj_s), e, l, d, d_s, _ptr(g_lt), _ptr(w_tok),
                                         _ptr(ws), ctypes.c_int64(ws.numel()), _stream()), "basd_angle_weights_bwd")
     return g_lt, w_tok
+
+
+SELECTOR_MAX_D = 192         # widest frame the selector entries take (the LDS-resident eigensolver)
+
+
+def selector_frames(unc: torch.Tensor, csum: torch.Tensor, m_rows: int, with_ranks: bool):
+    """Selector frames of one side as ONE C call (basd_selector_frames): unc [n, D, D] fp64 uncentred Grams (lower
+    triangles), csum [n, D] fp64 column sums, m_rows tokens per layer -> (ranks int32 [n] | None, sigma [n, D] fp32,
+    lam [n, D] fp64, v [n, D, D] fp32); with ranks, sigma and the rows of v are masked at the rank."""
+    _need_cuda(unc, csum)
+    unc = unc.detach().contiguous().double()
+    csum = csum.detach().contiguous().double()
+    n, d, _ = unc.shape
+    assert csum.shape == (n, d)
+    dev = unc.device
+    ranks = torch.empty(n, dtype=torch.int32, device=dev) if with_ranks else None
+    sigma = torch.empty(n, d, dtype=torch.float32, device=dev)
+    lam = torch.empty(n, d, dtype=torch.float64, device=dev)
+    v = torch.empty(n, d, d, dtype=torch.float32, device=dev)
+    ws = torch.empty(int(lib().basd_selector_frames_workspace_bytes(n, d)), dtype=torch.uint8, device=dev)
+    _check(lib().basd_selector_frames(_ptr(unc), _ptr(csum), n, ctypes.c_int64(m_rows), d, int(with_ranks), _ptr(ranks),
+                                      _ptr(sigma), _ptr(lam), _ptr(v), _ptr(status_word(dev)), _ptr(ws),
+                                      ctypes.c_int64(ws.numel()), _stream()), "basd_selector_frames")
+    return ranks, sigma, lam, v
+
+
+def selector_weights(v_s: torch.Tensor, ranks: torch.Tensor, vm_t: torch.Tensor, sw: torch.Tensor,
+                     log_temp: torch.Tensor):
+    """Selector weights as ONE C call (basd_selector_weights): v_s [E, D, D] student frames, ranks [L] int32, vm_t
+    [L, D, D] / sw [L, D] rank-masked teacher frames, log_temp [E] -> (weights, pre, d2 [E, L] fp32,
+    t_seed [E, L, D, D] fp32: the seeds basd_angle_weights_bwd takes)."""
+    _need_cuda(v_s, ranks, vm_t, sw, log_temp)
+    f32 = lambda t_: t_.detach().contiguous().float()
+    v_s, vm_t, sw, log_temp = map(f32, (v_s, vm_t, sw, log_temp))
+    ranks = ranks.detach().contiguous().int()
+    e, d, _ = v_s.shape
+    l = vm_t.shape[0]
+    assert vm_t.shape == (l, d, d) and sw.shape == (l, d) and ranks.numel() == l and log_temp.numel() == e
+    dev = v_s.device
+    wts = torch.empty(e, l, dtype=torch.float32, device=dev)
+    pre, d2 = torch.empty_like(wts), torch.empty_like(wts)
+    t_seed = torch.empty(e, l, d, d, dtype=torch.float32, device=dev)
+    ws = torch.empty(int(lib().basd_selector_weights_workspace_bytes(e, l, d)), dtype=torch.uint8, device=dev)
+    _check(lib().basd_selector_weights(_ptr(v_s), _ptr(ranks), _ptr(vm_t), _ptr(sw), _ptr(log_temp), e, l, d, _ptr(wts),
+                                       _ptr(pre), _ptr(d2), _ptr(t_seed), _ptr(status_word(dev)), _ptr(ws),
+                                       ctypes.c_int64(ws.numel()), _stream()), "basd_selector_weights")
+    return wts, pre, d2, t_seed
 
 
 def _ptr_table(layers: list[torch.Tensor]):

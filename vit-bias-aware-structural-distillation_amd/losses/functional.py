@@ -375,6 +375,13 @@ def _layer_grams(tokens, proj, grams=None):
     return unc, csum
 
 
+def _selector_entries(ops, t, d: int) -> bool:
+    """The selector forward runs as the two C entries (basd_selector_frames / basd_selector_weights) when the provider
+    has them, takes these tensors and the frames fit the LDS-resident eigensolver; otherwise the torch composition
+    below (wide students, other providers)."""
+    return getattr(ops, "selector_weights", None) is not None and ops.handles(t) and d <= WIDE_PANEL
+
+
 def teacher_frames(teacher_tokens, proj_t, grams=None):
     """Teacher half of the selector (no gradient): per-layer Gram statistics -> MP ranks (device
     int32, no host sync) and rank-masked PCA frames.  Reference layer_selector.py:69-74, 133-138.
@@ -387,6 +394,11 @@ def teacher_frames(teacher_tokens, proj_t, grams=None):
     D = proj_t.shape[0]
     m_t = teacher_tokens[0].shape[0] * teacher_tokens[0].shape[1]
     unc, csum = _layer_grams(teacher_tokens, proj_t, grams)              # layer_selector.py:71-73, :134-136
+    if _selector_entries(ops, unc, D):
+        # centring, both eigen-decompositions, MP ranks and the rank masks in one C call
+        ranks, sw, _, vm_t = ops.selector_frames(unc, csum, m_t, with_ranks=True)
+        keep = (torch.arange(D, device=unc.device).unsqueeze(0) < ranks.unsqueeze(1)).float()
+        return {"ranks": ranks, "keep": keep, "vm_t": vm_t, "sw": sw}
     cen = unc - csum.unsqueeze(2) * csum.unsqueeze(1) / m_t              # centred Gram of every layer at once
     sigma, u, _ = psd_eig(torch.cat([unc, cen]), lower_only=True)
     ranks = ops.mp_rank(sigma[:L] ** 2, m_t, D, D - 1)  # int32 [L], stays on device
@@ -412,11 +424,16 @@ def teacher_ranks(teacher_tokens, proj_t) -> torch.Tensor:
 @torch.no_grad()
 def student_frames(student_tokens, proj_s):
     """Student half of the selector statistics (centred Gram eigen-decomposition per extraction point):
-    (sigma [E, D], v [E, D, D]).  No gradient flows through these tensors themselves -- the selector backward
+    (sigma [E, D], v [E, D, D]) -- and lam [E, D] = sigma^2 in fp64 as a third entry when the C entry formed it.
+    No gradient flows through these tensors themselves -- the selector backward
     differentiates the eigen-decomposition analytically from them -- so a trainer may compute them ahead of the
     loss (reference layer_selector.py:84-92)."""
     m_s = student_tokens[0].shape[0] * student_tokens[0].shape[1]
     unc, csum = _layer_grams([s.detach() for s in student_tokens], proj_s)
+    ops = get_ops()
+    if _selector_entries(ops, unc, proj_s.shape[0]):
+        _, sigma_s, lam_s, v_s = ops.selector_frames(unc, csum, m_s, with_ranks=False)
+        return sigma_s, v_s, lam_s
     sigma_s, v_s, _ = psd_eig(unc - csum.unsqueeze(2) * csum.unsqueeze(1) / m_s, lower_only=True)
     return sigma_s, v_s
 
@@ -429,11 +446,20 @@ class _SelectorWeightsFn(torch.autograd.Function):
         D = proj_s.shape[0]
         dev = proj_s.device
 
-        sigma_s, v_s = pre_s if pre_s is not None else student_frames(student, proj_s)
-        lam_s = sigma_s.double() ** 2
+        sigma_s, v_s, *lam = pre_s if pre_s is not None else student_frames(student, proj_s)
+        lam_s = lam[0] if lam else sigma_s.double() ** 2
         if ready is not None:
             ready()           # join the stream that produced the teacher frames only now: the student's own
                               # (latency-bound, 8-workgroup) eigen-solve above overlaps the teacher's
+
+        if _selector_entries(ops, v_s, D):
+            # products, masks, rank-masked Jacobi, angle weights and the backward seeds in one C call
+            # (basd_selector_weights: four fp32-MFMA batched products, no library GEMM)
+            wts, pre, d2, t_seed = ops.selector_weights(v_s, ranks, vm_t, sw, log_temp)
+            tau = F.softplus(log_temp.float())
+            ctx.save_for_backward(log_temp, proj_s, wts, d2, tau, t_seed, v_s, lam_s, *student)
+            ctx.n_student = E
+            return wts, pre
 
         # The small products of the selector (E L matrices of D x D, plus four [M, D_s] x [D_s, D_s] products in the
         # backward) stay on torch.matmul: moved to the own fp64-accumulated batched GEMM they cost +2.4 ms per c2 step
