@@ -50,6 +50,9 @@
  *   basd_attention_fwd_bf16, basd_attention_fwd_qmean_bf16, basd_cls_importance_bf16
  *                          timm Attention.forward of the frozen teacher (teacher.py:118 creates it) and the
  *                          attention capture hook src/models/teacher.py:27-39 + relational.py:22-27
+ *   basd_attention_fwd_long_bf16, basd_attention_bwd_long_bf16
+ *                          the same forward (with both taps) and backward for 1 <= T <= 1024 tokens (hd 64 | 80):
+ *                          /14 grids, 384 px inputs and hd-80 students, where the kernels above refuse the shape
  *   basd_layernorm_fwd_bf16 / _bwd_bf16, basd_add_layernorm_fwd_bf16
  *                          timm nn.LayerNorm of the ViT blocks (student: with backward; frozen teacher: fused with
  *                          the residual add in front of it)
@@ -397,6 +400,26 @@ int basd_attention_fwd_qmean_bf16(const void* qkv, int B, int T, int H, int hd, 
  * products like a flash kernel.  hd == 64, T <= 224. */
 int basd_attention_bwd_bf16(const void* qkv, const void* out, const void* dout, const float* lse, int B, int T, int H,
                             int hd, float scale, void* dqkv, void* stream);
+
+/* Tiled (flash) attention forward for 1 <= T <= 1024, hd 64 | 80: the contract of basd_attention_fwd_bf16 /
+ * basd_attention_fwd_qmean_bf16 at token counts they refuse.  qkv [B, T, 3, H, hd] bf16 ->
+ *   out [B, T, H * hd] bf16 (nullable: then only the CLS tap is computed), lse [B, H, T] fp32 (nullable unless the
+ *   query-mean tap is asked for: it reads the LSE back), cls_importance [B, H, T-1] fp32 (nullable, T >= 2: per head
+ *   the CLS-row softmax of basd_cls_importance_bf16 divided by H), qmean_importance [B, H, T] fp32 (nullable, needs out
+ *   and lse: per head sum_q softmax(q . k * scale)[q][key] / (H T), summed in a fixed order).
+ * The taps are summed over the H axis by the caller.  BASD_ERR_SHAPE outside the range. */
+int basd_attention_fwd_long_bf16(const void* qkv, int B, int T, int H, int hd, float scale, void* out,
+                                 float* cls_importance, float* qmean_importance, float* lse, void* stream);
+
+/* Tiled (FA2) attention backward for 1 <= T <= 1024, hd 64 | 80: the contract of basd_attention_bwd_bf16 (lse from
+ * basd_attention_fwd_bf16 or basd_attention_fwd_long_bf16).  The workspace (workspace_bytes >=
+ * basd_attention_bwd_long_workspace_bytes(B, T, H, hd), else BASD_ERR_WORKSPACE) holds delta = rowsum(dO * O) and one
+ * fp32 dQ partial per 128-key block, added in key-block order: the result is bitwise reproducible.  No allocation, no
+ * synchronisation. */
+int64_t basd_attention_bwd_long_workspace_bytes(int B, int T, int H, int hd);
+int basd_attention_bwd_long_bf16(const void* qkv, const void* out, const void* dout, const float* lse, int B, int T,
+                                 int H, int hd, float scale, void* dqkv, void* workspace, int64_t workspace_bytes,
+                                 void* stream);
 
 /* Forward of the attention-weighted Procrustes term between basd_procrustes_prep and the loss value, as one chain of
  * launches on a caller-provided workspace (src/losses/relational.py:47-48: cross = s_w^T t_w, its nuclear norm, and

@@ -31,7 +31,8 @@ EXPORTS = (
     "basd_cls_importance_bf16", "basd_add_layernorm_fwd_bf16", "basd_procrustes_bwd_rows", "basd_attention_fwd_bf16", "basd_attention_fwd_qmean_bf16", "basd_attention_bwd_bf16",
     "basd_split_bf16x2_table", "basd_split_patches_bf16x2", "basd_gemm_f32x3", "basd_attention_fwd_f32x3",
     "basd_add_layernorm_fwd_f32", "basd_selector_frames_workspace_bytes", "basd_selector_frames",
-    "basd_selector_weights_workspace_bytes", "basd_selector_weights",
+    "basd_selector_weights_workspace_bytes", "basd_selector_weights", "basd_attention_fwd_long_bf16",
+    "basd_attention_bwd_long_workspace_bytes", "basd_attention_bwd_long_bf16",
 )
 
 
@@ -84,6 +85,9 @@ _SIGNATURES = {
     "basd_attention_fwd_bf16": (_P, _I, _I, _I, _I, _F, _P, _P, _P, _P),
     "basd_attention_fwd_qmean_bf16": (_P, _I, _I, _I, _I, _F, _P, _P, _P),
     "basd_attention_bwd_bf16": (_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P),
+    "basd_attention_fwd_long_bf16": (_P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P),
+    "basd_attention_bwd_long_workspace_bytes": (_I, _I, _I, _I),
+    "basd_attention_bwd_long_bf16": (_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _I64, _P),
     "basd_sf_adamw_step": (_P, _P, _P, _P, _I64, _D, _D, _D, _D, _D, _D, _D, _P),
     "basd_lerp": (_P, _P, _I64, _F, _P),
     "basd_split_bf16x2_table": (_P, _I, _P),
@@ -922,8 +926,21 @@ def wgrad_bf16(dy: torch.Tensor, x: torch.Tensor, need_bias: bool = True, out_w:
     return dw, db
 
 
-def cls_importance_supported(t: int, hd: int) -> bool:
+# Attention past the single-workgroup kernels (csrc/attention_long.hip): 1 <= T <= LONG_ATTENTION_MAX_T, hd 64 | 80.
+# The entries below call the long kernels ONLY for shapes the short ones refuse.
+LONG_ATTENTION_MAX_T = 1024
+
+
+def _long_attention_ok(t: int, hd: int) -> bool:
+    return hd in (64, 80) and 1 <= t <= LONG_ATTENTION_MAX_T
+
+
+def _short_cls_importance_ok(t: int, hd: int) -> bool:
     return 2 <= t <= 320 and hd in (32, 64, 80)
+
+
+def cls_importance_supported(t: int, hd: int) -> bool:
+    return _short_cls_importance_ok(t, hd) or (t >= 2 and _long_attention_ok(t, hd))
 
 
 def cls_importance(qkv: torch.Tensor, heads: int, head_dim: int, scale: float) -> torch.Tensor:
@@ -932,14 +949,29 @@ def cls_importance(qkv: torch.Tensor, heads: int, head_dim: int, scale: float) -
     assert qkv.dtype == torch.bfloat16 and qkv.shape[-1] == 3 * heads * head_dim
     qkv = qkv.contiguous()
     b, t = qkv.shape[0], qkv.shape[1]
+    if not _short_cls_importance_ok(t, head_dim):
+        imp = torch.empty(b, heads, t - 1, dtype=torch.float32, device=qkv.device)
+        _check(lib().basd_attention_fwd_long_bf16(_ptr(qkv), b, t, heads, head_dim, ctypes.c_float(scale), _ptr(None),
+                                                  _ptr(imp), _ptr(None), _ptr(None), _stream()),
+               "basd_attention_fwd_long_bf16")
+        return imp.sum(dim=1)
     out = torch.empty(b, t - 1, dtype=torch.float32, device=qkv.device)
     _check(lib().basd_cls_importance_bf16(_ptr(qkv), b, t, heads, head_dim, ctypes.c_float(scale), _ptr(out), _stream()),
            "basd_cls_importance_bf16")
     return out
 
 
-def attention_fwd_supported(t: int, hd: int) -> bool:
+def _short_attention_fwd_ok(t: int, hd: int) -> bool:
     return hd in (64, 80) and 1 <= t <= 272
+
+
+def attention_fwd_supported(t: int, hd: int) -> bool:
+    return _short_attention_fwd_ok(t, hd) or _long_attention_ok(t, hd)
+
+
+def attention_fwd_f32x3_supported(t: int, hd: int) -> bool:
+    """the fp32 split-bf16 evaluation attention (``attention_fwd_f32x3``) has no long-sequence kernel"""
+    return _short_attention_fwd_ok(t, hd)
 
 
 def attention_fwd(qkv: torch.Tensor, heads: int, head_dim: int, scale: float, want_importance: bool = False,
@@ -954,6 +986,8 @@ def attention_fwd(qkv: torch.Tensor, heads: int, head_dim: int, scale: float, wa
     qkv = qkv.contiguous()
     b, t = qkv.shape[0], qkv.shape[1]
     out = torch.empty(b, t, heads * head_dim, dtype=torch.bfloat16, device=qkv.device)
+    if not _short_attention_fwd_ok(t, head_dim):
+        return _attention_fwd_long(qkv, out, heads, head_dim, scale, want_importance, want_lse, query_mean)
     if want_importance and query_mean:
         assert not want_lse
         imp = torch.empty(b, heads, t, dtype=torch.float32, device=qkv.device)
@@ -968,8 +1002,29 @@ def attention_fwd(qkv: torch.Tensor, heads: int, head_dim: int, scale: float, wa
     return (out, imp, lse) if want_lse else (out, imp)
 
 
-def attention_bwd_supported(t: int, hd: int) -> bool:
+def _attention_fwd_long(qkv, out, heads, head_dim, scale, want_importance, want_lse, query_mean):
+    b, t = qkv.shape[0], qkv.shape[1]
+    cls = qm = None
+    if want_importance and query_mean:
+        assert not want_lse
+        qm = torch.empty(b, heads, t, dtype=torch.float32, device=qkv.device)
+    elif want_importance:
+        cls = torch.empty(b, heads, t - 1, dtype=torch.float32, device=qkv.device)
+    lse = torch.empty(b, heads, t, dtype=torch.float32, device=qkv.device) if (want_lse or qm is not None) else None
+    _check(lib().basd_attention_fwd_long_bf16(_ptr(qkv), b, t, heads, head_dim, ctypes.c_float(scale), _ptr(out),
+                                              _ptr(cls), _ptr(qm), _ptr(lse), _stream()), "basd_attention_fwd_long_bf16")
+    if qm is not None:
+        return out, qm.sum(dim=1)
+    imp = cls.sum(dim=1) if cls is not None else None
+    return (out, imp, lse) if want_lse else (out, imp)
+
+
+def _short_attention_bwd_ok(t: int, hd: int) -> bool:
     return hd == 64 and 1 <= t <= 224
+
+
+def attention_bwd_supported(t: int, hd: int) -> bool:
+    return _short_attention_bwd_ok(t, hd) or _long_attention_ok(t, hd)
 
 
 def attention_bwd(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor, heads: int,
@@ -981,6 +1036,15 @@ def attention_bwd(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, lse:
     assert qkv.is_contiguous() and out.is_contiguous() and lse.is_contiguous() and lse.shape == (b, heads, t)
     dout = dout.to(torch.bfloat16).contiguous()
     dqkv = torch.empty_like(qkv)
+    if not _short_attention_bwd_ok(t, head_dim):
+        need = int(lib().basd_attention_bwd_long_workspace_bytes(b, t, heads, head_dim))
+        rec = _scratch("attention_bwd_long", qkv.device, need)
+        _check(lib().basd_attention_bwd_long_bf16(_ptr(qkv), _ptr(out), _ptr(dout), _ptr(lse), b, t, heads, head_dim,
+                                                  ctypes.c_float(scale), _ptr(dqkv), _ptr(rec.buf),
+                                                  ctypes.c_int64(rec.buf.numel()), _stream()),
+               "basd_attention_bwd_long_bf16")
+        _scratch_used(rec)
+        return dqkv
     _check(lib().basd_attention_bwd_bf16(_ptr(qkv), _ptr(out), _ptr(dout), _ptr(lse), b, t, heads, head_dim,
                                          ctypes.c_float(scale), _ptr(dqkv), _stream()), "basd_attention_bwd_bf16")
     return dqkv
