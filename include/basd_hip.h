@@ -5,7 +5,8 @@
  * (passed as void*), never allocates / frees / synchronises the device, and
  * returns an int status (0 = ok).  basd_last_error() returns a thread-local
  * message for the last non-zero status.  No C++ exception crosses this
- * boundary, no torch type appears in any signature.
+ * boundary, no torch type appears in any signature.  The library reads no
+ * environment variables: which kernel runs depends on the arguments alone.
  *
  * The reference project is pure Python and has no FFI layer; the entries
  * below replace the library calls its loss path makes (citations are
@@ -87,14 +88,14 @@ extern "C" {
 #define BASD_STATUS_NONFINITE 2      /* NaN / Inf among the singular values (non-finite input)               */
 #define BASD_STATUS_RANK0 4          /* Marchenko-Pastur rank 0: the reference divides by sum(sw) = 0 here   */
 /* bits 8 .. 27: diagnostics OR-ed in with BASD_STATUS_NONCONVERGED (informational): bits 8-11 the Jacobi kernel variant
- * (1 LDS-resident, 2 / 3 odd-even with a double / single mailbox, 4 two matrices per workgroup, 5 block ordering),
+ * (2 / 3 odd-even with a double / single mailbox, 6 quad-block, 7 hex-block; 1, 4, 5: kernels that no longer exist),
  * bits 12-27 the index of the matrix in its launch (saturating at 65535) */
 
 #define BASD_DTYPE_F32 0
 #define BASD_DTYPE_BF16 1
 #define BASD_DTYPE_F64 2
 
-/* largest matrix the LDS-resident Jacobi accepts: cols * ld(rows) * 4 <= 160 KiB - scratch */
+/* widest Jacobi input, and the LDS a Jacobi workgroup may use (the mailboxes of the register-resident kernels) */
 #define BASD_JACOBI_MAX_COLS 256
 #define BASD_JACOBI_LDS_BYTES 163840
 
@@ -175,14 +176,14 @@ int basd_trinv_f64_masked(const double* lwork, const int32_t* piv, const int32_t
  * active (optional, device int32 [batch], may be NULL): matrix b has non-zero entries only in its
  * leading active[b] columns (and rows, if active_rows != 0); the sweeps then run over that
  * block only (rank-masked principal-angle problems, no host sync on the ranks).  active[b] < 0 skips matrix b
- * altogether (w, sigma untouched, sweeps[b] = 0; register-resident single-matrix kernels, i.e. batch < 512 or tall /
- * single-mailbox shapes): converged matrices of a block tournament cost a 5 us launch instead of a sweep.
- * active_rows == 2 declares `active` a pure MASK -- every entry is either < 0 (skip) or n_cols (solve completely) --
- * which the block-ordering kernel of the large batches honours too.
+ * altogether (w, sigma untouched, sweeps[b] = 0): converged matrices of a block tournament cost a 5 us launch instead
+ * of a sweep.
+ * active_rows == 2 declares `active` a pure MASK -- every entry is either < 0 (skip) or n_cols (solve completely).
  * status (optional, device int32 word, may be NULL): BASD_STATUS_NONCONVERGED / BASD_STATUS_NONFINITE are OR-ed in.
- * Requires n_cols <= 256, ld % 4 == 0 and either n_cols * ld * 4 + 4096 <= 160 KiB (matrix resident in LDS) or the
- * register-resident forms: m_rows <= 224, or m_rows <= 384 with n_cols <= 192 (tall block pairs; with max_sweeps = 1
- * and sort = 0 this is one visit of a block-Jacobi tournament over wider matrices). */
+ * Requires n_cols <= 256, ld % 4 == 0, m_rows <= ld and one of: m_rows <= 224; m_rows <= 256 with n_cols <= 196;
+ * m_rows <= 384 with n_cols <= 192 (tall block pairs; with max_sweeps = 1 and sort = 0 this is one visit of a
+ * block-Jacobi tournament over wider matrices).  Anything else is BASD_ERR_SHAPE, at every batch size.  The kernel is
+ * chosen from (m_rows, n_cols) alone (the hex-block kernel also looks at batch > 256 for its occupancy). */
 int basd_jacobi_svd(float* w, int batch, int m_rows, int n_cols, int ld, int norm_rows,
                     float tol, int max_sweeps, int sort,
                     float* sigma, int32_t* sweeps, const int32_t* active, int active_rows,

@@ -34,7 +34,6 @@ def run(n, batch, group, spread, seed=7, tag=""):
         print(f"   matrix {b}: sweeps {int(sw[b])}, worst sigma indices {torch.topk(e, 4).indices.tolist()} errs {torch.topk(e, 4).values.tolist()}")
 
 
-tag = "B4" if os.environ.get("BASD_JACOBI_B4", "1") != "0" else "BLK"
 for (n, batch, group, spread) in [(96, 64, 8, 1e-6), (96, 64, 8, 1e-3), (96, 64, 2, 1e-6), (96, 64, 8, 0.0), (192, 64, 8, 1e-6),
                                   (192, 64, 1, 0.0), (96, 64, 96, 1e-6), (64, 64, 8, 1e-6)]:
-    run(n, batch, group, spread, tag=tag)
+    run(n, batch, group, spread, tag="B6" if n > 128 else "B4")     # hex-block above 128 columns, else quad-block

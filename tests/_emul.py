@@ -51,6 +51,7 @@ def jacobi_ld(m_rows: int) -> int:
 
 
 def jacobi_fits(n_cols: int, m_rows: int) -> bool:
+    """The host code's size rule, as basd_amd._native.jacobi_fits."""
     return n_cols <= 256 and n_cols * jacobi_ld(m_rows) * 4 + 520 * 4 <= JACOBI_LDS_BYTES
 
 

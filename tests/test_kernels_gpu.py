@@ -34,7 +34,13 @@ def _colmajor(a: torch.Tensor, ld: int) -> torch.Tensor:
                                        # rows): ragged last blocks (n % 6, n % 12), a phantom block, one / two / three row chunks,
                                        # two matrices per CU (batch > 256)
                                        (192, 130, 3), (150, 150, 2), (176, 191, 2), (64, 180, 2), (120, 133, 300),
-                                       (384, 192, 3), (300, 170, 2)])
+                                       (384, 192, 3), (300, 170, 2),
+                                       # fewer than 8 columns at batch >= 512: the double-buffered odd-even kernel, one
+                                       # matrix per workgroup
+                                       (40, 7, 513),
+                                       # more than 204 columns of 129 .. 192 rows: the single-mailbox odd-even kernel
+                                       # <7, 1, 1> holding six row chunks
+                                       (160, 210, 2)])
 def test_jacobi_singular_values_and_invariants(nat, m, n, batch):
     g = torch.Generator().manual_seed(m * 1000 + n)
     a = torch.randn(batch, m, n, generator=g)
@@ -732,7 +738,8 @@ def test_batch_strided_views_are_consumed_without_copy(nat, dtype):
 
 
 def test_jacobi_two_matrices_per_workgroup_path(nat):
-    """batch >= 512 takes the NMAT = 2 kernel (odd batch: the last workgroup carries one matrix)."""
+    """An odd batch above 512 of 40 x 33: the quad-block kernel (jacobi_b4_kernel<1, 16>), one matrix per workgroup
+    at every batch size."""
     g = torch.Generator().manual_seed(21)
     batch, m, n = 513, 40, 33
     a = torch.randn(batch, m, n, generator=g) * torch.logspace(0, -3, n).view(1, 1, n)
@@ -908,8 +915,9 @@ def test_attention_fwd_query_mean_tap(nat, B, T, H, hd):
 
 @pytest.mark.parametrize("m,n", [(192, 192), (100, 100), (60, 50), (40, 10), (96, 21)])
 def test_jacobi_block_ordering_large_batch(nat, m, n):
-    """batches >= 512 take the block-ordering kernel (two columns per side and slot): singular values,
-    orthogonality of the rotated columns and the invariance of A A^T, incl. an odd number of blocks"""
+    """batch 512 on the block kernels (192 x 192: hex-block jacobi_b6_kernel, the others: quad-block
+    jacobi_b4_kernel): singular values, orthogonality of the rotated columns and the invariance of A A^T, incl. an
+    odd number of blocks"""
     batch = 512
     g = torch.Generator().manual_seed(m * 31 + n)
     a = torch.randn(batch, m, n, generator=g) * torch.logspace(0, -3, n).unsqueeze(0).unsqueeze(0)

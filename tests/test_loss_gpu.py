@@ -74,7 +74,7 @@ def _big_fixture(name, grad_tol=5e-4):
 
 
 def test_c2_bench_batch_parity():
-    """BASELINE c2 at the BENCHMARKED per-GPU batch (256): E*B = 1024 Procrustes cores -> jacobi_blk_kernel, the
+    """BASELINE c2 at the BENCHMARKED per-GPU batch (256): E*B = 1024 Procrustes cores -> jacobi_b6_kernel (hex-block), the
     1024-matrix pchol_reg / trinv_blocked launches and the aligned fp64 GEMM, all against the reference itself."""
     _big_fixture("c2_b256")
 

@@ -212,7 +212,7 @@ def check_status(device=None) -> None:
 
 
 def jacobi_ld(m_rows: int) -> int:
-    """Column stride used for LDS-resident Jacobi inputs (multiple of 4, not of 32)."""
+    """Column stride used for Jacobi inputs (multiple of 4, not of 32)."""
     ld = (m_rows + 3) // 4 * 4
     if ld % 32 == 0:
         ld += 4
@@ -425,6 +425,9 @@ def jacobi_svd(w: torch.Tensor, m_rows: int, norm_rows: int | None = None, *, to
 
 
 def jacobi_fits(n_cols: int, m_rows: int) -> bool:
+    """Size rule of the host code (layouts, which Procrustes side is taken): the matrix with its padded columns fits
+    160 KiB.  It was the bound of an LDS-resident kernel that no longer exists; the value is kept because changing it
+    changes results.  basd_jacobi_svd has its own, narrower shape check."""
     return n_cols <= 256 and n_cols * jacobi_ld(m_rows) * 4 + 520 * 4 <= JACOBI_LDS_BYTES
 
 

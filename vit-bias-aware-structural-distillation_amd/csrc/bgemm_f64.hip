@@ -10,7 +10,6 @@
 // 2x2 MFMA tiles), K chunks of 16 staged through LDS in fp64, k-major so the
 // A/B fragments (one f64 per lane: A[i = lane&15][k = lane>>4]) are read from
 // consecutive addresses.
-#include <stdlib.h>
 #include "basd_common.h"
 
 namespace basd {
@@ -509,16 +508,13 @@ extern "C" int basd_bgemm_f64_masked(const void* a, int a_dtype, int64_t a_strid
   const int key = a_dtype * 100 + b_dtype * 10 + c_dtype;
   const bool aligned = M % 4 == 0 && N % 4 == 0 && K % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 &&
                        a_stride % 4 == 0 && b_stride % 4 == 0 && ((uintptr_t)a & 31) == 0 && ((uintptr_t)b & 31) == 0;
-  // C = X X^T of one row-major operand into fp64: the balanced Gram kernel (BASD_GRAM_ROWS=0: the generic tiles)
+  // C = X X^T of one row-major operand into fp64: the balanced Gram kernel
   if (symmetric && a == b && a_dtype == b_dtype && a_stride == b_stride && lda == ldb && !trans_a && trans_b &&
       c_dtype == BASD_DTYPE_F64 && aligned && skip == nullptr && M >= 64 && (M % 64) <= GRAM_RMAX &&
       (size_t)(M % 64) * K * 8 <= 65536) {
-    const char* env = getenv("BASD_GRAM_ROWS");
-    if (!(env && env[0] == '0')) {
-      if (a_dtype == BASD_DTYPE_F32) launch_gram_rows<float>(a, a_stride, lda, c, c_stride, ldc, batch, M, K, st);
-      else launch_gram_rows<double>(a, a_stride, lda, c, c_stride, ldc, batch, M, K, st);
-      return check_launch("bgemm_f64 (symmetric Gram)");
-    }
+    if (a_dtype == BASD_DTYPE_F32) launch_gram_rows<float>(a, a_stride, lda, c, c_stride, ldc, batch, M, K, st);
+    else launch_gram_rows<double>(a, a_stride, lda, c, c_stride, ldc, batch, M, K, st);
+    return check_launch("bgemm_f64 (symmetric Gram)");
   }
 #define BASD_BG(TA, TB, TC)                                                                                          \
   do {                                                                                                               \

@@ -1,16 +1,12 @@
-// Batched one-sided (Hestenes) Jacobi SVD, one matrix per workgroup, matrix
-// resident in LDS (column-major, fp32).  Replaces the torch.linalg.svd /
+// Batched one-sided (Hestenes) Jacobi SVD, one matrix per workgroup, the columns
+// resident in registers (column-major, fp32).  Replaces the torch.linalg.svd /
 // svdvals / eigvalsh / matrix_norm('nuc') calls of the reference loss path
 // (src/losses/layer_selector.py:16,36,92,99; src/losses/relational.py:48).
 //
 // Layout: column c at W + c*ld, rows 0..m-1 significant, rows m..ld-1 zero.
-// Work split: an aligned group of 8 lanes owns one column pair per step; each
-// lane holds rows {4*sub + 32*ch + 0..3} of both columns in registers
-// (ds_read_b128), the three dot products are reduced across the 8 lanes with
-// DPP (no LDS traffic), every lane computes the rotation redundantly and
-// writes its rows back.  Pairs of a step are disjoint (round-robin "circle"
-// ordering), one workgroup barrier per step.
-#include <stdlib.h>
+// Three kernels, chosen by shape alone in basd_jacobi_svd at the end of this file (DESIGN.md has the route table):
+// hex-block and quad-block ordering with scaled rotations for up to 196 columns, odd-even ordering of single
+// columns for everything else that is accepted.
 #include "basd_common.h"
 
 namespace basd {
@@ -31,8 +27,8 @@ namespace basd {
 // all max_sweeps sweeps and was still rotating, BASD_STATUS_NONFINITE when a singular value is NaN / Inf (a NaN input
 // makes every rotation test false, so such a matrix "converges" at once and would otherwise pass silently).
 // Bits 8 .. 27 of the word are diagnostics of a non-converged solve (informational; OR-ed like the rest, so exact
-// for the usual single offender): bits 8-11 the kernel variant (1 LDS-resident, 2 / 3 odd-even with a double / single
-// mailbox, 4 two matrices per workgroup, 5 block ordering), bits 12-27 the matrix index (saturating at 65535).
+// for the usual single offender): bits 8-11 the kernel variant (2 / 3 odd-even with a double / single mailbox, 6 quad-block,
+// 7 hex-block; 1, 4, 5 belonged to retired kernels), bits 12-27 the matrix index (saturating at 65535).
 __device__ __forceinline__ void report_status(int32_t* status, bool converged, const float* s_sig, int n, int tid,
                                               int nthreads, int kind, int mat) {
   if (!status) return;
@@ -45,147 +41,8 @@ __device__ __forceinline__ void report_status(int32_t* status, bool converged, c
   if (st) atomicOr(status, st);
 }
 
-template <int MAXCH>
-__global__ __launch_bounds__(1024) void jacobi_kernel(
-    float* __restrict__ wg, int m, int n, int ld, int norm_rows, float tol,
-    int max_sweeps, int sort, float* __restrict__ sigma, int32_t* __restrict__ sweeps_out,
-    const int32_t* __restrict__ active, int active_rows, int32_t* __restrict__ status) {
-  extern __shared__ __align__(16) float lds[];
-  float* W = lds;
-  const int tid = threadIdx.x;
-  const int nthreads = blockDim.x;
-  const size_t mat = (size_t)n * ld;
-  float* s_sig = W + mat;                                  // [n]
-  int* s_rank = reinterpret_cast<int*>(s_sig + 256);       // [n]
-  int* s_flag = s_rank + 256;                              // [2]
-  float* src = wg + (size_t)blockIdx.x * mat;
-
-  for (size_t i = tid; i < mat / 4; i += nthreads)
-    reinterpret_cast<float4*>(W)[i] = reinterpret_cast<const float4*>(src)[i];
-  if (tid < 2) s_flag[tid] = 0;
-  __syncthreads();
-
-  // rows m..ld-1 are zero padding (kept zero by any rotation): never loaded / rotated / stored
-  // `active` (optional, per matrix): only the leading n_act columns (and, with active_rows, rows)
-  // are non-zero -- the rank-masked principal-angle blocks.  The tournament then runs over n_act
-  // columns only; the remaining (zero) columns and rows are left untouched.
-  int n_act = n;
-  if (active) { n_act = active[blockIdx.x]; n_act = n_act < 2 ? 2 : (n_act > n ? n : n_act); }
-  int mrows = (m + 3) & ~3;
-  if (active && active_rows) { const int ma = (n_act + 3) & ~3; mrows = ma < mrows ? ma : mrows; }
-  const int n_even = n_act + (n_act & 1);
-  const int R = n_even - 1;
-  const int npairs = n_even >> 1;
-  const int g = tid >> 3, sub = tid & 7;
-  const bool has_pair = g < npairs;
-  int used_sweeps = 0;
-  bool converged = false;
-
-  for (int sweep = 0; sweep < max_sweeps; ++sweep) {
-    bool rotated = false;
-    for (int t = 0; t < R; ++t) {
-      int p, q;
-      if (g == 0) { p = R; q = t; }
-      else { p = t + g; if (p >= R) p -= R; q = t - g; if (q < 0) q += R; }
-      if (has_pair && p < n_act && q < n_act) {
-        float* cp = W + (size_t)p * ld + sub * 4;
-        float* cq = W + (size_t)q * ld + sub * 4;
-        float4 a[MAXCH], b[MAXCH];
-        float alpha = 0.f, beta = 0.f, gamma = 0.f;
-#pragma unroll
-        for (int ch = 0; ch < MAXCH; ++ch) {
-          if (sub * 4 + 32 * ch < mrows) {
-            a[ch] = *reinterpret_cast<const float4*>(cp + 32 * ch);
-            b[ch] = *reinterpret_cast<const float4*>(cq + 32 * ch);
-            alpha = fmaf(a[ch].x, a[ch].x, fmaf(a[ch].y, a[ch].y, fmaf(a[ch].z, a[ch].z, fmaf(a[ch].w, a[ch].w, alpha))));
-            beta = fmaf(b[ch].x, b[ch].x, fmaf(b[ch].y, b[ch].y, fmaf(b[ch].z, b[ch].z, fmaf(b[ch].w, b[ch].w, beta))));
-            gamma = fmaf(a[ch].x, b[ch].x, fmaf(a[ch].y, b[ch].y, fmaf(a[ch].z, b[ch].z, fmaf(a[ch].w, b[ch].w, gamma))));
-          }
-        }
-        alpha = group8_sum(alpha);
-        beta = group8_sum(beta);
-        gamma = group8_sum(gamma);
-        // |gamma| > tol sqrt(alpha beta), without the sqrt
-        // (the cosine is scaled UP by 1 / tol before squaring: tol^2 alpha beta underflows for graded factors -- a
-        // column of norm 1e-17 against one of norm 1 -- and the test then degenerates to gamma^2 > 0)
-        const float gsc = gamma * (1.0f / tol);
-        if (gsc * gsc > fmaxf(alpha * beta, BASD_JACOBI_TINY)) {
-          rotated = true;
-          // The rotation ANGLE may be approximate (hardware rcp / sqrt, 1 ulp): any t gives an exact
-          // plane rotation as long as (c, s) are consistent.  Only c = (1 + t^2)^(-1/2) is refined
-          // (one Newton step on v_rsq_f32) so that c^2 + s^2 = 1 to rounding.  This removes four
-          // IEEE divide / sqrt expansions from the per-step dependent chain.
-          const float zeta = (beta - alpha) * __builtin_amdgcn_rcpf(2.f * gamma);
-          const float tt = copysignf(1.f, zeta) * __builtin_amdgcn_rcpf(fabsf(zeta) + __builtin_amdgcn_sqrtf(fmaf(zeta, zeta, 1.f)));
-          const float w1 = fmaf(tt, tt, 1.f);
-          float c = __builtin_amdgcn_rsqf(w1);
-          c = c * fmaf(-0.5f * w1, c * c, 1.5f);
-          const float s = c * tt;
-          // Rutishauser form x' = x - s (y + tau x), y' = y + s (x - tau y), tau = s / (1 + c):
-          // c = 1 - s*tau is never rounded to 1, so small-angle rotations (t^2 < eps) do not
-          // inflate the column norms (a plain c*x - s*y update biased sigma by +2e-5 at n = 192)
-          const float tau = s * __builtin_amdgcn_rcpf(1.0f + c);
-#pragma unroll
-          for (int ch = 0; ch < MAXCH; ++ch) {
-            if (sub * 4 + 32 * ch < mrows) {
-              float4 na, nb;
-              na.x = fmaf(-s, fmaf(tau, a[ch].x, b[ch].x), a[ch].x); nb.x = fmaf(s, fmaf(-tau, b[ch].x, a[ch].x), b[ch].x);
-              na.y = fmaf(-s, fmaf(tau, a[ch].y, b[ch].y), a[ch].y); nb.y = fmaf(s, fmaf(-tau, b[ch].y, a[ch].y), b[ch].y);
-              na.z = fmaf(-s, fmaf(tau, a[ch].z, b[ch].z), a[ch].z); nb.z = fmaf(s, fmaf(-tau, b[ch].z, a[ch].z), b[ch].z);
-              na.w = fmaf(-s, fmaf(tau, a[ch].w, b[ch].w), a[ch].w); nb.w = fmaf(s, fmaf(-tau, b[ch].w, a[ch].w), b[ch].w);
-              *reinterpret_cast<float4*>(cp + 32 * ch) = na;
-              *reinterpret_cast<float4*>(cq + 32 * ch) = nb;
-            }
-          }
-        }
-      }
-      __syncthreads();
-    }
-    used_sweeps = sweep + 1;
-    if (rotated) s_flag[sweep & 1] = 1;
-    __syncthreads();
-    const int any = s_flag[sweep & 1];
-    if (tid == 0) s_flag[(sweep + 1) & 1] = 0;
-    __syncthreads();
-    if (!any) { converged = true; break; }
-  }
-
-  // column norms over the first norm_rows rows (one 8-lane group per column, strided)
-  for (int c = g; c < n; c += (nthreads >> 3)) {
-    const float* col = W + (size_t)c * ld;
-    float acc = 0.f;
-    for (int r = sub; r < norm_rows; r += 8) acc = fmaf(col[r], col[r], acc);
-    acc = group8_sum(acc);
-    if (sub == 0) s_sig[c] = sqrtf(acc);
-  }
-  __syncthreads();
-  if (tid < n) {
-    int rank = tid;
-    if (sort) {
-      const float mine = s_sig[tid];
-      rank = 0;
-      for (int c = 0; c < n; ++c) {
-        const float o = s_sig[c];
-        rank += (o > mine) || (o == mine && c < tid);
-      }
-    }
-    s_rank[tid] = rank;
-    sigma[(size_t)blockIdx.x * n + rank] = s_sig[tid];
-  }
-  __syncthreads();
-  // write back (permuted) columns
-  for (size_t i = tid; i < mat / 4; i += nthreads) {
-    const int c = (int)((i * 4) / ld);
-    const int r = (int)((i * 4) - (size_t)c * ld);
-    const int dst = s_rank[c];
-    *reinterpret_cast<float4*>(src + (size_t)dst * ld + r) = reinterpret_cast<const float4*>(W)[i];
-  }
-  if (sweeps_out && tid == 0) sweeps_out[blockIdx.x] = converged ? used_sweeps : -used_sweeps;
-  report_status(status, converged, s_sig, n, tid, nthreads, 1, blockIdx.x);
-}
-
 // ---------------------------------------------------------------------------------------------
-// Register-resident variant (the default when it fits): odd-even transposition ordering.
+// Odd-even transposition ordering of single columns.
 // The n columns form a line; steps alternate between pairing positions (2k, 2k+1) and
 // (2k+1, 2k+2), every rotation is followed by a (logical) swap, and n consecutive steps visit
 // every column pair exactly once.  An 8-lane slot keeps its two columns X, Y in VGPRs for the
@@ -193,10 +50,9 @@ __global__ __launch_bounds__(1024) void jacobi_kernel(
 // neighbour through an LDS mailbox (even->odd: Y goes to slot k-1, odd->even: X goes to slot k+1).
 //
 // The kernel is bound by the per-step dependent chain (LDS hand-over -> dot -> 8-lane reduction
-// -> rotation parameters -> update -> hand-over), not by bandwidth, so NMAT = 2 lets every
-// workgroup carry two INDEPENDENT matrices through the same steps: their instruction streams
-// interleave in each wave (ILP) and they share the barriers.  NMAT = 1 double-buffers the mailbox
-// (one barrier per step); NMAT = 2 uses one mailbox per matrix and two barriers per step.
+// -> rotation parameters -> update -> hand-over), not by bandwidth.  NMAT matrices share a workgroup and its
+// barriers; every instantiation has NMAT = 1 since the two-matrix form was retired (the quad-block kernel took its
+// shapes).  The parameter and its loops stay: without them the compiler schedules all six instantiations differently.
 typedef float v4f __attribute__((ext_vector_type(4)));
 // Quadratic-convergence stop: a sweep in which every rotation was SMALL -- |cos| of the pair below QUAD and
 // rotation tangent below QUAD_TAN -- is the last one: small-angle rotations at small cosines disturb the other
@@ -235,6 +91,8 @@ __device__ __forceinline__ void rotate_in_place(v4f& xa, v4f& ya, float tau, flo
 // NBUF = 2 double-buffers the mailbox (one barrier per step); NBUF = 1 halves its LDS footprint for a second
 // barrier per step: what lets columns of up to 384 rows (MAXCH = 12: the block pairs of the D_s = 384 eigensolver,
 // 96 slots x 1.5 KiB = 147 KiB) stay register-resident.
+// LDS behind the mailbox: s_sig [260], s_rank [260], s_id and s_nrm [2][2][132] each, s_flag [8]
+constexpr size_t JACOBI_OE_SCRATCH = (260 + 260 + 2 * 2 * 132 * 2 + 8) * 4;
 template <int MAXCH, int NMAT, int NBUF>
 __global__ __launch_bounds__((NMAT == 2 || MAXCH > 7) ? 768 : 1024)
 __attribute__((amdgpu_waves_per_eu((NMAT == 2 || MAXCH > 7) ? 3 : 4, (NMAT == 2 || MAXCH > 7) ? 3 : 4))) void jacobi_oe_kernel(
@@ -510,277 +368,15 @@ __attribute__((amdgpu_waves_per_eu((NMAT == 2 || MAXCH > 7) ? 3 : 4, (NMAT == 2 
 }
 
 // ---------------------------------------------------------------------------------------------
-// Block ordering (default for large batches): the hand-over chain (write -> wait -> barrier ->
-// read -> wait -> barrier, walked in lockstep by every wave) is two thirds of a step of the kernel
-// above and does not depend on the bytes moved (ablations).  Here a slot owns
-// two BLOCKS of two columns, P = (c0, c1) and Q = (c2, c3); the blocks travel along the odd-even
-// transposition line exactly like the single columns above, but every meeting of two blocks performs
-// all four cross rotations -- (c0,c2),(c1,c3) then (c0,c3),(c1,c2), two independent rotations at a
-// time -- before ONE hand-over of a whole block: four rotations per hand-over instead of one.  The
-// pair inside a block is rotated once per sweep.  One matrix per 8 * S-thread workgroup (S = slots =
-// a quarter of the columns: 384 threads at n = 192, 96 column VGPRs), single mailbox (74 KB): two
-// independent workgroups per CU, so one's hand-over overlaps the other's rotations.
-template <int MAXCH>
-__global__ __launch_bounds__(MAXCH > 6 ? 448 : 384) __attribute__((amdgpu_waves_per_eu(MAXCH > 6 ? 2 : 3, MAXCH > 6 ? 2 : 3))) void jacobi_blk_kernel(
-    float* __restrict__ wg, int batch, int m, int n, int ld, int norm_rows, float tol, int max_sweeps, int sort,
-    float* __restrict__ sigma, int32_t* __restrict__ sweeps_out, int32_t* __restrict__ status,
-    const int32_t* __restrict__ skip) {
-  extern __shared__ __align__(16) float lds[];
-  if (skip != nullptr && skip[blockIdx.x] < 0) {   // masked problem (active_rows == 2): nothing is read or written
-    if (sweeps_out && threadIdx.x == 0) sweeps_out[blockIdx.x] = 0;
-    return;
-  }
-  constexpr int LDC = 32 * MAXCH;                  // one column in the mailbox
-  constexpr int LDB = 2 * LDC;                     // one block
-  const int tid = threadIdx.x;
-  const int k = tid >> 3, sub = tid & 7, roff = sub * 4;
-  const int nb = (n + 1) >> 1;                     // blocks that hold real columns
-  const int nbe = nb + (nb & 1);                   // line length in blocks (a zero phantom block pads odd nb)
-  const int S = nbe >> 1;                          // slots
-  float* mbox = lds;                               // [S + 1][LDB]
-  float* s_sig = mbox + (size_t)(S + 1) * LDB;     // [4 S]
-  int* s_rank = reinterpret_cast<int*>(s_sig + 264);      // [4 S]
-  int* s_id = s_rank + 264;                        // [S][2] column ids travelling with the mailbox
-  float* s_nrm = reinterpret_cast<float*>(s_id + 264);    // [S][2] squared norms travelling along
-  int* s_flag = reinterpret_cast<int*>(s_nrm + 264);      // [2] any rotation, [2] any LARGE rotation
-
-  const int mat = blockIdx.x;
-  float* src = wg + (size_t)mat * n * ld;
-  const int mr = (m + 3) & ~3;
-  const bool live = k < S;
-  v4f C[4][MAXCH];
-  int id[4];
-  float nr[4];                                     // squared column norms (rotation identities inside a sweep)
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    id[c] = 4 * k + c;
-#pragma unroll
-    for (int ch = 0; ch < MAXCH; ++ch) {
-      const int r = roff + 32 * ch;
-      C[c][ch] = (live && id[c] < n && r < mr) ? *reinterpret_cast<const v4f*>(src + (size_t)id[c] * ld + r)
-                                               : (v4f){0.f, 0.f, 0.f, 0.f};
-    }
-  }
-  if (tid < 8) s_flag[tid] = 0;                    // [4 + parity]: largest squared column norm of the sweep
-  __syncthreads();
-
-  const float inv_tol = 1.0f / tol;
-  bool rotated = false, bigrot = false;
-  // one plane rotation of the column pair (A, B); the caller issues two independent ones back to back
-  auto rot1 = [&](v4f (&A)[MAXCH], v4f (&B)[MAXCH], float& na, float& nb_, bool ok) {
-    float ga = 0.f, gb = 0.f;
-#pragma unroll
-    for (int ch = 0; ch < MAXCH; ++ch) {
-      const v4f x = A[ch], y = B[ch];
-      ga = fmaf(x.x, y.x, fmaf(x.y, y.y, ga));
-      gb = fmaf(x.z, y.z, fmaf(x.w, y.w, gb));
-    }
-    const float g = group8_sum(ga + gb);
-    const float al = na, be = nb_;
-    // |g| > tol sqrt(al be) as (g / tol)^2 > al be (see jacobi_oe_kernel); a product below TINY (under-scaled input:
-    // both columns below 1e-19) is compared against TINY instead -- a coarser threshold there, never "any g != 0"
-    const float gsc = g * inv_tol;
-    if (ok && gsc * gsc > fmaxf(al * be, BASD_JACOBI_TINY)) {
-      rotated = true;
-      const float gq = g * (1.0f / BASD_JACOBI_QUAD);
-      const bool big_cos = gq * gq > al * be;
-      const float z = (be - al) * __builtin_amdgcn_rcpf(2.f * g);
-      const float t = copysignf(1.f, z) * __builtin_amdgcn_rcpf(fabsf(z) + __builtin_amdgcn_sqrtf(fmaf(z, z, 1.f)));
-      bigrot = bigrot || big_cos || fabsf(t) > BASD_JACOBI_QUAD_TAN;
-      const float w = fmaf(t, t, 1.f);
-      float c = __builtin_amdgcn_rsqf(w);
-      c = c * fmaf(-0.5f * w, c * c, 1.5f);
-      const float sn = c * t;
-      const float u = sn * __builtin_amdgcn_rcpf(1.0f + c);
-      na = fmaf(-t, g, al);
-      nb_ = fmaf(t, g, be);
-#pragma unroll
-      for (int ch = 0; ch < MAXCH; ++ch) rotate_in_place(A[ch], B[ch], u, sn);
-    }
-  };
-  auto rot2 = [&](v4f (&A0)[MAXCH], v4f (&B0)[MAXCH], float& na0, float& nb0, v4f (&A1)[MAXCH], v4f (&B1)[MAXCH],
-                  float& na1, float& nb1, bool ok) {
-    rot1(A0, B0, na0, nb0, ok);
-    __builtin_amdgcn_sched_barrier(0);             // keep the register live ranges of the inlined copies apart
-    rot1(A1, B1, na1, nb1, ok);
-    __builtin_amdgcn_sched_barrier(0);
-  };
-
-  int used_sweeps = 0;
-  bool converged = false;
-  int step = 0;                                    // even = blocks (2k, 2k+1); nbe is even, sweeps start and end there
-#pragma unroll 1
-  for (int sweep = 0; sweep < max_sweeps; ++sweep) {
-    rotated = false;
-    bigrot = false;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {                  // exact squared norms once per sweep
-      float a = 0.f;
-#pragma unroll
-      for (int ch = 0; ch < MAXCH; ++ch) {
-        const v4f x = C[c][ch];
-        a = fmaf(x.x, x.x, fmaf(x.y, x.y, fmaf(x.z, x.z, fmaf(x.w, x.w, a))));
-      }
-      nr[c] = group8_sum(a);
-    }
-    if (live && sub == 0)
-      atomicMax(&s_flag[4 + (sweep & 1)], __float_as_int(fmaxf(fmaxf(nr[0], nr[1]), fmaxf(nr[2], nr[3]))));
-    __syncthreads();
-    {
-      const float debris = __int_as_float(s_flag[4 + (sweep & 1)]) * BASD_JACOBI_DEBRIS;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {                // debris columns become exact zero columns (never rotated again)
-        const bool z = nr[c] < debris;
-#pragma unroll
-        for (int ch = 0; ch < MAXCH; ++ch)
-          if (z) C[c][ch] = (v4f){0.f, 0.f, 0.f, 0.f};
-        if (z) nr[c] = 0.f;
-      }
-    }
-    rot2(C[0], C[1], nr[0], nr[1], C[2], C[3], nr[2], nr[3], live);       // the pair inside each block
-#pragma unroll 1
-    for (int t = 0; t < nbe; ++t, ++step) {
-      const bool even_view = (step & 1) == 0;
-      const bool pair_ok = live && (even_view || k < S - 1);
-      rot2(C[0], C[2], nr[0], nr[2], C[1], C[3], nr[1], nr[3], pair_ok);
-      rot2(C[0], C[3], nr[0], nr[3], C[1], C[2], nr[1], nr[2], pair_ok);
-      // ---- hand one block over (after the logical swap the pair is stored as (lo = Q, hi = P)):
-      // even -> odd view: Q (block position 2k) goes to slot k-1, slot 0's copy stays parked in box 0;
-      // odd -> even view: P (position 2k+2; the lone last slot did not swap) goes to slot k+1.
-      // Register loads are the same for every live slot (a block copied or loaded under a per-slot condition
-      // makes the register allocator spill hundreds of VGPRs); only the LDS writes are conditional.
-      if (even_view) {
-        // Q (block position 2k after the swap) goes to slot k-1 through box k (slot 0's stays parked there);
-        // the last slot has no right neighbour: it parks its P in box S and takes it back as Q, which is
-        // where its lone block of the odd view has to sit for the next even view
-        if (live) {
-          float* box = mbox + (size_t)k * LDB + roff;
-#pragma unroll
-          for (int ch = 0; ch < MAXCH; ++ch) {
-            *reinterpret_cast<v4f*>(box + 32 * ch) = C[2][ch];
-            *reinterpret_cast<v4f*>(box + LDC + 32 * ch) = C[3][ch];
-          }
-          if (sub == 0) { s_id[2 * k] = id[2]; s_id[2 * k + 1] = id[3]; s_nrm[2 * k] = nr[2]; s_nrm[2 * k + 1] = nr[3]; }
-          if (k == S - 1) {
-#pragma unroll
-            for (int ch = 0; ch < MAXCH; ++ch) {
-              *reinterpret_cast<v4f*>(box + LDB + 32 * ch) = C[0][ch];
-              *reinterpret_cast<v4f*>(box + LDB + LDC + 32 * ch) = C[1][ch];
-            }
-            if (sub == 0) { s_id[2 * k + 2] = id[0]; s_id[2 * k + 3] = id[1]; s_nrm[2 * k + 2] = nr[0]; s_nrm[2 * k + 3] = nr[1]; }
-          }
-        }
-        __syncthreads();
-        if (live) {
-          const float* box = mbox + (size_t)(k + 1) * LDB + roff;
-#pragma unroll
-          for (int ch = 0; ch < MAXCH; ++ch) {
-            C[2][ch] = *reinterpret_cast<const v4f*>(box + 32 * ch);
-            C[3][ch] = *reinterpret_cast<const v4f*>(box + LDC + 32 * ch);
-          }
-          id[2] = s_id[2 * k + 2]; id[3] = s_id[2 * k + 3];
-          nr[2] = s_nrm[2 * k + 2]; nr[3] = s_nrm[2 * k + 3];
-        }
-      } else {
-        // P (position 2k+2 after the swap) goes to slot k+1 through box k+1; slot 0 takes the parked block back
-        if (live && k < S - 1) {
-          float* box = mbox + (size_t)(k + 1) * LDB + roff;
-#pragma unroll
-          for (int ch = 0; ch < MAXCH; ++ch) {
-            *reinterpret_cast<v4f*>(box + 32 * ch) = C[0][ch];
-            *reinterpret_cast<v4f*>(box + LDC + 32 * ch) = C[1][ch];
-          }
-          if (sub == 0) { s_id[2 * k + 2] = id[0]; s_id[2 * k + 3] = id[1]; s_nrm[2 * k + 2] = nr[0]; s_nrm[2 * k + 3] = nr[1]; }
-        }
-        __syncthreads();
-        if (live) {
-          const float* box = mbox + (size_t)k * LDB + roff;
-#pragma unroll
-          for (int ch = 0; ch < MAXCH; ++ch) {
-            C[0][ch] = *reinterpret_cast<const v4f*>(box + 32 * ch);
-            C[1][ch] = *reinterpret_cast<const v4f*>(box + LDC + 32 * ch);
-          }
-          id[0] = s_id[2 * k]; id[1] = s_id[2 * k + 1];
-          nr[0] = s_nrm[2 * k]; nr[1] = s_nrm[2 * k + 1];
-        }
-      }
-      __syncthreads();                             // single mailbox: reads done before the next writes
-    }
-    used_sweeps = sweep + 1;
-    if (rotated) s_flag[sweep & 1] = 1;
-    if (bigrot) s_flag[2 + (sweep & 1)] = 1;
-    __syncthreads();
-    const int any = s_flag[sweep & 1], anybig = s_flag[2 + (sweep & 1)];
-    if (tid == 0) { s_flag[(sweep + 1) & 1] = 0; s_flag[2 + ((sweep + 1) & 1)] = 0; s_flag[4 + ((sweep + 1) & 1)] = 0; }
-    __syncthreads();
-    if (!any || !anybig) { converged = true; break; }
-  }
-
-  // ---- singular values = column norms over the first norm_rows rows; phantom columns (id >= n) rank last
-  {
-    float a[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      float acc = 0.f;
-#pragma unroll
-      for (int ch = 0; ch < MAXCH; ++ch) {
-        const int r = roff + 32 * ch;
-        const float mx = (r + 0 < norm_rows) ? 1.f : 0.f, my = (r + 1 < norm_rows) ? 1.f : 0.f;
-        const float mz = (r + 2 < norm_rows) ? 1.f : 0.f, mw = (r + 3 < norm_rows) ? 1.f : 0.f;
-        const v4f x = C[c][ch];
-        acc = fmaf(mx * x.x, x.x, fmaf(my * x.y, x.y, fmaf(mz * x.z, x.z, fmaf(mw * x.w, x.w, acc))));
-      }
-      a[c] = group8_sum(acc);
-    }
-    if (live && sub == 0) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) s_sig[4 * k + c] = (id[c] >= n) ? -1.f : sqrtf(a[c]);
-    }
-  }
-  __syncthreads();
-  const int n_tot = 4 * S;                         // >= n; positions beyond the real columns hold -1
-  for (int p = tid; p < n_tot; p += blockDim.x) {
-    int rank = p;
-    if (sort) {
-      const float mine = s_sig[p];
-      rank = 0;
-      for (int c = 0; c < n_tot; ++c) {
-        const float o = s_sig[c];
-        rank += (o > mine) || (o == mine && c < p);
-      }
-    }
-    s_rank[p] = rank;
-  }
-  __syncthreads();
-  if (live) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int d = sort ? s_rank[4 * k + c] : id[c];
-      const float sg = s_sig[4 * k + c];
-      if (id[c] < n && d < n) {
-#pragma unroll
-        for (int ch = 0; ch < MAXCH; ++ch) {
-          const int r = roff + 32 * ch;
-          if (r < ld) *reinterpret_cast<v4f*>(src + (size_t)d * ld + r) = (r < mr) ? C[c][ch] : (v4f){0.f, 0.f, 0.f, 0.f};
-        }
-        if (sub == 0) sigma[(size_t)mat * n + d] = sg < 0.f ? 0.f : sg;
-      }
-    }
-  }
-  if (sweeps_out && tid == 0) sweeps_out[mat] = converged ? used_sweeps : -used_sweeps;
-  report_status(status, converged, s_sig, n_tot, tid, blockDim.x, 5, mat);
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// Quad-block ordering with scaled rotations (round 4; the default for batches of up to 192 x 192).
-// What the block kernel above still pays per rotation and wave: the rotation parameters (five
+// Quad-block ordering with scaled rotations (the default for 8 .. 196 columns where the hex-block kernel below does
+// not apply).  What its retired predecessor (block odd-even: 8-lane slots owning two blocks of TWO columns, DESIGN.md
+// section 5) still paid per rotation and wave: the rotation parameters (five
 // transcendentals, ~25 VALU instructions) are computed by all 8 lanes of a slot, i.e. 8 distinct
 // parameter sets per wave instruction stream; the plane rotation is four FMAs per row pair; and the
 // mailbox costs two barriers per hand-over.  Here
 //   * a slot is 16 lanes (12 rows per lane at 192 rows) and owns two blocks of FOUR columns (the same 96
 //     column VGPRs); a meeting of two blocks is 16 cross rotations in four rounds of four INDEPENDENT
-//     rotations, one hand-over per 16 rotations (block kernel: per 4);
+//     rotations, one hand-over per 16 rotations (two-column blocks: per 4);
 //   * the four dot products of a round are reduced with a reduce-scatter (11 DPP / select instructions for
 //     all four), after which lane q of every quad holds rotation q's sum and computes rotation q's
 //     parameters: ONE parameter instruction stream serves four rotations per slot, 16 per wave;
@@ -1225,7 +821,7 @@ __attribute__((amdgpu_waves_per_eu((LANES == 16 && MAXCH > 3) ? 2 : 3, (LANES ==
 }
 
 // ---------------------------------------------------------------------------------------------
-// Hex-block ordering (round 4, second step): blocks of SIX columns, 16 slots of 16 lanes for 192 columns -- FOUR
+// Hex-block ordering: blocks of SIX columns, 16 slots of 16 lanes for 192 columns -- FOUR
 // waves, one per SIMD.  What the quad-block kernel leaves on the table: its 24 slots are six waves on four SIMDs
 // (two SIMDs carry two waves, two carry one: the workgroup runs at the pace of the loaded pair), and one
 // parameter stream serves four rotations.  Here a meeting of two blocks is 36 cross rotations in six rounds of SIX
@@ -1648,6 +1244,13 @@ __global__ __launch_bounds__(16 * LANES) __attribute__((amdgpu_waves_per_eu(OCC,
 
 }  // namespace basd
 
+// Shape classes in priority order; each is tested on (rows4, n_cols) alone, so batch size and `active` never change
+// the class (only the hex-block kernel's occupancy variant looks at the batch size).  Anything outside them is
+// BASD_ERR_SHAPE (DESIGN.md section 5 has the table).
+//   hex-block   129 .. 192 columns, rows4 <= 192 (16-lane slots) or 257 .. 384 (32-lane slots)
+//   quad-block  8 .. 192 columns up to 384 rows (32-lane slots above 256), 8 .. 196 columns at 193 .. 256 rows
+//   odd-even    rows4 <= 224: what is left, i.e. fewer than 8 or more than 192 (196) columns
+//   tall        fewer than 8 columns, 225 .. 384 rows
 extern "C" int basd_jacobi_svd(float* w, int batch, int m_rows, int n_cols, int ld, int norm_rows,
                                float tol, int max_sweeps, int sort, float* sigma,
                                int32_t* sweeps, const int32_t* active, int active_rows, int32_t* status,
@@ -1657,165 +1260,74 @@ extern "C" int basd_jacobi_svd(float* w, int batch, int m_rows, int n_cols, int 
   if (n_cols < 1 || n_cols > BASD_JACOBI_MAX_COLS || ld % 4 != 0 || m_rows > ld || m_rows < 1 ||
       norm_rows < 1 || norm_rows > m_rows)
     return fail(BASD_ERR_SHAPE, "jacobi_svd: bad shape m=%d n=%d ld=%d norm_rows=%d", m_rows, n_cols, ld, norm_rows);
-  const int npairs = (n_cols + 1) / 2;
-  int threads = ((npairs * 8 + 63) / 64) * 64;
-  if (threads < 64) threads = 64;
-  const int chunks = (((m_rows + 3) & ~3) + 31) / 32;
   hipStream_t st = (hipStream_t)stream;
-  // register-resident odd-even kernel: LDS only holds the double-buffered mailbox
-  const int oe_ch = chunks <= 2 ? 2 : (chunks <= 4 ? 4 : (chunks <= 6 ? 6 : 7));
-  const size_t oe_scratch = (260 + 260 + 2 * 2 * 132 * 2 + 8) * 4;
-  // two matrices per workgroup (shared steps, ILP) once every CU would get at least two anyway
-  const size_t lds_oe2 = (size_t)2 * npairs * 32 * oe_ch * 4 + oe_scratch;       // NMAT 2, single mailbox each
-  const size_t lds_oe1 = lds_oe2;                                                // NMAT 1, double buffered
-  const bool fits = lds_oe1 <= BASD_JACOBI_LDS_BYTES && chunks <= 7 && npairs <= 128;
-#define BASD_LAUNCH_OE(MC, NM, GRID, LDSB)                                                            \
-  do {                                                                                               \
-    allow_full_lds((const void*)jacobi_oe_kernel<MC, NM, (NM == 1 ? 2 : 1)>);                         \
-    hipLaunchKernelGGL((jacobi_oe_kernel<MC, NM, (NM == 1 ? 2 : 1)>), dim3(GRID), dim3(threads), (LDSB), st, w, batch, m_rows, \
-                       n_cols, ld, norm_rows, tol, max_sweeps, sort, sigma, sweeps, active, active_rows, status); \
-  } while (0)
+  const int rows4 = (m_rows + 3) & ~3;
   // active_rows == 2: `active` is a MASK -- entries are either < 0 (skip the matrix) or n_cols (solve it completely)
   const bool mask_only = active != nullptr && active_rows == 2;
   if (mask_only) active_rows = 0;
-  {
-    // quad-block ordering with scaled rotations: every launch of up to 192 x 192 (BASD_JACOBI_B4=0 falls back to the
-    // kernels below: A/B timing).  BASD_JACOBI_B4_MIN sets the smallest batch it takes (default 1).
-    const char* b4env = getenv("BASD_JACOBI_B4");
-    const bool b4 = !(b4env && b4env[0] == '0');
-    const char* b4min = getenv("BASD_JACOBI_B4_MIN");
-    const int min_batch = b4min ? atoi(b4min) : 1;
-    const int rows4 = (m_rows + 3) & ~3;
-    const bool b4_16 = n_cols <= 196 && rows4 <= 256 && (rows4 <= 192 ? n_cols <= 192 : true);
-    const bool b4_32 = n_cols <= 192 && rows4 > 256 && rows4 <= 384;
-    const char* b6env = getenv("BASD_JACOBI_B6");
-    // (from 129 columns: below that the quad-block kernel is four waves or fewer itself and its shorter rounds win --
-    // 48 x 64^2: 0.136 vs 0.210 ms)
-    const bool b6_on = !(b6env && b6env[0] == '0') && n_cols > 128 && n_cols <= 192;
-    const bool b6_16 = b6_on && rows4 <= 192, b6_32 = b6_on && rows4 > 256 && rows4 <= 384;
-    if (b4 && (b6_16 || b6_32) && batch >= min_batch) {
-      // hex-block ordering: four waves for 192 columns (BASD_JACOBI_B6=0: the quad-block kernel, A/B timing)
-      const int mode = active == nullptr ? 0 : (mask_only ? 3 : (active_rows ? 2 : 1));
-      const int lanes = b6_32 ? 32 : 16;
-      const int nb6 = (n_cols + 5) / 6, slots6 = (nb6 + 1) / 2;
-      const int threads6 = ((slots6 * lanes + 63) / 64) * 64;
-      const int chn = (rows4 + 4 * lanes - 1) / (4 * lanes);
-      const size_t lds6 = ((size_t)(slots6 + 1) * 6 * 4 * lanes * chn + 200 * 2 + 104 * 2 + 8) * 4;
-      if (lds6 > BASD_JACOBI_LDS_BYTES)
-        return fail(BASD_ERR_SHAPE, "jacobi_svd: %d x %d needs %zu B of LDS", m_rows, n_cols, lds6);
-#define BASD_LAUNCH_B6(MC, OC, LN)                                                                   \
-  do {                                                                                               \
-    allow_full_lds((const void*)jacobi_b6_kernel<MC, OC, LN>);                                       \
-    hipLaunchKernelGGL((jacobi_b6_kernel<MC, OC, LN>), dim3(batch), dim3(threads6), lds6, st, w, batch, m_rows, n_cols, \
-                       ld, norm_rows, tol, max_sweeps, sort, sigma, sweeps, status, active, mode);   \
-  } while (0)
-      const char* occenv = getenv("BASD_JACOBI_B6_OCC");
-      const bool two = occenv ? occenv[0] == '2' : batch > 256;
-      if (lanes == 32) BASD_LAUNCH_B6(3, 2, 32);
-      else if (chn == 1) BASD_LAUNCH_B6(1, 2, 16);
-      else if (chn == 2) BASD_LAUNCH_B6(2, 2, 16);
-      else if (two) BASD_LAUNCH_B6(3, 2, 16);
-      else BASD_LAUNCH_B6(3, 1, 16);
-#undef BASD_LAUNCH_B6
-      return check_launch("jacobi_svd (hex-block, scaled rotations)");
-    }
-    if (b4 && batch >= min_batch && n_cols >= 8 && (b4_16 || b4_32)) {
-      const int mode = active == nullptr ? 0 : (mask_only ? 3 : (active_rows ? 2 : 1));
-      const int lanes = b4_32 ? 32 : 16;
-      const int nb4 = (n_cols + 3) / 4, slots4 = (nb4 + 1) / 2;
-      const int threads4 = ((slots4 * lanes + 63) / 64) * 64;
-      const int chn = (rows4 + 4 * lanes - 1) / (4 * lanes);
-      const size_t lds4 = ((size_t)(slots4 + 1) * 4 * 4 * lanes * chn + 200 * 2 + 104 * 2 + 8) * 4;
-      if (lds4 > BASD_JACOBI_LDS_BYTES)
-        return fail(BASD_ERR_SHAPE, "jacobi_svd: %d x %d needs %zu B of LDS", m_rows, n_cols, lds4);
-#define BASD_LAUNCH_B4(MC, LN)                                                                       \
-  do {                                                                                               \
-    allow_full_lds((const void*)jacobi_b4_kernel<MC, LN>);                                           \
-    hipLaunchKernelGGL((jacobi_b4_kernel<MC, LN>), dim3(batch), dim3(threads4), lds4, st, w, batch, m_rows, n_cols, \
-                       ld, norm_rows, tol, max_sweeps, sort, sigma, sweeps, status, active, mode);   \
-  } while (0)
-      if (lanes == 32) BASD_LAUNCH_B4(3, 32);
-      else if (chn == 1) BASD_LAUNCH_B4(1, 16);
-      else if (chn == 2) BASD_LAUNCH_B4(2, 16);
-      else if (chn == 3) BASD_LAUNCH_B4(3, 16);
-      else BASD_LAUNCH_B4(4, 16);
-#undef BASD_LAUNCH_B4
-      return check_launch("jacobi_svd (quad-block, scaled rotations)");
-    }
+  const int mode = active == nullptr ? 0 : (mask_only ? 3 : (active_rows ? 2 : 1));      // the block kernels' view of it
+
+  // block kernels: a slot of `lanes` lanes owns two blocks of BC columns, 4 * lanes rows per chunk; the mailbox holds
+  // one block per slot and one spare
+  const int lanes = rows4 > 256 ? 32 : 16;
+  const int chn = (rows4 + 4 * lanes - 1) / (4 * lanes);
+  auto launch_block = [&](auto kernel, int bc, const char* what) {
+    const int slots = ((n_cols + bc - 1) / bc + 1) / 2;
+    const int threads = ((slots * lanes + 63) / 64) * 64;
+    const size_t lds = ((size_t)(slots + 1) * bc * 4 * lanes * chn + 200 * 2 + 104 * 2 + 8) * 4;
+    if (lds > BASD_JACOBI_LDS_BYTES)
+      return fail(BASD_ERR_SHAPE, "jacobi_svd: %d x %d needs %zu B of LDS", m_rows, n_cols, lds);
+    allow_full_lds((const void*)kernel);
+    hipLaunchKernelGGL(kernel, dim3(batch), dim3(threads), lds, st, w, batch, m_rows, n_cols, ld, norm_rows, tol,
+                       max_sweeps, sort, sigma, sweeps, status, active, mode);
+    return check_launch(what);
+  };
+  // odd-even kernels: an 8-lane slot per column pair, NBUF mailboxes of one column (32 * MAXCH rows) per slot
+  auto launch_oe = [&](auto kernel, int maxch, int nbuf, const char* what) {
+    const int npairs = (n_cols + 1) / 2;
+    const int threads = ((npairs * 8 + 63) / 64) * 64;
+    const size_t lds = (size_t)nbuf * npairs * 32 * maxch * 4 + JACOBI_OE_SCRATCH;
+    allow_full_lds((const void*)kernel);
+    hipLaunchKernelGGL(kernel, dim3(batch), dim3(threads), lds, st, w, batch, m_rows, n_cols, ld, norm_rows, tol,
+                       max_sweeps, sort, sigma, sweeps, active, active_rows, status);
+    return check_launch(what);
+  };
+
+  // (hex-block from 129 columns: below that the quad-block kernel is four waves or fewer itself and its shorter rounds
+  // win -- 48 x 64^2: 0.136 vs 0.210 ms)
+  if (n_cols > 128 && n_cols <= 192 && (rows4 <= 192 || (rows4 > 256 && rows4 <= 384))) {
+    const char* what = "jacobi_svd (hex-block, scaled rotations)";
+    if (lanes == 32) return launch_block(jacobi_b6_kernel<3, 2, 32>, 6, what);
+    if (chn == 1) return launch_block(jacobi_b6_kernel<1, 2, 16>, 6, what);
+    if (chn == 2) return launch_block(jacobi_b6_kernel<2, 2, 16>, 6, what);
+    // 144 column VGPRs: a second workgroup per SIMD only pays once every CU has more than one matrix
+    if (batch > 256) return launch_block(jacobi_b6_kernel<3, 2, 16>, 6, what);
+    return launch_block(jacobi_b6_kernel<3, 1, 16>, 6, what);
   }
-  if (chunks > 7 && chunks <= 12 && npairs <= 96) {
-    // tall columns (up to 384 rows, at most 192 of them): single mailbox, 96 slots, 3 waves per SIMD
-    const size_t lds_tall = (size_t)npairs * 32 * 12 * 4 + oe_scratch;
-    allow_full_lds((const void*)jacobi_oe_kernel<12, 1, 1>);
-    hipLaunchKernelGGL((jacobi_oe_kernel<12, 1, 1>), dim3(batch), dim3(threads), lds_tall, st, w, batch, m_rows, n_cols, ld,
-                       norm_rows, tol, max_sweeps, sort, sigma, sweeps, active, active_rows, status);
-    return check_launch("jacobi_svd (odd-even, tall columns)");
+  if (n_cols >= 8 && rows4 <= 384 && n_cols <= ((rows4 > 192 && rows4 <= 256) ? 196 : 192)) {
+    const char* what = "jacobi_svd (quad-block, scaled rotations)";
+    if (lanes == 32) return launch_block(jacobi_b4_kernel<3, 32>, 4, what);
+    if (chn == 1) return launch_block(jacobi_b4_kernel<1, 16>, 4, what);
+    if (chn == 2) return launch_block(jacobi_b4_kernel<2, 16>, 4, what);
+    if (chn == 3) return launch_block(jacobi_b4_kernel<3, 16>, 4, what);
+    return launch_block(jacobi_b4_kernel<4, 16>, 4, what);
   }
-  // (the block ordering also wins on small batches: 1.06 vs 1.27 ms at 48 matrices of 192^2, 1.27 vs 1.39 at 256,
-  // equal at 4 - 24: measured in round 3; before, it was only taken from 512 matrices up)
-  // MAXCH = 7 (193 .. 224 rows, up to 196 columns: the 196-token Procrustes cores of the wide students): 112 column
-  // VGPRs (202 in all, no spills), seven waves, one workgroup per CU: 4.02 vs 5.00 ms per 512 matrices of 196 x 196
-  // with the single-mailbox odd-even kernel
-  const bool blk7 = oe_ch == 7 && n_cols <= 196;
-  if ((active == nullptr || mask_only) && batch >= 32 && ((n_cols <= 192 && oe_ch <= 6) || blk7) && n_cols >= 8) {
-    // block ordering: one matrix per workgroup, slots = ceil(ceil(n / 2) / 2)
-    const int nbk = (n_cols + 1) / 2, slots = (nbk + 1) / 2;
-    const int threads_b = ((slots * 8 + 63) / 64) * 64;
-    const size_t lds_b = ((size_t)(slots + 1) * 2 * 32 * oe_ch + 264 * 4 + 8) * 4;
-#define BASD_LAUNCH_BLK(MC)                                                                          \
-  do {                                                                                               \
-    allow_full_lds((const void*)jacobi_blk_kernel<MC>);                                              \
-    hipLaunchKernelGGL((jacobi_blk_kernel<MC>), dim3(batch), dim3(threads_b), lds_b, st, w, batch, m_rows, n_cols, \
-                       ld, norm_rows, tol, max_sweeps, sort, sigma, sweeps, status, active);         \
-  } while (0)
-    if (oe_ch == 2) BASD_LAUNCH_BLK(2);
-    else if (oe_ch == 4) BASD_LAUNCH_BLK(4);
-    else if (oe_ch == 6) BASD_LAUNCH_BLK(6);
-    else BASD_LAUNCH_BLK(7);
-#undef BASD_LAUNCH_BLK
-    return check_launch("jacobi_svd (block odd-even)");
+  if (rows4 <= 224) {
+    // 2, 4, 6 or 7 chunks of 32 rows in registers; double-buffered mailbox if it fits, else a single one (more than
+    // 204 columns of 129 .. 192 rows, more than 196 of 193 .. 224: the 196-token Procrustes cores of the wide students)
+    const int chunks = (rows4 + 31) / 32;
+    const int maxch = chunks <= 2 ? 2 : (chunks <= 4 ? 4 : (chunks <= 6 ? 6 : 7));
+    const size_t lds2 = (size_t)2 * ((n_cols + 1) / 2) * 32 * maxch * 4 + JACOBI_OE_SCRATCH;
+    if (lds2 > BASD_JACOBI_LDS_BYTES)
+      return launch_oe(jacobi_oe_kernel<7, 1, 1>, 7, 1, "jacobi_svd (odd-even, single mailbox)");
+    const char* what = "jacobi_svd (odd-even)";
+    if (maxch == 2) return launch_oe(jacobi_oe_kernel<2, 1, 2>, 2, 2, what);
+    if (maxch == 4) return launch_oe(jacobi_oe_kernel<4, 1, 2>, 4, 2, what);
+    if (maxch == 6) return launch_oe(jacobi_oe_kernel<6, 1, 2>, 6, 2, what);
+    return launch_oe(jacobi_oe_kernel<7, 1, 2>, 7, 2, what);
   }
-  if (fits && batch >= 512 && npairs <= 96 && oe_ch <= 6) {
-    const int grid2 = (batch + 1) / 2;
-    if (oe_ch == 2) BASD_LAUNCH_OE(2, 2, grid2, lds_oe2);
-    else if (oe_ch == 4) BASD_LAUNCH_OE(4, 2, grid2, lds_oe2);
-    else BASD_LAUNCH_OE(6, 2, grid2, lds_oe2);
-    return check_launch("jacobi_svd (odd-even x2)");
-  }
-  const size_t lds_single = (size_t)npairs * 32 * oe_ch * 4 + oe_scratch;            // NMAT 1, ONE mailbox
-  if (!fits && chunks <= 7 && npairs <= 128 && lds_single <= BASD_JACOBI_LDS_BYTES) {
-    // 193 .. 224 rows x up to 256 columns (the 196 x 196 token-side Procrustes cores of the wide students): the
-    // double-buffered mailbox does not fit, a single one does; still register-resident (the LDS-resident kernel below
-    // takes 7.7 ms for 512 such matrices)
-    allow_full_lds((const void*)jacobi_oe_kernel<7, 1, 1>);
-    hipLaunchKernelGGL((jacobi_oe_kernel<7, 1, 1>), dim3(batch), dim3(threads), lds_single, st, w, batch, m_rows, n_cols, ld,
-                       norm_rows, tol, max_sweeps, sort, sigma, sweeps, active, active_rows, status);
-    return check_launch("jacobi_svd (odd-even, single mailbox)");
-  }
-  if (fits) {
-    if (oe_ch == 2) BASD_LAUNCH_OE(2, 1, batch, lds_oe1);
-    else if (oe_ch == 4) BASD_LAUNCH_OE(4, 1, batch, lds_oe1);
-    else if (oe_ch == 6) BASD_LAUNCH_OE(6, 1, batch, lds_oe1);
-    else BASD_LAUNCH_OE(7, 1, batch, lds_oe1);
-    return check_launch("jacobi_svd (odd-even)");
-  }
-#undef BASD_LAUNCH_OE
-  const size_t lds_bytes = (size_t)n_cols * ld * 4 + (256 + 256 + 8) * 4;
-  if (lds_bytes > BASD_JACOBI_LDS_BYTES)
-    return fail(BASD_ERR_SHAPE, "jacobi_svd: %d x %d (ld %d) needs %zu B of LDS > 160 KiB", m_rows, n_cols, ld, lds_bytes);
-#define BASD_LAUNCH_JACOBI(MC)                                                                     \
-  do {                                                                                             \
-    allow_full_lds((const void*)jacobi_kernel<MC>);                                                  \
-    hipLaunchKernelGGL(jacobi_kernel<MC>, dim3(batch), dim3(threads), lds_bytes, st, w, m_rows,    \
-                       n_cols, ld, norm_rows, tol, max_sweeps, sort, sigma, sweeps, active,       \
-                       active_rows, status);                                                      \
-  } while (0)
-  if (chunks <= 2) BASD_LAUNCH_JACOBI(2);
-  else if (chunks <= 4) BASD_LAUNCH_JACOBI(4);
-  else if (chunks <= 6) BASD_LAUNCH_JACOBI(6);
-  else if (chunks <= 7) BASD_LAUNCH_JACOBI(7);
-  else if (chunks <= 10) BASD_LAUNCH_JACOBI(10);
-  else return fail(BASD_ERR_SHAPE, "jacobi_svd: ld %d > 320 rows unsupported", ld);
-#undef BASD_LAUNCH_JACOBI
-  return check_launch("jacobi_svd");
+  if (n_cols < 8 && rows4 <= 384)   // single mailbox, 3 waves per SIMD
+    return launch_oe(jacobi_oe_kernel<12, 1, 1>, 12, 1, "jacobi_svd (odd-even, tall columns)");
+  return fail(BASD_ERR_SHAPE, "jacobi_svd: %d rows x %d columns is outside every kernel's domain (DESIGN.md section 5)",
+              m_rows, n_cols);
 }

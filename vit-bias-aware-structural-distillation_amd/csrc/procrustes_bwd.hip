@@ -30,7 +30,6 @@
 // (no change), the whole B strip of a group loaded in one burst into 56 registers (the right idea for the measured
 // bottleneck, but 259 spilled registers at the 168-register budget of three waves per SIMD: 1.78 ms).  Next: a
 // 4-wave / 256-register layout that holds the B strip, or the strip staged through LDS with transposing reads.
-#include <stdlib.h>
 #include "basd_common.h"
 
 namespace basd {
@@ -521,30 +520,30 @@ template <typename TO>
 static int launch_side(const float* fac, const float* w, const float* a, const float* gl, int batch, int n, int d,
                        TO* out, float* rowdot, hipStream_t st) {
   const int mt = (n + 15) / 16;
-  // W through LDS (BASD_PBWD_LDSB=0: straight from global memory as in the first version, A/B timing); the parked
-  // epilogue tiles (6 KiB) alias the A buffer: MT >= 4 rows of tiles
-  const char* env = getenv("BASD_PBWD_LDSB");
-  const bool ldsb = !(env && env[0] == '0') && mt >= 4;
-#define BASD_PB_LAUNCH(MT)                                                                                   \
+  // fewer than four rows of tiles: W straight from global memory; from four on W goes through LDS, where the parked
+  // epilogue tiles (6 KiB) alias the A buffer
+#define BASD_PB_DIRECT(MT)                                                                                   \
   do {                                                                                                       \
     const size_t lds = (size_t)4 * MT * 16 * PB_ROWB + (size_t)MT * 16 * 4 * (PB_WAVES + 1);       /* MT >= 2: the parked tiles fit */                                  \
-    const size_t lds2 = (size_t)2 * MT * 16 * PB_ROWB + (size_t)2 * 32 * PB_BPITCH + (size_t)MT * 16 * 4 * (PB_WAVES + 1);  \
-    if (ldsb) {                                                                                              \
-      allow_full_lds((const void*)procrustes_bwd_side_lds_kernel<MT, TO>);                                   \
-      hipLaunchKernelGGL((procrustes_bwd_side_lds_kernel<MT, TO>), dim3(batch), dim3(PB_THREADS), lds2, st, fac, w, a, gl, n, \
-                         d, out, rowdot);                                                                    \
-    } else {                                                                                                 \
-      allow_full_lds((const void*)procrustes_bwd_side_kernel<MT, TO>);                                       \
-      hipLaunchKernelGGL((procrustes_bwd_side_kernel<MT, TO>), dim3(batch), dim3(PB_THREADS), lds, st, fac, w, a, gl, n, d, \
-                         out, rowdot);                                                                       \
-    }                                                                                                        \
+    allow_full_lds((const void*)procrustes_bwd_side_kernel<MT, TO>);                                         \
+    hipLaunchKernelGGL((procrustes_bwd_side_kernel<MT, TO>), dim3(batch), dim3(PB_THREADS), lds, st, fac, w, a, gl, n, d, \
+                       out, rowdot);                                                                         \
   } while (0)
-  if (mt <= 2) BASD_PB_LAUNCH(2);
-  else if (mt <= 4) BASD_PB_LAUNCH(4);
-  else if (mt <= 8) BASD_PB_LAUNCH(8);
-  else if (mt <= 13) BASD_PB_LAUNCH(13);
-  else BASD_PB_LAUNCH(16);
-#undef BASD_PB_LAUNCH
+#define BASD_PB_STAGED(MT)                                                                                   \
+  do {                                                                                                       \
+    const size_t lds2 = (size_t)2 * MT * 16 * PB_ROWB + (size_t)2 * 32 * PB_BPITCH + (size_t)MT * 16 * 4 * (PB_WAVES + 1);  \
+    allow_full_lds((const void*)procrustes_bwd_side_lds_kernel<MT, TO>);                                     \
+    hipLaunchKernelGGL((procrustes_bwd_side_lds_kernel<MT, TO>), dim3(batch), dim3(PB_THREADS), lds2, st, fac, w, a, gl, n, \
+                       d, out, rowdot);                                                                      \
+  } while (0)
+  if (mt <= 2) BASD_PB_DIRECT(2);
+  else if (mt == 3) BASD_PB_DIRECT(4);
+  else if (mt == 4) BASD_PB_STAGED(4);
+  else if (mt <= 8) BASD_PB_STAGED(8);
+  else if (mt <= 13) BASD_PB_STAGED(13);
+  else BASD_PB_STAGED(16);
+#undef BASD_PB_DIRECT
+#undef BASD_PB_STAGED
   return check_launch("procrustes_bwd (fused residual product)");
 }
 

@@ -6,7 +6,6 @@
 //   procrustes_prep   resample + importance normalise + weighted centring + sqrt-weighting
 //                     (src/losses/relational.py:29-46, src/losses/combined.py:9-14)
 // Loads are 16 B per lane (8 bf16 / 4 fp32), grid-stride, <= 2048 workgroups.
-#include <stdlib.h>
 #include "basd_common.h"
 
 namespace basd {
@@ -684,19 +683,17 @@ extern "C" int basd_procrustes_prep(const void* s, int s_dtype, int64_t s_batch_
   const bool vec_ok = D_s % 4 == 0 && D_t % 4 == 0 && s_batch_stride % 4 == 0 && ((uintptr_t)s & 15) == 0 &&
                       ((uintptr_t)t & 15) == 0 && ((uintptr_t)s_w & 15) == 0 && ((uintptr_t)t_w & 15) == 0 && lds4 <= 64 * 1024;
   if (vec_ok && (s_dtype == BASD_DTYPE_F32 || s_dtype == BASD_DTYPE_BF16) && D_s % 64 == 0 && D_t % 64 == 0 && N_s <= 256) {
-    // single pass over the tokens (BASD_PREP_V5=0: the two-pass kernel below, A/B timing)
-    const char* env = getenv("BASD_PREP_V5");
-    if (!(env && env[0] == '0')) {
-      const size_t lds5 = ((size_t)4 * ((N_s + 3) & ~3) + 2 * 32 * 64 + 2 * 64 + 64) * 4;
+    // single pass over the tokens
+    const size_t lds5 = ((size_t)4 * ((N_s + 3) & ~3) + 2 * 32 * 64 + 2 * 64 + 64) * 4;
 #define BASD_PREP5(TS, TPT)                                                                                  \
   hipLaunchKernelGGL((procrustes_prep_v5_kernel<TS, TPT>), dim3(B), dim3(1024), lds5, st, (const TS*)s, t, imp, N_s, N_t, \
                      D_s, D_t, s_batch_stride, s_w, t_w, a, tr)
-      if (s_dtype == BASD_DTYPE_F32) { if (N_s <= 224) BASD_PREP5(float, 7); else BASD_PREP5(float, 8); }
-      else { if (N_s <= 224) BASD_PREP5(unsigned short, 7); else BASD_PREP5(unsigned short, 8); }
+    if (s_dtype == BASD_DTYPE_F32) { if (N_s <= 224) BASD_PREP5(float, 7); else BASD_PREP5(float, 8); }
+    else { if (N_s <= 224) BASD_PREP5(unsigned short, 7); else BASD_PREP5(unsigned short, 8); }
 #undef BASD_PREP5
-      return check_launch("procrustes_prep (single pass)");
-    }
+    return check_launch("procrustes_prep (single pass)");
   }
+  // two passes, vectorised: widths that are not multiples of 64, more than 256 student tokens
   if (vec_ok && (s_dtype == BASD_DTYPE_F32 || s_dtype == BASD_DTYPE_BF16)) {
     if (s_dtype == BASD_DTYPE_F32)
       hipLaunchKernelGGL(procrustes_prep_v4_kernel<float>, dim3(B), dim3(1024), lds4, st, (const float*)s, t, imp,

@@ -7,7 +7,6 @@
 // Workgroup = 512 threads (8 waves), 64-row tiles, grid-stride; the fp64 Gram
 // accumulators (lower-triangular 16x16 tiles) stay in registers across all the
 // tiles of a workgroup and are added to HBM once (fp64 atomics, <= 256 WGs).
-#include <stdlib.h>
 #include "basd_common.h"
 
 namespace basd {
@@ -604,9 +603,8 @@ static void launch_tg_bf16x3(const void* x, int64_t rows, int d_in, int rows_per
   const size_t z_bytes = (size_t)TM2 * (D_OUT + 16) * 4 + (size_t)D_OUT * 12;     // z tile + fp32 mean + fp64 w
   const size_t lds = p_bytes > z_bytes ? p_bytes : z_bytes;
   const int64_t ntiles = (rows + TM2 - 1) / TM2;
-  // 256-row tiles once every CU would get more than one 128-row tile (BASD_TOKEN_GRAM_T256=0: always 128, A/B timing)
-  const char* env = getenv("BASD_TOKEN_GRAM_T256");
-  if (ntiles > 256 && !(env && env[0] == '0')) {
+  // 256-row tiles once every CU would get more than one 128-row tile
+  if (ntiles > 256) {
     const int64_t nt2 = (rows + 2 * TM2 - 1) / (2 * TM2);
     const int grid2 = (int)(nt2 < 256 ? nt2 : 256);
     allow_full_lds((const void*)token_gram_bf16x3_t256_kernel<NCT>);
