@@ -559,9 +559,16 @@ def test_gemm_bf16_gelu_training_pair(nat, M, hidden, d):
     assert float((err / (ref.abs() + 1e-2 * float(ref.abs().max()))).max()) < 1.2e-2
 
 
-@pytest.mark.parametrize("B,C,soft,smoothing,with_geo", [(256, 1000, True, 0.1, True), (256, 1000, False, 0.1, True),
-                                                          (7, 10, True, 0.0, True), (33, 100, False, 0.05, False)])
-def test_ce_uwso_matches_torch(nat, B, C, soft, smoothing, with_geo):
+_CE_CASES = [(256, 1000, True, 0.1, True, 0), (256, 1000, False, 0.1, True, 0), (7, 10, True, 0.0, True, 0),
+             (33, 100, False, 0.05, False, 0)]
+# a confident classifier: one class per row `margin` logits above all others (the target on even rows, another class
+# on odd rows), and row 0 all equal
+_CE_CASES += [(64, C, soft, 0.1, True, margin) for margin in (30, 100) for C in (100, 1000) for soft in (False, True)]
+
+
+@pytest.mark.parametrize("B,C,soft,smoothing,with_geo,margin", _CE_CASES,
+                         ids=["-".join(str(v) for v in c[:5]) + (f"-margin{c[5]}" if c[5] else "") for c in _CE_CASES])
+def test_ce_uwso_matches_torch(nat, B, C, soft, smoothing, with_geo, margin):
     """basd_ce_uwso: CE(label smoothing; soft or hard targets) + UW-SO weights + d total / d logits in two launches,
     against nn.CrossEntropyLoss and the reference's weighting arithmetic through autograd"""
     g = torch.Generator().manual_seed(B + C)
@@ -571,6 +578,14 @@ def test_ce_uwso_matches_torch(nat, B, C, soft, smoothing, with_geo):
         targets = (t / t.sum(-1, keepdim=True)).cuda()
     else:
         targets = torch.randint(C, (B,), generator=g).cuda()
+    if margin:
+        top = targets.argmax(-1) if soft else targets.clone()
+        other = (top + torch.randint(1, C, (B,), generator=g).cuda()) % C
+        top[1::2] = other[1::2]
+        rows = torch.arange(B, device="cuda")
+        logits[rows, top] = -float("inf")
+        logits[rows, top] = logits.amax(-1) + margin
+        logits[0] = 7.25
     geo = torch.tensor(3.7, device="cuda") if with_geo else None
     out4, dl = nat.ce_uwso(logits, targets, smoothing, geo)
     z = logits.double().requires_grad_(True)
