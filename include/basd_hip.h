@@ -63,6 +63,9 @@
  *                          (src/training/trainer.py:183-188, src/train.py:153-160, src/eval.py:16): nn.Linear,
  *                          Attention, nn.LayerNorm and the patch-embedding convolution on split-bf16 (bf16x3) MFMA
  *                          products, fp32 everywhere else
+ *   basd_attention_fwd_f32x3_long
+ *                          the Attention of that forward for 1 <= T <= 1024 tokens (384 px inputs, /14 grids), where
+ *                          basd_attention_fwd_f32x3 refuses the shape
  */
 #ifndef BASD_HIP_H
 #define BASD_HIP_H
@@ -510,6 +513,14 @@ int basd_gemm_f32x3(const void* x_img, const void* w_img, const float* bias, voi
  * logits and softmax in fp32, both products on images; out = the image [B T, 2 H hd] of the [B, T, H hd] output (the
  * proj GEMM's input).  hd in {64, 80}, 1 <= T <= 272. */
 int basd_attention_fwd_f32x3(const float* qkv, int B, int T, int H, int hd, float scale, void* out_img, void* stream);
+
+/* The same contract (inputs, arithmetic, output image) for 1 <= T <= 1024, hd in {64, 80}, without the T x T state:
+ * keys are walked in blocks of 128 with an online softmax (running maximum and sum, rescaled fp32 accumulators), P is
+ * split relative to the running maximum and 1 / sum is applied once to the fp32 output.  The blocks are summed in key
+ * order: the result is bitwise reproducible.  The whole range is accepted (also T <= 272, where callers normally use
+ * the entry above).  No workspace.  BASD_ERR_SHAPE outside the range, checked before anything is enqueued. */
+int basd_attention_fwd_f32x3_long(const float* qkv, int B, int T, int H, int hd, float scale, void* out_img,
+                                  void* stream);
 
 /* nn.LayerNorm in fp32 with the residual step in front of it: s = residual + xscale * x (residual / xscale NULL: no
  * add / no LayerScale gamma [D]), y = LayerNorm(s) with fp32 statistics.  Outputs (NULL: not written): s_out fp32

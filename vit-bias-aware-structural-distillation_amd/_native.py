@@ -32,7 +32,7 @@ EXPORTS = (
     "basd_split_bf16x2_table", "basd_split_patches_bf16x2", "basd_gemm_f32x3", "basd_attention_fwd_f32x3",
     "basd_add_layernorm_fwd_f32", "basd_selector_frames_workspace_bytes", "basd_selector_frames",
     "basd_selector_weights_workspace_bytes", "basd_selector_weights", "basd_attention_fwd_long_bf16",
-    "basd_attention_bwd_long_workspace_bytes", "basd_attention_bwd_long_bf16",
+    "basd_attention_bwd_long_workspace_bytes", "basd_attention_bwd_long_bf16", "basd_attention_fwd_f32x3_long",
 )
 
 
@@ -94,6 +94,7 @@ _SIGNATURES = {
     "basd_split_patches_bf16x2": (_P, _I, _I, _I, _I, _I, _I, _P, _P),
     "basd_gemm_f32x3": (_P, _P, _P, _P, _I64, _I, _I, _I, _P),
     "basd_attention_fwd_f32x3": (_P, _I, _I, _I, _I, _F, _P, _P),
+    "basd_attention_fwd_f32x3_long": (_P, _I, _I, _I, _I, _F, _P, _P),
     "basd_add_layernorm_fwd_f32": (_P, _P, _P, _P, _P, _I64, _I, _F, _P, _P, _P, _P),
 }
 
@@ -973,8 +974,14 @@ def attention_fwd_supported(t: int, hd: int) -> bool:
 
 
 def attention_fwd_f32x3_supported(t: int, hd: int) -> bool:
-    """the fp32 split-bf16 evaluation attention (``attention_fwd_f32x3``) has no long-sequence kernel"""
+    """the range of the single-pass fp32 split-bf16 evaluation attention (``basd_attention_fwd_f32x3``)"""
     return _short_attention_fwd_ok(t, hd)
+
+
+def attention_fwd_f32x3_long_supported(t: int, hd: int) -> bool:
+    """the range of the tiled one (``basd_attention_fwd_f32x3_long``), which ``attention_fwd_f32x3`` calls past the
+    short kernel's"""
+    return hd in (64, 80) and 1 <= t <= 1024
 
 
 def attention_fwd(qkv: torch.Tensor, heads: int, head_dim: int, scale: float, want_importance: bool = False,
@@ -1194,8 +1201,8 @@ def attention_fwd_f32x3(qkv: torch.Tensor, heads: int, head_dim: int, scale: flo
     qkv = qkv.contiguous()
     b, t = qkv.shape[0], qkv.shape[1]
     out = torch.empty(b * t, 2 * heads * head_dim, dtype=torch.bfloat16, device=qkv.device)
-    _check(lib().basd_attention_fwd_f32x3(_ptr(qkv), b, t, heads, head_dim, ctypes.c_float(scale), _ptr(out), _stream()),
-           "basd_attention_fwd_f32x3")
+    name = "basd_attention_fwd_f32x3" if _short_attention_fwd_ok(t, head_dim) else "basd_attention_fwd_f32x3_long"
+    _check(getattr(lib(), name)(_ptr(qkv), b, t, heads, head_dim, ctypes.c_float(scale), _ptr(out), _stream()), name)
     return out
 
 

@@ -13,7 +13,8 @@
 //   split_patches_kernel  [B, C, H, W] fp32 image batch -> unfolded patch rows (the stride-p convolution as a GEMM)
 //   gemm_f32x3_kernel     y = epi(x w^T + bias): fp32 out, exact-erf GELU, or the image of either for the next GEMM
 //   attn_f32x3_kernel     softmax(q k^T scale) v per (batch, head, 128 queries) from the packed fp32 qkv projection;
-//                         fp32 logits (no bf16 rounding), fp32 softmax, P split against V split
+//                         fp32 logits (no bf16 rounding), fp32 softmax, P split against V split; T <= 272
+//   attn_f32x3_long_kernel  the same arithmetic tiled over key blocks of 128 with an online softmax: 1 <= T <= 1024
 //   ln_f32_kernel         s = residual + gamma_ls x (optional), y = LayerNorm(s): fp32 s, fp32 y and / or the image
 #include "basd_common.h"
 
@@ -375,6 +376,210 @@ __global__ __launch_bounds__(512) void attn_f32x3_kernel(const float* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// Tiled attention for 1 <= T <= 1024: the arithmetic of attn_f32x3_kernel without its T x T state.  Workgroup = 8 waves
+// = 8 query tiles of 16 of one (batch, head); grid (B H, ceil(T / 128)).  Keys stream through LDS in blocks of 128: the
+// four images of a block (K hi, K lo, V hi, V lo: [128][LD] bf16 each, 72 KiB at hd 64 and 104 KiB at hd 80) fit
+// together, so a block is staged once; the fp32 rows of the next block are loaded into registers while the current one
+// multiplies and are split on their way into LDS.  Per block: S^T = K Q^T (8 key tiles, fragment layout as above),
+// scaled in fp32, online softmax (running maximum and sum per query, kept on lane & 15; the output accumulators are
+// rescaled by exp(m_old - m_new), fetched from the query's lane), P unnormalised in (0, 1] against the running maximum
+// split into (hi, lo), O += P V through ds_read_tr16_b64.  The blocks are walked in key order by every wave: the sum has
+// one order and the result is bitwise reproducible.  1 / sum is applied once to the fp32 output.
+template <int HD>
+__global__ __launch_bounds__(512) void attn_f32x3_long_kernel(const float* __restrict__ qkv, int T, int H, float scale,
+                                                              unsigned short* __restrict__ out) {
+  constexpr int KB = 128;                            // keys per block
+  constexpr int NKT = KB / 16, NKS = KB / 32;
+  constexpr int NDS = (HD + 31) / 32;
+  constexpr int NDT = HD / 16;
+  constexpr int LD = NDS * 32 + 8;
+  constexpr int NC4 = HD / 4;                        // 4-float chunks of a row that hold data
+  constexpr int NLD = KB * NC4 / 512;                // chunks per thread, block and operand (4 | 5)
+  static_assert(KB * NC4 % 512 == 0, "a key block is a whole number of chunks per thread");
+  extern __shared__ __align__(16) unsigned short sm[];
+  unsigned short* Kh = sm;                            // [KB][LD] each
+  unsigned short* Kl = sm + KB * LD;
+  unsigned short* Vh = sm + 2 * KB * LD;
+  unsigned short* Vl = sm + 3 * KB * LD;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int li = lane & 15, g = lane >> 4;
+  const int b = blockIdx.x / H, h = blockIdx.x - b * H;
+  const int C = H * HD;
+  const size_t row = (size_t)3 * C;
+  const float* base = qkv + (size_t)b * T * row + (size_t)h * HD;
+  const int q0 = (blockIdx.y * 8 + wave) * 16;
+  const bool active = q0 < T;                        // wave-uniform; idle waves still stage and meet the barriers
+
+  float4 kreg[NLD], vreg[NLD];
+  auto load_kv = [&](int k0) {
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+      const int idx = tid + 512 * i;
+      const int r = idx / NC4, c4 = idx - r * NC4;
+      kreg[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      vreg[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (k0 + r < T) {                              // keys past the end are zero rows (and masked below)
+        const float* p = base + (size_t)(k0 + r) * row + 4 * c4;
+        kreg[i] = *reinterpret_cast<const float4*>(p + C);
+        vreg[i] = *reinterpret_cast<const float4*>(p + 2 * C);
+      }
+    }
+  };
+  load_kv(0);
+  // the K columns hd .. 32 NDS - 1 meet the zero columns of Q in the contraction: written once, never staged over
+  if constexpr (NDS * 32 > HD) {
+    if (tid < 2 * KB) {
+      unsigned short* p = (tid & 1 ? Kl : Kh) + (tid >> 1) * LD + HD;
+#pragma unroll
+      for (int c = 0; c < NDS * 32 - HD; c += 8) *reinterpret_cast<uint4*>(p + c) = make_uint4(0u, 0u, 0u, 0u);
+    }
+  }
+  // Q fragments: query q0 + li, d = 32 ks + 8 g .. + 7
+  ev_bf16x8 qh[NDS], ql[NDS];
+#pragma unroll
+  for (int ks = 0; ks < NDS; ++ks) {
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = 0.f;
+    if (q0 + li < T && 32 * ks + 8 * g < HD) {
+      const float* p = base + (size_t)(q0 + li) * row + 32 * ks + 8 * g;
+      const float4 f0 = *reinterpret_cast<const float4*>(p), f1 = *reinterpret_cast<const float4*>(p + 4);
+      v[0] = f0.x; v[1] = f0.y; v[2] = f0.z; v[3] = f0.w; v[4] = f1.x; v[5] = f1.y; v[6] = f1.z; v[7] = f1.w;
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      unsigned short hi, lo;
+      ev_split(v[e], hi, lo);
+      qh[ks][e] = (short)hi;
+      ql[ks][e] = (short)lo;
+    }
+  }
+
+  float m_run = -3.0e38f, l_run = 0.f;               // of query q0 + li (the same value in the four lane groups)
+  ev_f32x4 o[NDT];
+#pragma unroll
+  for (int dt = 0; dt < NDT; ++dt) o[dt] = (ev_f32x4){0.f, 0.f, 0.f, 0.f};
+  const int nblocks = (T + KB - 1) / KB;
+  for (int j = 0; j < nblocks; ++j) {
+    const int k0 = j * KB;
+    if (j > 0) lds_barrier();                        // every wave is done with the previous block
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+      const int idx = tid + 512 * i;
+      const int r = idx / NC4, c4 = idx - r * NC4;
+      const float kv[4] = {kreg[i].x, kreg[i].y, kreg[i].z, kreg[i].w};
+      const float vv[4] = {vreg[i].x, vreg[i].y, vreg[i].z, vreg[i].w};
+      uint2 hi, lo;
+      ev_split4(kv, hi, lo);
+      *reinterpret_cast<uint2*>(Kh + r * LD + 4 * c4) = hi;
+      *reinterpret_cast<uint2*>(Kl + r * LD + 4 * c4) = lo;
+      ev_split4(vv, hi, lo);
+      *reinterpret_cast<uint2*>(Vh + r * LD + 4 * c4) = hi;
+      *reinterpret_cast<uint2*>(Vl + r * LD + 4 * c4) = lo;
+    }
+    lds_barrier();
+    if (j + 1 < nblocks) load_kv(k0 + KB);           // in flight during this block's products
+    if (!active) continue;
+
+    // ---- S^T of the 8 key tiles
+    ev_f32x4 s[NKT];
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt) {
+      ev_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < NDS; ++ks) {
+        const int off = (16 * kt + li) * LD + 32 * ks + 8 * g;
+        const ev_bf16x8 kh = *reinterpret_cast<const ev_bf16x8*>(Kh + off);
+        const ev_bf16x8 kl = *reinterpret_cast<const ev_bf16x8*>(Kl + off);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kl, qh[ks], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kh, ql[ks], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kh, qh[ks], acc, 0, 0, 0);
+      }
+      s[kt] = acc;
+    }
+    // ---- online softmax of this block
+    float mx = -3.0e38f;
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        s[kt][r] *= scale;
+        if (k0 + 16 * kt + 4 * g + r >= T) s[kt][r] = -3.0e38f;
+        mx = fmaxf(mx, s[kt][r]);
+      }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float m_new = fmaxf(m_run, mx);            // every block holds a valid key: m_new is finite
+    const float alpha = __expf(m_run - m_new);       // first block: exp(-3e38) = 0 against l_run = 0, o = 0
+    float sum = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float p = __expf(s[kt][r] - m_new);
+        s[kt][r] = p;
+        sum += p;
+      }
+    sum += __shfl_xor(sum, 16, 64);
+    sum += __shfl_xor(sum, 32, 64);
+    l_run = fmaf(l_run, alpha, sum);
+    m_run = m_new;
+    // O rows are the queries q0 + 4 g + r: their factors live on lanes 4 g + r
+    if (j > 0) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float ar = __shfl(alpha, 4 * g + r, 64);
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt) o[dt][r] *= ar;
+      }
+    }
+    // ---- O += P V
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) {
+      ev_bf16x8 ph, pl;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        unsigned short hi, lo;
+        ev_split(s[2 * ks + (e >> 2)][e & 3], hi, lo);
+        ph[e] = (short)hi;
+        pl[e] = (short)lo;
+      }
+      const int qq = li >> 2, pp = li & 3;
+#pragma unroll
+      for (int dt = 0; dt < NDT; ++dt) {
+        const int off = (32 * ks + 4 * g + qq) * LD + 16 * dt + 4 * pp;
+        const ev_v4s h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ev_lds_v4s*)(Vh + off));
+        const ev_v4s h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ev_lds_v4s*)(Vh + off + 16 * LD));
+        const ev_v4s l0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ev_lds_v4s*)(Vl + off));
+        const ev_v4s l1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ev_lds_v4s*)(Vl + off + 16 * LD));
+        const ev_bf16x8 vh = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+        const ev_bf16x8 vl = {l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
+        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pl, vh, o[dt], 0, 0, 0);
+        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ph, vl, o[dt], 0, 0, 0);
+        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ph, vh, o[dt], 0, 0, 0);
+      }
+    }
+  }
+  if (!active) return;
+  // o[dt][r] = O[query q0 + 4 g + r][d = 16 dt + li] * sum; 1 / sum belongs to query q0 + li: fetch it from lane 4 g + r
+  const float inv = 1.f / l_run;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float ir = __shfl(inv, 4 * g + r, 64);
+    const int q = q0 + 4 * g + r;
+    if (q >= T) continue;
+    unsigned short* dst = out + (size_t)(b * T + q) * 2 * C + h * HD;
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) {
+      unsigned short hi, lo;
+      ev_split(o[dt][r] * ir, hi, lo);
+      dst[16 * dt + li] = hi;
+      dst[C + 16 * dt + li] = lo;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // LayerNorm, one wave per row, D % 4 == 0, D <= 2048 (<= 8 float4 per lane); statistics two-pass in fp32 from registers.
 __global__ __launch_bounds__(256) void ln_f32_kernel(const float* x, const float* res,
                                                      const float* __restrict__ xscale, const float* __restrict__ gamma,
@@ -441,6 +646,15 @@ static void launch_attn(const float* qkv, int B, int T, int H, float scale, unsi
   allow_full_lds((const void*)attn_f32x3_kernel<NKT, HD>);
   hipLaunchKernelGGL((attn_f32x3_kernel<NKT, HD>), dim3(B * H, (((T + 15) >> 4) + 7) / 8), dim3(512), lds, st, qkv, T,
                      H, scale, out);
+}
+
+template <int HD>
+static void launch_attn_long(const float* qkv, int B, int T, int H, float scale, unsigned short* out, hipStream_t st) {
+  constexpr int LD = ((HD + 31) / 32) * 32 + 8;
+  const size_t lds = (size_t)4 * 128 * LD * sizeof(unsigned short);
+  allow_full_lds((const void*)attn_f32x3_long_kernel<HD>);
+  hipLaunchKernelGGL(attn_f32x3_long_kernel<HD>, dim3(B * H, (T + 127) / 128), dim3(512), lds, st, qkv, T, H, scale,
+                     out);
 }
 
 }  // namespace basd
@@ -534,6 +748,20 @@ extern "C" int basd_attention_fwd_f32x3(const float* qkv, int B, int T, int H, i
   BASD_ATTN32(17)
 #undef BASD_ATTN32
   return fail(BASD_ERR_SHAPE, "attention_fwd_f32x3: T = %d", T);
+}
+
+extern "C" int basd_attention_fwd_f32x3_long(const float* qkv, int B, int T, int H, int hd, float scale, void* out_img,
+                                             void* stream) {
+  using namespace basd;
+  if (B <= 0) return BASD_OK;
+  if (T < 1 || T > 1024 || (hd != 64 && hd != 80) || H < 1)
+    return fail(BASD_ERR_SHAPE, "attention_fwd_f32x3_long: need hd in {64, 80}, 1 <= T <= 1024, H >= 1 (got T=%d hd=%d H=%d)",
+                T, hd, H);
+  if (!ev_aligned(qkv, 16)) return fail(BASD_ERR_SHAPE, "attention_fwd_f32x3_long: qkv must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  if (hd == 64) launch_attn_long<64>(qkv, B, T, H, scale, (unsigned short*)out_img, st);
+  else launch_attn_long<80>(qkv, B, T, H, scale, (unsigned short*)out_img, st);
+  return check_launch("attention_fwd_f32x3_long");
 }
 
 extern "C" int basd_add_layernorm_fwd_f32(const float* x, const float* residual, const float* xscale, const float* gamma,

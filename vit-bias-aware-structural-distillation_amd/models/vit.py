@@ -342,7 +342,8 @@ class Block(nn.Module):
         a, d = self.attn, self.attn.qkv.in_features
         lins = (a.qkv, a.proj, self.mlp.fc1, self.mlp.fc2)
         return (type(self.mlp) is Mlp and isinstance(self.mlp.act, nn.GELU) and self.mlp.act.approximate == "none"
-                and a.tap is None and ops.attention_fwd_f32x3_supported(t, a.head_dim)
+                and a.tap is None and (ops.attention_fwd_f32x3_supported(t, a.head_dim)
+                                       or ops.attention_fwd_f32x3_long_supported(t, a.head_dim))
                 and ops.f32x3_layernorm_supported(d)
                 and all(l.bias is not None and l.weight.dtype == torch.float32 and l.bias.dtype == torch.float32
                         and ops.f32x3_gemm_supported(l.out_features, l.in_features) for l in lins)
