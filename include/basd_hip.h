@@ -529,6 +529,35 @@ int basd_add_layernorm_fwd_f32(const float* x, const float* residual, const floa
                                const float* beta, int64_t rows, int D, float eps, float* s_out, float* y, void* y_img,
                                void* stream);
 
+/* ---- frozen ConvNeXt-V2 teacher trunk (models/convnext.py).  A feature map [B, H, W, C] is a channels-last matrix of
+ * B H W bf16 rows with row stride ld >= C (elements); the columns C .. ld are zero (padded layout of the widths the GEMM
+ * does not tile: 96 channels in rows of 128).  The pointwise layers are basd_gemm_bf16 on these rows. */
+
+/* Depthwise 7 x 7 convolution (zero padding 3, bias) followed by LayerNorm over the C channels of every output pixel,
+ * one launch; the convolution output is never stored.  x [B, H, W, ld_in] bf16, w49 [49, C] bf16 tap-major
+ * (w49[(dy * 7 + dx) * C + c] = conv weight[c, 0, dy, dx]), bias / gamma / beta fp32 [C]; fp32 accumulation and two-pass
+ * fp32 statistics -> y [B, H, W, ld_out] bf16, columns C .. ld_out written as zero.  Any H, W >= 1; C % 8 == 0,
+ * 8 <= C <= 2048; ld % 8 == 0, C <= ld_in, C <= ld_out <= 2 C; 16-byte aligned buffers; y must not alias x.
+ * With H = W = 1 and the one-hot centre tap it is LayerNorm over the first C columns of rows of stride ld. */
+int basd_dwconv7_ln_bf16(const void* x, const void* w49, const float* bias, const float* gamma, const float* beta,
+                         int B, int H, int W, int C, int ld_in, int ld_out, float eps, void* y, void* stream);
+
+/* Global response normalisation of ConvNeXt-V2, in place on x [B, HW, C] bf16 (contiguous; fc1's output):
+ *   g[b, c] = ||x[b, :, c]||_2,  n = g / (mean_c g + eps),  x <- bf16(x + bias + weight x n),  weight / bias fp32 [C].
+ * Two launches: sums of squares in fp32 into the workspace (>= basd_grn_workspace_bytes(B, HW, C) bytes, else
+ * BASD_ERR_WORKSPACE; fixed summation order, no atomics), then the apply pass.  C % 8 == 0, 8 <= C <= 4096. */
+int64_t basd_grn_workspace_bytes(int B, int HW, int C);
+int basd_grn_bf16(void* x, const float* weight, const float* bias, int B, int HW, int C, float eps, void* workspace,
+                  int64_t workspace_bytes, void* stream);
+
+/* Non-overlapping p x p patches of a bf16 image / feature map as GEMM rows (a stride-p, kernel-p convolution is the
+ * GEMM of these rows with the re-laid weight).  x is addressed through ELEMENT strides (sb, sc, sh, sw) of its
+ * [B, C, H, W] index, so NCHW and channels-last sources (and padded rows: C = ld) are the same call:
+ *   out[(b (H/p) + oh) (W/p) + ow, (i p + j) C + c] = x[b, c, oh p + i, ow p + j],  columns C p p .. K_pad zero.
+ * H % p == 0, W % p == 0, K_pad % 8 == 0, K_pad >= C p p; out 16-byte aligned.  Exact (a copy). */
+int basd_patchify_bf16(const void* x, int B, int C, int H, int W, int64_t sb, int64_t sc, int64_t sh, int64_t sw,
+                       int p, int K_pad, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

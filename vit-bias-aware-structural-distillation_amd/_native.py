@@ -33,6 +33,7 @@ EXPORTS = (
     "basd_add_layernorm_fwd_f32", "basd_selector_frames_workspace_bytes", "basd_selector_frames",
     "basd_selector_weights_workspace_bytes", "basd_selector_weights", "basd_attention_fwd_long_bf16",
     "basd_attention_bwd_long_workspace_bytes", "basd_attention_bwd_long_bf16", "basd_attention_fwd_f32x3_long",
+    "basd_dwconv7_ln_bf16", "basd_grn_workspace_bytes", "basd_grn_bf16", "basd_patchify_bf16",
 )
 
 
@@ -96,6 +97,10 @@ _SIGNATURES = {
     "basd_attention_fwd_f32x3": (_P, _I, _I, _I, _I, _F, _P, _P),
     "basd_attention_fwd_f32x3_long": (_P, _I, _I, _I, _I, _F, _P, _P),
     "basd_add_layernorm_fwd_f32": (_P, _P, _P, _P, _P, _I64, _I, _F, _P, _P, _P, _P),
+    "basd_dwconv7_ln_bf16": (_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P),
+    "basd_grn_workspace_bytes": (_I, _I, _I),
+    "basd_grn_bf16": (_P, _P, _P, _I, _I, _I, _F, _P, _I64, _P),
+    "basd_patchify_bf16": (_P, _I, _I, _I, _I, _I64, _I64, _I64, _I64, _I, _I, _P, _P),
 }
 
 
@@ -1229,3 +1234,59 @@ def add_layernorm_f32(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, 
                                             _ptr(beta.contiguous()), ctypes.c_int64(rows), d, ctypes.c_float(eps),
                                             _ptr(s), _ptr(y), _ptr(img), _stream()), "basd_add_layernorm_fwd_f32")
     return tuple(t for t in (s, y, img) if t is not None)
+
+
+# --------------------------------------------------------------------------- ConvNeXt-V2 teacher trunk (csrc/convnext.hip)
+def dwconv7_ln_supported(c: int, ld_in: int, ld_out: int) -> bool:
+    return (c % 8 == 0 and 8 <= c <= 2048 and ld_in % 8 == 0 and ld_out % 8 == 0 and c <= ld_in
+            and c <= ld_out <= 2 * c)
+
+
+def dwconv7_ln(x: torch.Tensor, w49: torch.Tensor, bias: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+               eps: float, ld_out: int | None = None) -> torch.Tensor:
+    """x [B, H, W, ld_in] bf16 channels-last rows (columns C .. ld_in zero), w49 [49, C] bf16 tap-major, bias / gamma /
+    beta fp32 [C] -> LayerNorm_C(depthwise 7x7 (x) + bias) [B, H, W, ld_out] bf16, columns C .. ld_out zero."""
+    _need_cuda(x, w49, bias, gamma, beta)
+    assert x.dtype == torch.bfloat16 and w49.dtype == torch.bfloat16 and x.dim() == 4 and x.is_contiguous()
+    assert bias.dtype == gamma.dtype == beta.dtype == torch.float32
+    b, h, w, ld_in = x.shape
+    c = w49.shape[1]
+    ld_out = ld_in if ld_out is None else ld_out
+    assert w49.shape == (49, c) and w49.is_contiguous() and dwconv7_ln_supported(c, ld_in, ld_out), (c, ld_in, ld_out)
+    y = torch.empty(b, h, w, ld_out, dtype=torch.bfloat16, device=x.device)
+    _check(lib().basd_dwconv7_ln_bf16(_ptr(x), _ptr(w49), _ptr(bias.contiguous()), _ptr(gamma.contiguous()),
+                                      _ptr(beta.contiguous()), b, h, w, c, ld_in, ld_out, ctypes.c_float(eps), _ptr(y),
+                                      _stream()), "basd_dwconv7_ln_bf16")
+    return y
+
+
+def grn_supported(c: int) -> bool:
+    return c % 8 == 0 and 8 <= c <= 4096
+
+
+def grn_(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float = 1e-6) -> torch.Tensor:
+    """GRN of ConvNeXt-V2 IN PLACE on x [B, HW, C] bf16 contiguous; weight / bias fp32 [C].  Returns x."""
+    _need_cuda(x, weight, bias)
+    assert x.dtype == torch.bfloat16 and x.dim() == 3 and x.is_contiguous() and grn_supported(x.shape[2])
+    assert weight.dtype == torch.float32 and bias.dtype == torch.float32
+    b, hw, c = x.shape
+    need = int(lib().basd_grn_workspace_bytes(b, hw, c))
+    rec = _scratch("grn", x.device, need)
+    _check(lib().basd_grn_bf16(_ptr(x), _ptr(weight.contiguous()), _ptr(bias.contiguous()), b, hw, c, ctypes.c_float(eps),
+                               _ptr(rec.buf), ctypes.c_int64(rec.buf.numel()), _stream()), "basd_grn_bf16")
+    _scratch_used(rec)
+    return x
+
+
+def patchify(x: torch.Tensor, p: int, k_pad: int) -> torch.Tensor:
+    """x [B, C, H, W] bf16 in any strides (NCHW, channels-last, or the NCHW view of padded channels-last rows) ->
+    [B (H/p) (W/p), k_pad] bf16 rows with column (i p + j) C + c = x[b, c, oh p + i, ow p + j], zero behind C p p."""
+    _need_cuda(x)
+    assert x.dtype == torch.bfloat16 and x.dim() == 4
+    b, c, h, w = x.shape
+    assert h % p == 0 and w % p == 0 and k_pad % 8 == 0 and k_pad >= c * p * p, (tuple(x.shape), p, k_pad)
+    out = torch.empty(b * (h // p) * (w // p), k_pad, dtype=torch.bfloat16, device=x.device)
+    sb, sc, sh, sw = x.stride()
+    _check(lib().basd_patchify_bf16(_ptr(x), b, c, h, w, ctypes.c_int64(sb), ctypes.c_int64(sc), ctypes.c_int64(sh),
+                                    ctypes.c_int64(sw), p, k_pad, _ptr(out), _stream()), "basd_patchify_bf16")
+    return out

@@ -1,17 +1,21 @@
-"""Convolutional teachers for the cross-architecture configuration (BASELINE configs[2]: ResNet-50 teacher,
-single "layer" of 7 x 7 = 49 tokens x 2048 channels, uniform importance).
+"""Convolutional teachers for the cross-architecture configuration: the ResNets defined here (BASELINE configs[2]:
+ResNet-50 teacher, single "layer" of 7 x 7 = 49 tokens x 2048 channels, uniform importance) and the ConvNeXt-V2
+family of ``models/convnext.py`` (what the reference's cross-arch overlay names,
+``configs/experiment/basd_imagenet_cross_arch.yaml:6``), both listed in ``CNN_PRESETS``.
 
-The reference takes CNN teachers from timm (``src/models/teacher.py:118``; its cross-arch overlay names a
-ConvNeXt, ``configs/experiment/basd_imagenet_cross_arch.yaml:6``) and only ever calls ``forward_features`` on them
-(``teacher.py:184-191``).  timm / torchvision are not available offline, so the trunk is defined here with the
-torchvision / timm parameter names (``conv1``, ``bn1``, ``layer1..4.N.conv1`` ...) so that a local state dict of
-either package loads.  The frozen trunk is a black box for the BASD step ("c3"): it runs through
-PyTorch-ROCm / MIOpen in channels-last bf16, no hand-written kernel is involved.
+The reference takes CNN teachers from timm (``src/models/teacher.py:118``) and only ever calls ``forward_features``
+on them (``teacher.py:184-191``).  timm / torchvision are not available offline, so the trunks are defined in this
+package with the torchvision / timm parameter names (``conv1``, ``bn1``, ``layer1..4.N.conv1`` ...) so that a local
+state dict of either package loads.  The frozen ResNet trunk is a black box for the BASD step (SURVEY section 8,
+"c3"): it runs through PyTorch-ROCm / MIOpen in channels-last bf16, no hand-written kernel is involved.  The
+ConvNeXt-V2 trunk runs on the package's own kernels (``csrc/convnext.hip`` + ``basd_gemm_bf16``).
 """
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
+
+from .convnext import CONVNEXT_PRESETS
 
 
 class Bottleneck(nn.Module):
@@ -75,6 +79,7 @@ class ResNet(nn.Module):
 CNN_PRESETS = {
     "resnet50": lambda: ResNet((3, 4, 6, 3)),
     "resnet101": lambda: ResNet((3, 4, 23, 3)),
+    **CONVNEXT_PRESETS,
 }
 
 

@@ -68,7 +68,9 @@ def probe_model(model: nn.Module, img_size: int) -> dict:
     """Architecture record with the reference's keys (teacher.py:100-110): ``embed_dim, heads_per_layer, depth,
     mlp_ratio, layer_paths, attn_subpath, has_cls_token, feature_format, num_tokens``.  One pass over the stage
     modules collects heads / MLP width, one forward of a zero image through a hook on the LAST stage tells the
-    feature format (token / nchw / nhwc) and the token count.  Runs on the model's own device."""
+    feature format (token / nchw / nhwc) and the token count.  Runs on the model's own device.  It needs the forward
+    to go through the stage modules: probe BEFORE a trunk that bypasses them is prepared (``ConvNeXtV2.prepare_fused``
+    replaces the stages' forward on bf16 device tensors, so their hooks no longer fire), as ``load_teacher`` does."""
     layer_paths = _stage_paths(model)
     width = getattr(model, "embed_dim", None) or getattr(model, "num_features", None)
     heads, attn_name, hidden = [], None, None
@@ -133,12 +135,24 @@ def fold_layerscale(model: nn.Module) -> int:
     return folded
 
 
+def _probe_scope(model: nn.Module):
+    """The probe's one zero image runs through the model BEFORE the bf16 cast.  A trunk that reports its own library
+    path (models/convnext.py) would count that fp32 forward as a fallback of the training path: it is a declared
+    library call instead."""
+    import contextlib
+
+    from ..losses._ops import declared_library_calls
+    return declared_library_calls() if hasattr(model, "prepare_fused") else contextlib.nullcontext()
+
+
 def load_teacher(model_name: str, img_size: int, *, weights: str | None = None, device="cuda",
                  seed: int = 42, patch_size: int | None = None, dtype=torch.bfloat16) -> TeacherModel:
     """Build (not download: reference teacher.py:113-148 fetches from the network) the named teacher -- a ViT preset of
     ``models/vit.py`` or a CNN preset of ``models/cnn.py`` -- frozen, in eval mode, weights pre-cast to bf16; ``weights``
     = a local state dict (timm / torchvision parameter names)."""
     from .cnn import CNN_PRESETS, create_cnn
+    if model_name not in VIT_PRESETS and model_name not in CNN_PRESETS and model_name.split(".", 1)[0] in CNN_PRESETS:
+        model_name = model_name.split(".", 1)[0]      # timm's pretrained tag ("convnextv2_tiny.fcmae"): weights are local
     gen_state = torch.random.get_rng_state()
     torch.manual_seed(seed)
     if model_name in VIT_PRESETS:
@@ -156,13 +170,16 @@ def load_teacher(model_name: str, img_size: int, *, weights: str | None = None, 
     for p in model.parameters():
         p.requires_grad = False
     fold_layerscale(model)
-    info = probe_model(model, img_size)
+    with _probe_scope(model):
+        info = probe_model(model, img_size)
     model = model.to(dtype)
     if info["feature_format"] != "token" and torch.device(device).type == "cuda":
         model = model.to(memory_format=torch.channels_last)
     for m in model.modules():           # LayerNorm parameters stay fp32 (autocast semantics); the fused
         if isinstance(m, nn.LayerNorm):   # kernel takes bf16 activations with fp32 gamma / beta
             m.float()
+    if hasattr(model, "prepare_fused") and torch.device(device).type == "cuda" and dtype == torch.bfloat16:
+        model.prepare_fused()           # weight images of the fused trunk, once: the teacher is frozen
     return TeacherModel(model=model, embed_dim=info["embed_dim"], heads_per_layer=info["heads_per_layer"],
                         depth=info["depth"], mlp_ratio=info["mlp_ratio"], layer_paths=info["layer_paths"],
                         attn_subpath=info["attn_subpath"], has_cls_token=info["has_cls_token"],
