@@ -446,8 +446,11 @@ int basd_procrustes_fwd(const float* s_w, const float* t_w, int batch, int n, in
  *     out[b, i, :]  = 2 gl[b] sqrt(a[b, i]) (W - fac W)[b, i, :]        (fp32 or bf16)
  *     rowdot[b, i]  = 2 gl[b] <(W - fac W)[b, i, :], W[b, i, :]>
  * in one launch: the product runs on the bf16 matrix cores as a three-product split of both fp32 operands (relative
- * error 2^-16), residual / scaling / row dots in its epilogue.  4 <= n <= 256, n % 4 == 0, d % 16 == 0, 16-byte
- * aligned buffers. */
+ * error 2^-16), residual / scaling / row dots in its epilogue.  4 <= n <= 1024, d % 16 == 0, d >= 16; w and out 16-byte
+ * aligned.  n <= 256 with n % 4 == 0 (fac 16-byte aligned): one workgroup per matrix; every other n: row tiles of 128
+ * rows, one workgroup each (fac 4-byte aligned; 4-byte factor loads when n % 4 != 0 or fac is not 16-byte aligned).  The
+ * row dots are summed in a fixed order, without atomics: the results are bitwise reproducible.  BASD_ERR_SHAPE outside
+ * the range. */
 int basd_procrustes_bwd_side(const float* fac, const float* w, const float* a, const float* gl, int batch, int n, int d,
                              void* out, int out_dtype, float* rowdot, void* stream);
 
@@ -455,7 +458,10 @@ int basd_procrustes_bwd_side(const float* fac, const float* w, const float* a, c
  * (d loss / d value), fac_s / a_t (basd_procrustes_fwd outputs; fac_s is [batch, n, n] when n <= d_s, else
  * [batch, n, d_s]) -> g_s [batch, n, d_s] (g_s_dtype: BASD_DTYPE_F32 | BASD_DTYPE_BF16), g_t [batch, n, d_t] fp32
  * (gradients w.r.t. the RAW student tokens and the resampled teacher tokens), g_a [batch, n] (w.r.t. the normalised
- * importance).  workspace: >= basd_procrustes_bwd_workspace_bytes(batch, n) bytes (the two row-dot vectors). */
+ * importance).  workspace: >= basd_procrustes_bwd_workspace_bytes(batch, n) bytes (the two row-dot vectors).
+ * 4 <= n <= 1024 and d_t % 16 == 0; token side (n <= d_s): d_s % 16 == 0, both sides through basd_procrustes_bwd_side;
+ * feature side (n > d_s, the only one basd_procrustes_fwd reaches past 256 tokens): d_s % 4 == 0, the student side
+ * through basd_procrustes_bwd_rows. */
 int64_t basd_procrustes_bwd_workspace_bytes(int batch, int n);
 int basd_procrustes_bwd(const float* s_w, const float* t_w, const float* a, const float* gl, const float* fac_s,
                         const float* a_t, int batch, int n, int d_s, int d_t, void* g_s, int g_s_dtype, float* g_t,

@@ -1,20 +1,34 @@
 """basd_procrustes_bwd (fused bf16 three-product split + residual epilogue) against the library fp32 bmm + the row
-kernels, at the c2 shapes (1024 x [196, 196] x [196, 768])."""
-import os, sys, time, torch
+kernels.  Default: the c2 shapes (1024 x [196, 196] x [196, 768]); --n / --batch (with --d-s / --d-t) time one other
+shape, e.g. the 384 px ones (--batch 256 --n 576, --n 729: the row-tiled kernel).  Each figure is the median of --runs
+device-event brackets of --iters calls, the two paths alternated in one process."""
+import argparse, os, statistics, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import basd_amd._native as nat
 
+ap = argparse.ArgumentParser()
+ap.add_argument("--n", type=int, default=None, help="tokens (rows of a matrix); default: the two c2 shapes")
+ap.add_argument("--batch", type=int, default=256)
+ap.add_argument("--d-s", type=int, default=192)
+ap.add_argument("--d-t", type=int, default=768)
+ap.add_argument("--iters", type=int, default=10)
+ap.add_argument("--runs", type=int, default=3)
+args = ap.parse_args()
 
-def timeit(f, it=10):
-    f(); torch.cuda.synchronize()
-    t0 = time.perf_counter()
+
+def bracket(f, it):
+    """ms per call between two device events"""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
     for _ in range(it):
         f()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / it * 1e3
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / it
 
 
-for (batch, n, d_s, d_t) in [(1024, 196, 192, 768), (512, 196, 384, 1024)]:
+shapes = [(1024, 196, 192, 768), (512, 196, 384, 1024)] if args.n is None else [(args.batch, args.n, args.d_s, args.d_t)]
+for (batch, n, d_s, d_t) in shapes:
     g = torch.Generator().manual_seed(0)
     s_w = torch.randn(batch, n, d_s, generator=g).cuda(); t_w = torch.randn(batch, n, d_t, generator=g).cuda()
     a = torch.rand(batch, n, generator=g).cuda() + 0.1; a = (a / a.sum(-1, keepdim=True)).contiguous()
@@ -34,6 +48,14 @@ for (batch, n, d_s, d_t) in [(1024, 196, 192, 768), (512, 196, 384, 1024)]:
         return g_s, g_t, (dot_s + dot_t) / (2.0 * a)
 
     f, u = fused(), unfused()
+    torch.cuda.synchronize()
     err = float((f[1] - u[1]).norm() / u[1].norm())
-    print(f"batch {batch} n {n} d_s {d_s} d_t {d_t}: fused {timeit(fused):.3f} ms, library bmm + rows {timeit(unfused):.3f} ms, "
-          f"g_t rel diff {err:.1e}")
+    for _ in range(2):                                       # warm both paths at this shape
+        fused(); unfused()
+    torch.cuda.synchronize()
+    tf, tu = [], []
+    for _ in range(args.runs):                               # alternated
+        tf.append(bracket(fused, args.iters)); tu.append(bracket(unfused, args.iters))
+    fmt = lambda xs: "/".join(f"{x:.3f}" for x in xs)
+    print(f"batch {batch} n {n} d_s {d_s} d_t {d_t}: fused {statistics.median(tf):.3f} ms ({fmt(tf)}), "
+          f"library bmm + rows {statistics.median(tu):.3f} ms ({fmt(tu)}), g_t rel diff {err:.1e}", flush=True)

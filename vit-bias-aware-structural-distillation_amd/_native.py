@@ -719,7 +719,8 @@ def procrustes_fwd(s_w: torch.Tensor, t_w: torch.Tensor, tol: float = 1e-13):
 
 
 def procrustes_bwd_supported(n: int, d_s: int, d_t: int) -> bool:
-    return 4 <= n <= 256 and n % 4 == 0 and d_t % 16 == 0 and d_t >= 16 and (n > d_s or (d_s % 16 == 0 and d_s >= 16)) and d_s % 4 == 0
+    # n <= 256 with n % 4 == 0: one workgroup per matrix; everything else up to 1024 rows: the row-tiled kernel
+    return 4 <= n <= 1024 and d_t % 16 == 0 and d_t >= 16 and (n > d_s or (d_s % 16 == 0 and d_s >= 16)) and d_s % 4 == 0
 
 
 def procrustes_bwd(s_w: torch.Tensor, t_w: torch.Tensor, a: torch.Tensor, gl: torch.Tensor, fac_s: torch.Tensor,

@@ -547,19 +547,289 @@ static int launch_side(const float* fac, const float* w, const float* a, const f
   return check_launch("procrustes_bwd (fused residual product)");
 }
 
+
+// ---- the row-tiled form: 257 <= n <= 1024, and every n % 4 != 0 -----------------------------------------------------
+// The kernels above keep all ceil(n / 16) accumulator tiles of a 16-column strip in one wave and give a workgroup a
+// whole matrix: 144 accumulator registers per lane at 576 rows.  Here a workgroup owns ONE ROW TILE of PBL_RT = 128 rows
+// (8 accumulator tiles per strip, the MT = 8 budget of the staged kernel) of one matrix and runs the K loop over all n
+// rows of W: grid = batch x ceil(n / 128), the row tiles of a matrix adjacent in the grid so that they run together and
+// share W in the caches (at batch-major order 256 matrices x 1.8 MB of W would be re-read from HBM once per row tile).
+// Same arithmetic and the same staging as procrustes_bwd_side_lds_kernel<8>: A (the 128 x 32 slice of the factor) and
+// the W tile ([32 k rows][96 columns]) go through LDS as (hi, mid) bf16 planes, three MFMAs per tile and K step, the
+// residual / scaling / row dots in the epilogue through the parked tile.  A row tile sees all d columns, so its row
+// dots are complete inside the workgroup: each wave adds its column groups in order into its own slice, the slices are
+// added in wave order -- no atomics, bitwise reproducible.  Rows >= n of the last tile and the K tail (n % 32) are
+// zeroed by selects on the way into LDS and never stored.
+// VEC4 = false (n % 4 != 0: the rows of the factor, and every matrix of the batch but the first, are not 16-byte
+// aligned -- 729 tokens of a /14 grid at 384 px) loads the factor with 4-byte loads; W, the gradient and the LDS
+// traffic are the same (d % 16 == 0 keeps their rows aligned).
+// Compiler's resource report (hipcc --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage; LDS is dynamic:
+// 37376 bytes = 2 x 10240 A planes + 2 x 6656 W planes + 7 x 512 row dots / scales; two workgroups per CU):
+//   <float, true>            VGPRs 156  AGPRs 0  scratch 0 bytes/lane  occupancy 3 waves/SIMD
+//   <unsigned short, true>   VGPRs 156  AGPRs 0  scratch 0 bytes/lane  occupancy 3 waves/SIMD
+//   <float, false>           VGPRs 164  AGPRs 0  scratch 0 bytes/lane  occupancy 3 waves/SIMD
+//   <unsigned short, false>  VGPRs 164  AGPRs 0  scratch 0 bytes/lane  occupancy 3 waves/SIMD
+constexpr int PBL_MT = 8;                   // m tiles (16 rows each) of a row tile
+constexpr int PBL_RT = 16 * PBL_MT;         // rows of a row tile
+
+template <typename TO, bool VEC4>
+__global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3))) void procrustes_bwd_side_long_kernel(
+    const float* __restrict__ fac, const float* __restrict__ w, const float* __restrict__ a,
+    const float* __restrict__ gl, int n, int d, int tiles, TO* __restrict__ out, float* __restrict__ rowdot) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  constexpr int MT = PBL_MT;
+  constexpr int PLANE = MT * 16 * PB_ROWB;                 // one bf16 plane of one K step
+  constexpr int ITEMS = (MT * 16 * 4 + PB_THREADS - 1) / PB_THREADS;         // staging items (row, k octet) per thread and K step
+  unsigned char* abuf = smem;                              // [2 planes][128 rows][PB_ROWB]
+  unsigned char* bbuf = smem + 2 * PLANE;                  // [2 planes][32 k rows][PB_BPITCH]: the W tile of a K step
+  float* s_dotw = reinterpret_cast<float*>(smem + 2 * PLANE + 2 * 32 * PB_BPITCH);  // [waves][128] row dots
+  float* s_c = s_dotw + PB_WAVES * MT * 16;                // [128] row scales 2 gl sqrt(a)
+  float* s_park = reinterpret_cast<float*>(abuf);          // [waves][16 rows][16 columns] epilogue tile (operands idle)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = (int)blockIdx.x / tiles;
+  const int r0 = ((int)blockIdx.x - b * tiles) * PBL_RT;   // first row of this tile; r0 < n
+  const float* A = fac + (size_t)b * n * n;
+  const float* W = w + (size_t)b * n * d;
+  TO* O = out + (size_t)b * n * d;
+  const int ksteps = (n + 31) >> 5;
+  const int strips = d >> 4;
+  const float c2 = 2.f * gl[b];
+  for (int i = tid; i < PBL_RT; i += PB_THREADS) {
+#pragma unroll
+    for (int wv_ = 0; wv_ < PB_WAVES; ++wv_) s_dotw[wv_ * PBL_RT + i] = 0.f;
+    s_c[i] = r0 + i < n ? c2 * __builtin_amdgcn_sqrtf(a[(size_t)b * n + r0 + i]) : 0.f;
+  }
+
+  // Staging of one K step of the A slice: item = (row of the tile, k octet), the global loads issued before the MFMAs
+  // of the current step, the split and the LDS writes after them.  Every address is clamped into the matrix (rows >= n
+  // to row n - 1, the end of the last row to the last 16 / 4 bytes); what was clamped is zeroed by a select.
+  float sa[ITEMS][8];
+  unsigned sa_off[ITEMS];
+  const unsigned a_last = (unsigned)n * (unsigned)n - (VEC4 ? 4u : 1u);
+#pragma unroll
+  for (int it = 0; it < ITEMS; ++it) {
+    const int item = tid + PB_THREADS * it;
+    const int row = r0 + (item >> 2), oct = item & 3;
+    sa_off[it] = (unsigned)(row < n ? row : n - 1) * (unsigned)n + (unsigned)(oct * 8);
+  }
+  auto stage_load = [&](int ks) {
+    const unsigned kbase = (unsigned)ks * 32u;
+#pragma unroll
+    for (int it = 0; it < ITEMS; ++it) {
+      const unsigned o0 = sa_off[it] + kbase;
+      if constexpr (VEC4) {
+        const unsigned o1 = o0 + 4u;
+        const float4 v0 = *reinterpret_cast<const float4*>(A + (o0 < a_last ? o0 : a_last));
+        const float4 v1 = *reinterpret_cast<const float4*>(A + (o1 < a_last ? o1 : a_last));
+        sa[it][0] = v0.x; sa[it][1] = v0.y; sa[it][2] = v0.z; sa[it][3] = v0.w;
+        sa[it][4] = v1.x; sa[it][5] = v1.y; sa[it][6] = v1.z; sa[it][7] = v1.w;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const unsigned oj = o0 + (unsigned)j;
+          sa[it][j] = A[oj < a_last ? oj : a_last];
+        }
+      }
+    }
+  };
+  auto stage_store = [&](int ks) {
+#pragma unroll
+    for (int it = 0; it < ITEMS; ++it) {
+      const int item = tid + PB_THREADS * it;
+      const int row = item >> 2, oct = item & 3;
+      if (item < MT * 16 * 4) {
+        const int k0 = ks * 32 + oct * 8;
+        const bool rok = r0 + row < n;
+        float x[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = (rok && k0 + j < n) ? sa[it][j] : 0.f;
+        uint4 hi, mid;
+        pb_split2(x[0], x[1], hi.x, mid.x); pb_split2(x[2], x[3], hi.y, mid.y);
+        pb_split2(x[4], x[5], hi.z, mid.z); pb_split2(x[6], x[7], hi.w, mid.w);
+        const unsigned lo = (unsigned)row * PB_ROWB + (unsigned)oct * 16;
+        *reinterpret_cast<uint4*>(abuf + lo) = hi;
+        *reinterpret_cast<uint4*>(abuf + PLANE + lo) = mid;
+      }
+    }
+  };
+
+  for (int g0 = 0; g0 < strips; g0 += PB_WAVES) {          // column groups of PB_WAVES strips (96 columns), one per wave
+    const int s0 = g0 + wave;
+    const bool has = s0 < strips;
+    const int col = (lane & 15);
+    // the W tile of a K step: global -> registers (16-byte loads) -> (hi, mid) planes in LDS; the wave's B fragment
+    // comes out of the transposing read, as in procrustes_bwd_side_lds_kernel
+    const int c0 = g0 * 16;                                // first column of the group
+    float4 sb[2];
+    auto bload = [&](int ks) {
+#pragma unroll
+      for (int it = 0; it < 2; ++it) {
+        const int item = tid + PB_THREADS * it;            // 768 items = 32 rows x 24 quads
+        const int row = item / 24, q = item - row * 24;
+        const int kr = ks * 32 + row, cc = c0 + 4 * q;
+        const bool ok = kr < n && cc < d;
+        sb[it] = *reinterpret_cast<const float4*>(W + (size_t)(ok ? kr : 0) * d + (ok ? cc : 0));
+        if (!ok) sb[it] = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    };
+    auto bstore = [&]() {
+#pragma unroll
+      for (int it = 0; it < 2; ++it) {
+        const int item = tid + PB_THREADS * it;
+        const int row = item / 24, q = item - row * 24;
+        uint2 hi, mid;
+        pb_split2(sb[it].x, sb[it].y, hi.x, mid.x); pb_split2(sb[it].z, sb[it].w, hi.y, mid.y);
+        const unsigned lo = (unsigned)row * PB_BPITCH + (unsigned)q * 8;
+        *reinterpret_cast<uint2*>(bbuf + lo) = hi;
+        *reinterpret_cast<uint2*>(bbuf + 32 * PB_BPITCH + lo) = mid;
+      }
+    };
+    __syncthreads();                                       // previous group's fragment / parked-tile reads are done
+    stage_load(0);
+    bload(0);
+    stage_store(0);
+    bstore();
+    __syncthreads();
+    pb_f32x4 acc[MT];
+#pragma unroll
+    for (int i = 0; i < MT; ++i) acc[i] = (pb_f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int ks = 0; ks < ksteps; ++ks) {
+      const bool more = ks + 1 < ksteps;
+      if (more) {                                          // next step's operands: loads only, stored after the MFMAs
+        bload(ks + 1);
+        stage_load(ks + 1);
+      }
+      pb_bf16x8 bh, bm;
+      {
+        const int li = lane & 15, qq = li >> 2, pp = li & 3;
+        const unsigned char* b0 = bbuf + (size_t)((lane >> 4) * 8 + qq) * PB_BPITCH + (size_t)(wave * 16 + 4 * pp) * 2;
+        const pb_v4s h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pb_lds_v4s*)b0);
+        const pb_v4s h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pb_lds_v4s*)(b0 + 4 * PB_BPITCH));
+        const pb_v4s m0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pb_lds_v4s*)(b0 + 32 * PB_BPITCH));
+        const pb_v4s m1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pb_lds_v4s*)(b0 + 32 * PB_BPITCH + 4 * PB_BPITCH));
+        bh = (pb_bf16x8){h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+        bm = (pb_bf16x8){m0[0], m0[1], m0[2], m0[3], m1[0], m1[1], m1[2], m1[3]};
+      }
+      // A fragments in two batches of four tiles (one exposed LDS latency per batch; the fence keeps the second
+      // batch's reads from being hoisted on top of the first: registers)
+      const unsigned char* ap = abuf + (size_t)(lane & 15) * PB_ROWB + (lane >> 4) * 16;
+      constexpr int HB = MT / 2;
+#pragma unroll
+      for (int hb = 0; hb < 2; ++hb) {
+        pb_bf16x8 fh[HB], fm[HB];
+#pragma unroll
+        for (int j = 0; j < HB; ++j) {
+          const int i = hb * HB + j;
+          fh[j] = *reinterpret_cast<const pb_bf16x8*>(ap + (size_t)i * 16 * PB_ROWB);
+          fm[j] = *reinterpret_cast<const pb_bf16x8*>(ap + PLANE + (size_t)i * 16 * PB_ROWB);
+        }
+#pragma unroll
+        for (int j = 0; j < HB; ++j) {
+          const int i = hb * HB + j;
+          acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[j], bh, acc[i], 0, 0, 0);
+          acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[j], bm, acc[i], 0, 0, 0);
+          acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fm[j], bh, acc[i], 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      __syncthreads();                                     // every wave has read the operands of step ks
+      if (more) { stage_store(ks + 1); bstore(); }
+      __syncthreads();                                     // step ks + 1 is complete
+    }
+    // ---- epilogue: acc[i][r] = P at row r0 + 16 i + 4 (lane >> 4) + r, column 16 s0 + (lane & 15).  The wave parks one
+    // 16 x 16 tile at a time in its own 1 KiB of LDS and reads it back row-wise (16 bytes per lane, 64 contiguous bytes
+    // per row segment for the W load and the store, a 4-lane reduction per row), as in the kernels above.
+    float* park = s_park + wave * 256;
+    const int g4 = lane >> 4;
+    const int prow = lane >> 2, pch = lane & 3;            // row-wise walk: 16 rows x 4 chunks of 4 columns
+    const int pcol = s0 * 16 + pch * 4;
+    constexpr int H0 = MT / 2;                             // tiles per batch: the W loads of a batch are in flight together
+#pragma unroll
+    for (int hb = 0; hb < 2; ++hb) {
+      float4 wq[H0];
+#pragma unroll
+      for (int j = 0; j < H0; ++j) {
+        const int row = r0 + (hb * H0 + j) * 16 + prow;
+        const bool ok = has && row < n;
+        wq[j] = *reinterpret_cast<const float4*>(W + (unsigned)(ok ? row : 0) * (unsigned)d + (unsigned)(ok ? pcol : 0));
+      }
+#pragma unroll
+      for (int j = 0; j < H0; ++j) {
+        const int i = hb * H0 + j;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) park[(g4 * 4 + r) * 16 + col] = acc[i][r];
+        // wave-private tile: the wave's own LDS writes precede its reads (in order), no barrier
+        const float4 pv = *reinterpret_cast<const float4*>(park + prow * 16 + pch * 4);
+        const int lrow = i * 16 + prow, row = r0 + lrow;
+        const bool ok = has && row < n;                    // rows >= n are never stored
+        const unsigned off = (unsigned)(ok ? row : 0) * (unsigned)d + (unsigned)(ok ? pcol : 0);
+        const float4 wv = wq[j];
+        const float cr = s_c[lrow];
+        const float4 rv = make_float4(wv.x - pv.x, wv.y - pv.y, wv.z - pv.z, wv.w - pv.w);
+        float dot = ok ? fmaf(rv.x, wv.x, fmaf(rv.y, wv.y, fmaf(rv.z, wv.z, rv.w * wv.w))) : 0.f;
+        if (ok) {
+          if constexpr (sizeof(TO) == 4) {
+            *reinterpret_cast<float4*>(O + off) = make_float4(cr * rv.x, cr * rv.y, cr * rv.z, cr * rv.w);
+          } else {
+            uint2 o;
+            o.x = (unsigned)__builtin_bit_cast(unsigned short, (__bf16)(cr * rv.x)) |
+                  ((unsigned)__builtin_bit_cast(unsigned short, (__bf16)(cr * rv.y)) << 16);
+            o.y = (unsigned)__builtin_bit_cast(unsigned short, (__bf16)(cr * rv.z)) |
+                  ((unsigned)__builtin_bit_cast(unsigned short, (__bf16)(cr * rv.w)) << 16);
+            *reinterpret_cast<uint2*>(O + off) = o;
+          }
+        }
+        dot += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(dot), 0xB1, 0xF, 0xF, true));     // quad_perm 1,0,3,2
+        dot += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(dot), 0x4E, 0xF, 0xF, true));     // quad_perm 2,3,0,1
+        if (pch == 0) s_dotw[wave * PBL_RT + lrow] += c2 * dot;
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < PBL_RT; i += PB_THREADS) {
+    if (r0 + i < n) {
+      float t = 0.f;
+#pragma unroll
+      for (int wv_ = 0; wv_ < PB_WAVES; ++wv_) t += s_dotw[wv_ * PBL_RT + i];
+      rowdot[(size_t)b * n + r0 + i] = t;
+    }
+  }
+}
+
+template <typename TO>
+static int launch_side_long(const float* fac, const float* w, const float* a, const float* gl, int batch, int n, int d,
+                            TO* out, float* rowdot, hipStream_t st) {
+  const int tiles = (n + PBL_RT - 1) / PBL_RT;
+  const size_t lds = (size_t)2 * PBL_RT * PB_ROWB + (size_t)2 * 32 * PB_BPITCH + (size_t)PBL_RT * 4 * (PB_WAVES + 1);
+  const dim3 grid((unsigned)batch * (unsigned)tiles);
+  if (n % 4 == 0 && (((uintptr_t)fac) & 15) == 0)
+    hipLaunchKernelGGL((procrustes_bwd_side_long_kernel<TO, true>), grid, dim3(PB_THREADS), lds, st, fac, w, a, gl, n, d,
+                       tiles, out, rowdot);
+  else
+    hipLaunchKernelGGL((procrustes_bwd_side_long_kernel<TO, false>), grid, dim3(PB_THREADS), lds, st, fac, w, a, gl, n, d,
+                       tiles, out, rowdot);
+  return check_launch("procrustes_bwd (row-tiled residual product)");
+}
+
 }  // namespace basd
 
 extern "C" int basd_procrustes_bwd_side(const float* fac, const float* w, const float* a, const float* gl, int batch,
                                         int n, int d, void* out, int out_dtype, float* rowdot, void* stream) {
   using namespace basd;
   if (batch <= 0) return BASD_OK;
-  if (n < 4 || n > 256 || n % 4 || d < 16 || d % 16 || (((uintptr_t)fac) & 15) || (((uintptr_t)w) & 15) || (((uintptr_t)out) & 15))
-    return fail(BASD_ERR_SHAPE, "procrustes_bwd_side: need 4 <= n <= 256, n %% 4 == 0, d %% 16 == 0, 16-byte aligned "
-                                "buffers (n=%d d=%d)", n, d);
+  const bool whole = n <= 256 && n % 4 == 0;   // one workgroup per matrix (launch_side); everything else is row-tiled
+  if (n < 4 || n > 1024 || d < 16 || d % 16 || (((uintptr_t)fac) & (whole ? 15 : 3)) || (((uintptr_t)w) & 15) ||
+      (((uintptr_t)out) & 15))
+    return fail(BASD_ERR_SHAPE, "procrustes_bwd_side: need 4 <= n <= 1024, d %% 16 == 0, 16-byte aligned buffers "
+                                "(n=%d d=%d)", n, d);
   hipStream_t st = (hipStream_t)stream;
-  if (out_dtype == BASD_DTYPE_F32) return launch_side<float>(fac, w, a, gl, batch, n, d, (float*)out, rowdot, st);
+  if (out_dtype == BASD_DTYPE_F32)
+    return whole ? launch_side<float>(fac, w, a, gl, batch, n, d, (float*)out, rowdot, st)
+                 : launch_side_long<float>(fac, w, a, gl, batch, n, d, (float*)out, rowdot, st);
   if (out_dtype == BASD_DTYPE_BF16)
-    return launch_side<unsigned short>(fac, w, a, gl, batch, n, d, (unsigned short*)out, rowdot, st);
+    return whole ? launch_side<unsigned short>(fac, w, a, gl, batch, n, d, (unsigned short*)out, rowdot, st)
+                 : launch_side_long<unsigned short>(fac, w, a, gl, batch, n, d, (unsigned short*)out, rowdot, st);
   return fail(BASD_ERR_DTYPE, "procrustes_bwd_side: out dtype %d", out_dtype);
 }
 

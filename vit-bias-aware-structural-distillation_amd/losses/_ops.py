@@ -111,7 +111,12 @@ class record_library_gemms:
 
     def __exit__(self, *exc):
         self._probe.__exit__(*exc)
-        _GEMM_RECORDERS.remove(self.seen)
+        # by identity: list.remove compares with ==, and two recorders that have seen the same sites (two empty sets of
+        # nested blocks, say) are equal -- the inner block would take the outer one's set off the list
+        for i, rec in enumerate(_GEMM_RECORDERS):
+            if rec is self.seen:
+                del _GEMM_RECORDERS[i]
+                break
         return False
 
 
