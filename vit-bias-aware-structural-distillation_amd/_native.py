@@ -818,8 +818,9 @@ def trinv(lwork: torch.Tensor, piv: torch.Tensor, rank: torch.Tensor, skip: torc
 
 # Tiles a workgroup of the persistent GEMM kernel multiplies before it retires (basd_gemm_bf16's ``tile_run``): 0 = its
 # whole share, the fastest form when the GEMM has the GPU to itself (the default: inference, eager / single-stream steps);
-# the Trainer sets 2 while its two-stream pipelined step is in use (a persistent launch holds every CU until it ends and
-# the other stream's short kernels queue behind it: measured 41.3 vs 39.5 ms per c2 step).
+# the Trainer sets basd.gemm_tile_run (default 1) while its two-stream pipelined step is in use (a persistent launch holds
+# every CU until it ends and the other stream's short kernels queue behind it: measured 41.3 vs 39.5 ms per c2 step with
+# 2; training/trainer.py has the later measurements that made 1 the default).
 GEMM_TILE_RUN = 0
 # The same for the GEMMs of the TRAINED model that take the persistent kernel (fc1 + GELU forward, fc2 input gradient +
 # GELU backward: basd_gemm_bf16_gelu_fwd / _bwd): they are on the step's own chain, not on the side stream.
