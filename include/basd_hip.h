@@ -66,6 +66,13 @@
  *   basd_attention_fwd_f32x3_long
  *                          the Attention of that forward for 1 <= T <= 1024 tokens (384 px inputs, /14 grids), where
  *                          basd_attention_fwd_f32x3 refuses the shape
+ *   basd_dwconv7_ln_bf16, basd_grn_bf16, basd_patchify_bf16
+ *                          the frozen ConvNeXt-V2 teacher trunk (src/models/teacher.py through timm)
+ *   basd_resample_u8, basd_ta_normalize_u8
+ *                          the torchvision v2 transforms of both training views (src/data/datasets.py:80-94 clean /
+ *                          evaluation view, :137-149 augmented view), which the reference runs in its loader workers
+ *
+ * 63 entries in all (basd_version and basd_last_error included).
  */
 #ifndef BASD_HIP_H
 #define BASD_HIP_H
@@ -564,6 +571,37 @@ int basd_grn_bf16(void* x, const float* weight, const float* bias, int B, int HW
  * H % p == 0, W % p == 0, K_pad % 8 == 0, K_pad >= C p p; out 16-byte aligned.  Exact (a copy). */
 int basd_patchify_bf16(const void* x, int B, int C, int H, int W, int64_t sb, int64_t sc, int64_t sh, int64_t sw,
                        int p, int K_pad, void* out, void* stream);
+
+/* ---- both training views from one uint8 batch (data/device_views.py).  The CPU functions of data/transforms.py are the
+ * definition, stage by stage. */
+
+/* Window -> antialiased bilinear resize -> offset crop -> horizontal flip, uint8 in and out.  src [B, 3, H, W] uint8
+ * (contiguous); rec [B, 9] int32 on the device, per sample
+ *   {top, left, h, w}   the source window inside the H x W canvas (the sample's own size for the clean view),
+ *   {nh, nw}            the size the window is resized to (virtual: only the S x S part below is computed),
+ *   {off_y, off_x}      the output's offset inside that resized image,
+ *   flip                non-zero: the S x S output is mirrored horizontally;
+ * out [B, 3, S, S] uint8, 4-byte aligned, written as packed 32-bit words.  The arithmetic is that of
+ * F.interpolate(mode="bilinear", antialias=True, align_corners=False) on the fp32 window (separable triangle filter,
+ * scale = n_in / n_out, support = max(scale, 1), weights normalised per output index, the horizontal pass first with an
+ * fp32 value between the passes), then round-half-even and a clamp to 0 .. 255: against the CPU at most one level off at
+ * fp32 near-ties, and exact where a window has the output's size.  Clean view: window = the image, (nh, nw) =
+ * Resize(int)'s size, offset = CenterCrop's; augmented view: window = the RandomResizedCrop, (nh, nw) = (S, S), offset 0.
+ * Every index is clamped into the canvas and the resized image: a bad record cannot read out of bounds.
+ * 3 <= S <= 1024, 1 <= H, W <= 16384. */
+int basd_resample_u8(const void* src, const int* rec, int B, int H, int W, int S, void* out, void* stream);
+
+/* One TrivialAugmentWide operation per image, then ToDtype(float32, scale=True) and Normalize: img [B, 3, S, S] uint8,
+ * ops [B] int32 (index into TA_WIDE_OPS: Identity, ShearX, ShearY, TranslateX, TranslateY, Rotate, Brightness, Color,
+ * Contrast, Sharpness, Posterize, Solarize, AutoContrast, Equalize; anything else is Identity) and mags [B] fp64 (the
+ * signed magnitude apply_ta_op is called with), both on the device; ops NULL: Identity for every image (the clean
+ * view; mags is then not read).  out [B, 3, S, S] fp32, 16-byte aligned, = ((op(img) / 255) - mean_c) / std_c.
+ * One workgroup per image: the reductions its operation needs in LDS (fp32 gray mean for Contrast, per-channel min / max
+ * for AutoContrast, per-channel 256-bin histogram and integer LUT for Equalize), then 16-byte stores with a scalar head
+ * and tail.  The affine coordinates and the blends keep the CPU's fp32 operation order (no contraction).
+ * 3 <= S <= 1024. */
+int basd_ta_normalize_u8(const void* img, const int* ops, const double* mags, int B, int S, float mean0, float mean1,
+                         float mean2, float std0, float std1, float std2, float* out, void* stream);
 
 #ifdef __cplusplus
 }

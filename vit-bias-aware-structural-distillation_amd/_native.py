@@ -34,6 +34,7 @@ EXPORTS = (
     "basd_selector_weights_workspace_bytes", "basd_selector_weights", "basd_attention_fwd_long_bf16",
     "basd_attention_bwd_long_workspace_bytes", "basd_attention_bwd_long_bf16", "basd_attention_fwd_f32x3_long",
     "basd_dwconv7_ln_bf16", "basd_grn_workspace_bytes", "basd_grn_bf16", "basd_patchify_bf16",
+    "basd_resample_u8", "basd_ta_normalize_u8",
 )
 
 
@@ -101,6 +102,8 @@ _SIGNATURES = {
     "basd_grn_workspace_bytes": (_I, _I, _I),
     "basd_grn_bf16": (_P, _P, _P, _I, _I, _I, _F, _P, _I64, _P),
     "basd_patchify_bf16": (_P, _I, _I, _I, _I, _I64, _I64, _I64, _I64, _I, _I, _P, _P),
+    "basd_resample_u8": (_P, _P, _I, _I, _I, _I, _P, _P),
+    "basd_ta_normalize_u8": (_P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P),
 }
 
 
@@ -1291,4 +1294,42 @@ def patchify(x: torch.Tensor, p: int, k_pad: int) -> torch.Tensor:
     sb, sc, sh, sw = x.stride()
     _check(lib().basd_patchify_bf16(_ptr(x), b, c, h, w, ctypes.c_int64(sb), ctypes.c_int64(sc), ctypes.c_int64(sh),
                                     ctypes.c_int64(sw), p, k_pad, _ptr(out), _stream()), "basd_patchify_bf16")
+    return out
+
+
+# --------------------------------------------------------------------------- device-side dual views (csrc/dual_view.hip)
+def dual_view_supported(image_size: int) -> bool:
+    """output sizes basd_resample_u8 / basd_ta_normalize_u8 take (odd ones included)"""
+    return 3 <= image_size <= 1024
+
+
+def resample_u8(images: torch.Tensor, records: torch.Tensor, image_size: int) -> torch.Tensor:
+    """images [B, 3, H, W] uint8, records [B, 9] int32 {top, left, h, w, nh, nw, off_y, off_x, flip} ->
+    [B, 3, S, S] uint8: window -> antialiased bilinear resize to (nh, nw) -> S x S part at the offset -> flip."""
+    _need_cuda(images, records)
+    assert images.dtype == torch.uint8 and images.dim() == 4 and images.shape[1] == 3 and images.is_contiguous()
+    b, _, h, w = images.shape
+    assert records.dtype == torch.int32 and records.shape == (b, 9) and records.is_contiguous()
+    assert dual_view_supported(image_size), image_size
+    out = torch.empty(b, 3, image_size, image_size, dtype=torch.uint8, device=images.device)
+    _check(lib().basd_resample_u8(_ptr(images), _ptr(records), b, h, w, image_size, _ptr(out), _stream()),
+           "basd_resample_u8")
+    return out
+
+
+def ta_normalize_u8(images: torch.Tensor, ops: torch.Tensor | None, mags: torch.Tensor | None, mean, std) -> torch.Tensor:
+    """images [B, 3, S, S] uint8, ops [B] int32 (index into TA_WIDE_OPS) and mags [B] fp64 (None, None: Identity), mean /
+    std: three floats each -> ((op(image) / 255) - mean) / std as fp32 [B, 3, S, S]."""
+    _need_cuda(images, ops, mags)
+    assert images.dtype == torch.uint8 and images.dim() == 4 and images.shape[1] == 3 and images.is_contiguous()
+    b, _, s, s2 = images.shape
+    assert s == s2 and dual_view_supported(s), tuple(images.shape)
+    assert (ops is None) == (mags is None) and len(mean) == 3 and len(std) == 3
+    if ops is not None:
+        assert ops.dtype == torch.int32 and ops.shape == (b,) and ops.is_contiguous()
+        assert mags.dtype == torch.float64 and mags.shape == (b,) and mags.is_contiguous()
+    out = torch.empty(b, 3, s, s, dtype=torch.float32, device=images.device)
+    f = ctypes.c_float
+    _check(lib().basd_ta_normalize_u8(_ptr(images), _ptr(ops), _ptr(mags), b, s, f(mean[0]), f(mean[1]), f(mean[2]),
+                                      f(std[0]), f(std[1]), f(std[2]), _ptr(out), _stream()), "basd_ta_normalize_u8")
     return out

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
+from .device_views import DeviceDualView, DeviceEvalView
 from .transforms import AugmentTransform, EvalTransform
 
 _NUM_WORKERS = 8
@@ -154,12 +155,26 @@ def _loader(ds, batch_size, *, shuffle, drop_last, num_workers, seed):
                       generator=g)
 
 
+def _require_npz(ds: LocalImageSplit, dataset_name: str) -> None:
+    if ds.kind != "npz":
+        raise ValueError(f"{dataset_name}: device_views needs a .npz split (uniform image size); a directory split "
+                         "goes through the CPU path (device_views=False)")
+
+
 def create_eval_loader(dataset_name: str, *, image_size: int, batch_size: int, mean, std, crop_ratio: float,
-                       num_workers: int = _NUM_WORKERS, class_names=None) -> DataLoader:
-    """reference :97-123: ``{"pixel_values", "label"}`` batches of the evaluation split, not shuffled"""
+                       num_workers: int = _NUM_WORKERS, class_names=None, device_views: bool = False) -> DataLoader:
+    """reference :97-123: ``{"pixel_values", "label"}`` batches of the evaluation split, not shuffled.
+    ``device_views``: the loader yields raw ``{"image" uint8, "label"}`` batches and carries the object that builds
+    ``pixel_values`` on the device as ``loader.device_views`` (``evaluate_model`` applies it)."""
     info = dataset_info(dataset_name)
-    tf = build_eval_transform(image_size, mean=mean, std=std, crop_ratio=crop_ratio)
     ds = LocalImageSplit(dataset_name, info["eval_split"], class_names=class_names or info["class_names"])
+    if device_views:
+        _require_npz(ds, dataset_name)
+        views = DeviceEvalView(image_size, mean, std, crop_ratio)
+        loader = _loader(ds, batch_size, shuffle=False, drop_last=False, num_workers=num_workers, seed=0)
+        loader.device_views = views
+        return loader
+    tf = build_eval_transform(image_size, mean=mean, std=std, crop_ratio=crop_ratio)
     ds.transform = _EvalView(tf)
     return _loader(ds, batch_size, shuffle=False, drop_last=False, num_workers=num_workers, seed=0)
 
@@ -196,9 +211,24 @@ class _DualView:
         return {"clean": self.clean_tf(img), "augmented": self.aug_tf(img, gen), "label": label}
 
 
-def create_dataloaders(config, *, teacher_stats, num_workers: int = _NUM_WORKERS):
+class _RawDualView(_DualView):
+    """``device_views``: the worker returns the uint8 image and the augmentation decisions of sample i in epoch e,
+    drawn from the generator ``_DualView`` seeds; ``DeviceDualView`` builds both views from them on the device"""
+
+    def __init__(self, views: DeviceDualView, seed: int):
+        super().__init__(None, None, seed)
+        self.views = views
+
+    def __call__(self, i: int, img: torch.Tensor, label: int):
+        gen = torch.Generator().manual_seed((self.seed * 1_000_003 + self.epoch) * 2_000_003 + i)
+        return {"image": img, "view_params": self.views.draw(img.shape[1], img.shape[2], gen), "label": label}
+
+
+def create_dataloaders(config, *, teacher_stats, num_workers: int = _NUM_WORKERS, device_views=None):
     """reference :126-178: (train loader of dual-view batches, evaluation loader).  ``teacher_stats`` = (mean, std) the
-    frozen teacher was trained with (``TeacherModel.mean / .std``)."""
+    frozen teacher was trained with (``TeacherModel.mean / .std``).  ``device_views`` (default:
+    ``config.data.device_views``, else off): the workers ship uint8 images and augmentation parameters, and the loaders
+    carry the objects that build the views on the device as ``loader.device_views`` (data/device_views.py)."""
     name = config.data.dataset
     info = dataset_info(name)
     mean, std = get_channel_stats(name)
@@ -209,8 +239,17 @@ def create_dataloaders(config, *, teacher_stats, num_workers: int = _NUM_WORKERS
     clean_tf = build_eval_transform(image_size, mean=teacher_mean, std=teacher_std, crop_ratio=crop_ratio)
     seed = int(config.run.get("seed", 0)) if hasattr(config, "run") else 0
     train = LocalImageSplit(name, info["train_split"])
-    train.transform = _DualView(clean_tf, aug_tf, seed)
+    if device_views is None:
+        device_views = bool(config.data.get("device_views", False))
+    if device_views:
+        _require_npz(train, name)
+        views = DeviceDualView(image_size, mean, std, teacher_mean, teacher_std, crop_ratio)
+        train.transform = _RawDualView(views, seed)
+    else:
+        train.transform = _DualView(clean_tf, aug_tf, seed)
     train_loader = _loader(train, config.data.batch_size, shuffle=True, drop_last=True, num_workers=num_workers, seed=seed)
+    if device_views:
+        train_loader.device_views = views
     val_loader = create_eval_loader(name, image_size=image_size, batch_size=config.data.batch_size, mean=mean, std=std,
-                                    crop_ratio=crop_ratio, num_workers=num_workers)
+                                    crop_ratio=crop_ratio, num_workers=num_workers, device_views=bool(device_views))
     return train_loader, val_loader

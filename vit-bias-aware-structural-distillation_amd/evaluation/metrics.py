@@ -41,7 +41,10 @@ def evaluate_model(model: nn.Module, data_loader, criterion: nn.Module, *, num_c
     dev = _device_of(model)
     tally = torch.zeros(4, dtype=torch.float64, device=dev)        # hits@1, hits@5, summed loss, samples
     keep = None if valid_indices is None else torch.as_tensor(valid_indices, device=dev)
+    views = getattr(data_loader, "device_views", None)      # raw uint8 batches: pixel_values are built on the device
     for batch in data_loader:
+        if views is not None:
+            batch = views({k: v.to(dev, non_blocking=True) for k, v in batch.items()})
         x = batch["pixel_values"].to(dev, non_blocking=True)
         y = batch["label"].to(dev, non_blocking=True)
         logits = model(x).float()

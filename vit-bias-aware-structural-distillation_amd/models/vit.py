@@ -11,11 +11,14 @@ split order, ``attn.num_heads``, scale ``hd**-0.5``, CLS token at index 0
 ``attn.qkv``, ``attn.proj``, ``ls1.gamma``, ``mlp.fc1`` ...) so that
 ``model_state_dict`` files are interchangeable (trainer.py:105-111, eval.py:29-30).
 
-Round 1: GEMMs / attention go through PyTorch-ROCm library kernels (hipBLASLt,
-SDPA) under bf16 autocast; the per-block CLS-row importance tap is computed
-from the block's own q/k (no duplicate QKV GEMM, no [B,H,T,T] map).  Parity of
-the ViT arithmetic itself is UNPINNED by the reference (it has no tests and
-timm is absent) -- see DESIGN.md.
+On the device the linear layers, attention (forward and backward, with the
+per-block CLS-row importance tap computed from the block's own q/k: no duplicate
+QKV GEMM, no [B,H,T,T] map) and LayerNorm run on the library's own gfx950 kernels
+(csrc/gemm_bf16.hip, attention*.hip, layernorm.hip) under bf16 autocast; a layer
+that has to take a PyTorch-ROCm library kernel instead is counted in
+``losses._ops.FALLBACKS`` (an error in strict mode).  Parity of the ViT
+arithmetic itself is UNPINNED by the reference (it has no tests and timm is
+absent) -- see DESIGN.md.
 """
 from __future__ import annotations
 

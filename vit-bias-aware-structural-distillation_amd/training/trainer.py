@@ -657,8 +657,15 @@ class Trainer:
         total_loss = torch.tensor(0.0, device=self.device)
         correct = torch.tensor(0, device=self.device, dtype=torch.long)
         total = 0
+        # a loader built with device_views ships uint8 images + augmentation parameters: both views are built here, on
+        # the device, right behind the copy (data/device_views.py); every other loader yields the views themselves
+        views = getattr(train_loader, "device_views", None)
+
         def on_device(b):
-            return None if b is None else {k: v.to(self.device, non_blocking=True) for k, v in b.items()}
+            if b is None:
+                return None
+            b = {k: v.to(self.device, non_blocking=True) for k, v in b.items()}
+            return b if views is None else views(b)
 
         it = iter(train_loader)
         upcoming = on_device(next(it, None))
