@@ -1,8 +1,12 @@
 """basd_procrustes_bwd (fused bf16 three-product split + residual epilogue) against the library fp32 bmm + the row
 kernels.  Default: the c2 shapes (1024 x [196, 196] x [196, 768]); --n / --batch (with --d-s / --d-t) time one other
 shape, e.g. the 384 px ones (--batch 256 --n 576, --n 729: the row-tiled kernel).  Each figure is the median of --runs
-device-event brackets of --iters calls, the two paths alternated in one process."""
-import argparse, os, statistics, sys, torch
+device-event brackets of --iters calls, the two paths alternated in one process.
+
+--side times basd_procrustes_bwd_side alone (one side of the backward: fac [n, n] x W [n, d], fp32 output) at
+--batch / --n / --d and prints the median of the brackets; BASD_LIB=<another build of the library> times that build, so
+two builds are compared by alternating runs of this script on one machine."""
+import argparse, ctypes, os, statistics, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import basd_amd._native as nat
 
@@ -11,6 +15,8 @@ ap.add_argument("--n", type=int, default=None, help="tokens (rows of a matrix); 
 ap.add_argument("--batch", type=int, default=256)
 ap.add_argument("--d-s", type=int, default=192)
 ap.add_argument("--d-t", type=int, default=768)
+ap.add_argument("--side", action="store_true", help="time basd_procrustes_bwd_side alone at --batch / --n / --d")
+ap.add_argument("--d", type=int, default=768, help="columns of W for --side")
 ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--runs", type=int, default=3)
 args = ap.parse_args()
@@ -26,6 +32,30 @@ def bracket(f, it):
     e1.synchronize()
     return e0.elapsed_time(e1) / it
 
+
+if args.side:
+    batch, n, d = args.batch, args.n or 196, args.d
+    g = torch.Generator().manual_seed(0)
+    w = torch.randn(batch, n, d, generator=g).cuda()
+    a = torch.rand(batch, n, generator=g).cuda() + 0.1; a = (a / a.sum(-1, keepdim=True)).contiguous()
+    gl = torch.randn(batch, generator=g).cuda()
+    fac = (torch.randn(batch, n, n, generator=g) / n ** 0.5).cuda()
+    out, rowdot = torch.empty_like(w), torch.empty_like(a)
+    p = ctypes.c_void_p
+
+    def side():
+        nat._check(nat.lib().basd_procrustes_bwd_side(p(fac.data_ptr()), p(w.data_ptr()), p(a.data_ptr()), p(gl.data_ptr()),
+                                                      batch, n, d, p(out.data_ptr()), nat.DTYPE_F32, p(rowdot.data_ptr()),
+                                                      nat._stream()), "basd_procrustes_bwd_side")
+
+    for _ in range(3):
+        side()
+    torch.cuda.synchronize()
+    ts = [bracket(side, args.iters) for _ in range(args.runs)]
+    gb = (2 * batch * n * d + batch * n * n) * 4 / 1e9       # W read + gradient written + factor read, once each
+    print(f"side batch {batch} n {n} d {d} ({nat.LIB_PATH}): median {statistics.median(ts):.4f} ms "
+          f"({'/'.join(f'{x:.4f}' for x in ts)}), {gb / statistics.median(ts):.2f} TB/s of {gb:.2f} GB algorithmic", flush=True)
+    sys.exit(0)
 
 shapes = [(1024, 196, 192, 768), (512, 196, 384, 1024)] if args.n is None else [(args.batch, args.n, args.d_s, args.d_t)]
 for (batch, n, d_s, d_t) in shapes:

@@ -28,8 +28,9 @@
 // dropped: 8 waves x 2 strips (104 accumulator registers: 85 - 300 spilled VGPRs whatever the fencing), the residual in
 // the accumulator layout (4-byte loads / stores + 16-lane reductions: 0.8 of 1.2 ms), fragment reads in two batches
 // (no change), the whole B strip of a group loaded in one burst into 56 registers (the right idea for the measured
-// bottleneck, but 259 spilled registers at the 168-register budget of three waves per SIMD: 1.78 ms).  Next: a
-// 4-wave / 256-register layout that holds the B strip, or the strip staged through LDS with transposing reads.
+// bottleneck, but 259 spilled registers at the 168-register budget of three waves per SIMD: 1.78 ms).
+// From five m tiles on (n > 64) these kernels are replaced by procrustes_bwd_side_resident_kernel below (0.94 -> 0.52 ms
+// at the shape above); they remain for n <= 64 and for up to 128 rows with fewer than 112 columns.
 #include "basd_common.h"
 
 namespace basd {
@@ -516,10 +517,364 @@ __global__ __launch_bounds__(256) void procrustes_ga_kernel(const float* __restr
   if (i < total) g_a[i] = (dot_s[i] + dot_t[i]) / (2.0f * a[i]);
 }
 
+// ---- the resident form: 5 <= ceil(n / 16) <= 16 m tiles ------------------------------------------------------------
+// The staged kernel above re-reads, re-splits and re-stores the [n, n] factor once per 96-column group (8 times at
+// d = 768) and puts two __syncthreads() -- each of which also drains the wave's outstanding global loads -- into every
+// K step, so every step exposes one memory round trip.  Here the factor is loaded, masked and split ONCE per workgroup
+// and its (hi, mid) planes stay in LDS for all column groups; what moves in the loop is W alone.
+// * A workgroup owns a ROW TILE of one matrix, MT <= 8 m tiles (the accumulator budget of the row-tiled kernel below),
+//   and runs over all d columns: its row dots are complete inside the workgroup (no atomics).  Tiles per matrix: the
+//   fewest that fit the 160 KiB of LDS -- one up to 128 rows, two up to 224 (196 rows: 7 + 6 m tiles), three above.
+//   A short tile runs the MFMAs of MT m tiles on rows zeroed in LDS (1 / 14 of the matrix work at 196 rows).
+// * Resident planes: row-major, [2 planes][16 MT rows][pbr_apitch(ksteps)] bytes: 64 bytes per K step and 16 or 48
+//   bytes of padding -- the pitch for which the 16-lane groups of the 16-byte fragment reads meet fewest banks twice.
+// * Grid: the tiles of matrix b sit 8 blocks apart (block = 8 T (b / 8) + 8 t + b % 8).  Workgroups go to the 8 XCDs
+//   round-robin, so the tiles of a matrix, which read the same W, run at the same time on the same L2.  This is the
+//   mapping that was measured; adjacent tiles (block = T b + t) land on different L2s and were not timed.
+// * 8 waves (two per SIMD, 256 registers each), one 16-column strip each: 128-column groups.  The (group, K step)
+//   pairs form ONE flat sequence of steps.  The W tile of a step ([32 k rows][128 columns] fp32: two 16-byte loads
+//   per thread) is loaded PBR_PF = 4 steps ahead into registers -- across group boundaries, so the epilogue of a group
+//   runs with the next group's tiles in flight --, split and stored into the other of two LDS buffers one step ahead.
+//   One barrier per step, and it orders LDS traffic only (lds_barrier): global loads stay in flight across it.
+// * Same arithmetic as the kernels above: per accumulator tile K ascends in steps of 32, three MFMAs per step in the
+//   order hi hi, hi mid, mid hi; the epilogue (fp32 W re-read, residual, scale, fmaf row dot over the 4-column chunk,
+//   quad reduction) is the same code, so `out` has the same bits.  Row dots: strip s is added to slot s % 6 in LDS, strips
+//   ascending, and the six slots are added in order -- the order of the kernels above, whose wave s % 6 owns strip s; so
+//   `rowdot` has the same bits too, and the step computes what it computed.  No atomics (see `pend` in the kernel).
+// * Bounds: rows >= n and the rows of the other tiles are clamped to row n - 1 on the load and zeroed by a select, the
+//   K tail likewise (every load is clamped to the last 16 bytes of the matrix's own factor); W rows >= n and columns
+//   >= d of a ragged last group read element 0 of the matrix and are zeroed; nothing is stored outside [n, d].
+// Rejected: (b) hi plane resident, mid plane streamed -- it keeps a whole matrix per workgroup (13 accumulator tiles,
+// 168-register budget gone) but puts half of the factor's traffic and its split back into every column group; not built
+// once (a) fitted with no scratch.  Two strips per wave (4 waves): halves the fragment reads per MFMA, one wave per
+// SIMD; not built: LDS reads (0.07 ms per launch by the rates of the LDS table) are not what bounds this kernel.
+constexpr int PBR_WAVES = 8;
+constexpr int PBR_THREADS = 64 * PBR_WAVES;
+constexpr int PBR_COLS = 16 * PBR_WAVES;     // columns of a group
+constexpr int PBR_BPITCH = 304;              // bytes between the k rows of a staged W plane (128 bf16 = 256 + 48 pad)
+constexpr int PBR_PF = 4;                    // W tiles in flight (steps between a tile's global load and its LDS store)
+
+__host__ __device__ inline int pbr_apitch(int ksteps) { return ksteps * 64 + ((ksteps & 3) == 3 ? 48 : 16); }
+
+template <int MT, typename TO>      // MT = m tiles of the longest row tile
+__global__ __launch_bounds__(PBR_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void procrustes_bwd_side_resident_kernel(
+    const float* __restrict__ fac, const float* __restrict__ w, const float* __restrict__ a,
+    const float* __restrict__ gl, int batch, int n, int d, int tiles, TO* __restrict__ out, float* __restrict__ rowdot) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int per = 8 * tiles;
+  const int grp = (int)blockIdx.x / per, rem = (int)blockIdx.x - grp * per;
+  const int b = grp * 8 + (rem & 7), t = rem >> 3;
+  if (b >= batch) return;                                  // the grid is padded to whole groups of 8 matrices
+  const int mt = (n + 15) >> 4;
+  const int base = mt / tiles, extra = mt - base * tiles;  // the first `extra` tiles hold base + 1 m tiles (= MT)
+  const int trows = 16 * (base + (t < extra ? 1 : 0));     // rows of this tile (the last one of the matrix: padded)
+  const int r0 = 16 * (t * base + (t < extra ? t : extra));
+  const int ksteps = (n + 31) >> 5;
+  const int AP = pbr_apitch(ksteps);
+  const int APLANE = MT * 16 * AP;
+  constexpr int BPLANE = 32 * PBR_BPITCH;
+  unsigned char* abuf = smem;                              // [2 planes][MT * 16 rows][AP]: the resident factor slice
+  unsigned char* bbuf = smem + 2 * APLANE;                 // [2 buffers][2 planes][32 k rows][PBR_BPITCH]: W tiles
+  float* s_park = reinterpret_cast<float*>(bbuf + 4 * BPLANE);   // [waves][16 rows][16 columns] epilogue tiles
+  float* s_c = s_park + PBR_WAVES * 256;                   // [MT * 16] row scales 2 gl sqrt(a)
+  float* s_slot = s_c + MT * 16;                           // [PB_WAVES slots][MT * 16] row dots, see the epilogue
+  const float* A = fac + (size_t)b * n * n;
+  const float* W = w + (size_t)b * n * d;
+  TO* O = out + (size_t)b * n * d;
+  const int strips = d >> 4;
+  const int total = ((d + PBR_COLS - 1) / PBR_COLS) * ksteps;    // steps = (column group, K step), group-major
+  const float c2 = 2.f * gl[b];
+
+  // the W tile of a step: global -> registers (16-byte loads, 512 contiguous bytes per k row) -> (hi, mid) planes
+  // The loads are unconditional and only clamp their address (W rows >= n and the columns >= d of a ragged last group
+  // read element 0 of the matrix); what was clamped is zeroed by a select when the tile is stored.  A select or a
+  // branch right behind the load would make the wave wait for it there.
+  float4 wr[PBR_PF][2];
+  auto wload = [&](float4 (&r)[2], int g, int ks) {
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      const int item = tid + PBR_THREADS * it;             // 1024 items = 32 rows x 32 quads
+      const int kr = ks * 32 + (item >> 5), cc = g * PBR_COLS + 4 * (item & 31);
+      const bool ok = kr < n && cc < d;
+      r[it] = *reinterpret_cast<const float4*>(W + (size_t)(ok ? kr : 0) * d + (ok ? cc : 0));
+    }
+  };
+  auto wstore = [&](const float4 (&r)[2], int buf, int g, int ks) {
+    unsigned char* dst = bbuf + (size_t)buf * 2 * BPLANE;
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      const int item = tid + PBR_THREADS * it;
+      const int kr = ks * 32 + (item >> 5), cc = g * PBR_COLS + 4 * (item & 31);
+      const bool ok = kr < n && cc < d;
+      const float4 v = ok ? r[it] : make_float4(0.f, 0.f, 0.f, 0.f);
+      uint2 hi, mid;
+      pb_split2(v.x, v.y, hi.x, mid.x); pb_split2(v.z, v.w, hi.y, mid.y);
+      const unsigned lo = (unsigned)(item >> 5) * PBR_BPITCH + (unsigned)(item & 31) * 8;
+      *reinterpret_cast<uint2*>(dst + lo) = hi;
+      *reinterpret_cast<uint2*>(dst + BPLANE + lo) = mid;
+    }
+  };
+  // The step sequence is padded to a multiple of PF with steps that repeat the last tile: no branch around a load or
+  // a barrier in the loop.  A padding step's products land in accumulators whose epilogue, if it comes at all (fewer
+  // K steps than PF), belongs to a column group past d and stores nothing.
+  const int padded = (total + PBR_PF - 1) / PBR_PF * PBR_PF;
+  int lt = 0, lg = 0, lks = 0;                             // the next step to load, as index and as (group, K step)
+  auto wnext = [&](float4 (&r)[2]) {
+    wload(r, lg, lks);
+    if (++lt < total && ++lks == ksteps) { lks = 0; ++lg; }
+  };
+#pragma unroll
+  for (int u = 0; u < PBR_PF; ++u) wnext(wr[u]);           // steps 0 .. PF - 1 are in flight under the factor's staging
+
+  for (int i = tid; i < MT * 16; i += PBR_THREADS) {
+    s_c[i] = (i < trows && r0 + i < n) ? c2 * __builtin_amdgcn_sqrtf(a[(size_t)b * n + r0 + i]) : 0.f;
+#pragma unroll
+    for (int j = 0; j < PB_WAVES; ++j) s_slot[j * MT * 16 + i] = 0.f;
+  }
+
+  // ---- the factor slice, once: item = (row of the tile, k octet of 32 slots), two 16-byte loads each, four items in
+  // flight per thread.  n % 4 == 0: a 16-byte load is inside the row or beyond it as a whole.
+  {
+    const int octs = ksteps * 4;
+    const unsigned a_last = (unsigned)n * (unsigned)n - 4u;
+    for (int it0 = 0; it0 < MT * 16 * 32; it0 += 4 * PBR_THREADS) {
+      float4 v[4][2];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int item = it0 + j * PBR_THREADS + tid;
+        const int rg = r0 + (item >> 5);
+        const unsigned o0 = (unsigned)(rg < n ? rg : n - 1) * (unsigned)n + (unsigned)((item & 31) * 8), o1 = o0 + 4u;
+        v[j][0] = *reinterpret_cast<const float4*>(A + (o0 < a_last ? o0 : a_last));
+        v[j][1] = *reinterpret_cast<const float4*>(A + (o1 < a_last ? o1 : a_last));
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int item = it0 + j * PBR_THREADS + tid;
+        const int row = item >> 5, oct = item & 31;
+        if (row < MT * 16 && oct < octs) {
+          const bool rok = row < trows && r0 + row < n;
+          const bool k0 = rok && oct * 8 + 4 <= n, k1 = rok && oct * 8 + 8 <= n;
+          const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+          const float4 v0 = k0 ? v[j][0] : z, v1 = k1 ? v[j][1] : z;
+          uint4 hi, mid;
+          pb_split2(v0.x, v0.y, hi.x, mid.x); pb_split2(v0.z, v0.w, hi.y, mid.y);
+          pb_split2(v1.x, v1.y, hi.z, mid.z); pb_split2(v1.z, v1.w, hi.w, mid.w);
+          const unsigned lo = (unsigned)row * (unsigned)AP + (unsigned)oct * 16;
+          *reinterpret_cast<uint4*>(abuf + lo) = hi;
+          *reinterpret_cast<uint4*>(abuf + APLANE + lo) = mid;
+        }
+      }
+    }
+  }
+  wstore(wr[0], 0, 0, 0);                                  // step 0; visible after the barrier of step 0
+  wnext(wr[0]);                                            // step PF
+
+  pb_f32x4 acc[MT];
+  const int col = lane & 15, g4 = lane >> 4;
+  const int prow = lane >> 2, pch = lane & 3;              // epilogue's row-wise walk: 16 rows x 4 chunks of 4 columns
+  // Row dots in the order of the staged kernel, whose wave s % 6 adds strip s to its own slice, strips ascending, and
+  // whose slices are added in wave order: strip s goes to slot s % 6 here as well.  The strips of waves 0 .. 5 of a
+  // group fall into six different slots; those of waves 6 and 7 share a slot with waves 0 and 1 and come after them,
+  // so these two waves keep their dots (pend) and add them behind the next barrier.  At least two barriers separate
+  // the epilogues of two groups (ksteps >= 3 from 65 rows on), so every slot is added to in strip order.
+  float pend[MT];
+  int pend_slot = -1;                                      // wave-uniform: >= 0 while dots are waiting
+#pragma unroll
+  for (int i = 0; i < MT; ++i) { acc[i] = (pb_f32x4){0.f, 0.f, 0.f, 0.f}; pend[i] = 0.f; }
+  auto flush = [&]() {
+    if (pend_slot >= 0) {
+      if (pch == 0) {
+#pragma unroll
+        for (int i = 0; i < MT; ++i) s_slot[pend_slot * MT * 16 + i * 16 + prow] += c2 * pend[i];
+      }
+      pend_slot = -1;
+    }
+  };
+  float* park = s_park + wave * 256;
+  int ks = 0, g = 0;
+  for (int t0 = 0; t0 < padded; t0 += PBR_PF) {
+#pragma unroll
+    for (int u = 0; u < PBR_PF; ++u) {                     // unrolled: step t lives in the register set t % PF
+      {
+        const int buf = (t0 + u) & 1;
+        lds_barrier();                                     // this step's tile is complete, buffer buf ^ 1 has been read
+        flush();
+        {
+          const bool wrap = ks + 1 == ksteps;
+          wstore(wr[(u + 1) % PBR_PF], buf ^ 1, wrap ? g + 1 : g, wrap ? 0 : ks + 1);   // the next step, loaded PF steps ago
+          wnext(wr[(u + 1) % PBR_PF]);                     // the step PF after it
+        }
+        pb_bf16x8 bh, bm;
+        {
+          const int qq = col >> 2, pp = col & 3;
+          const unsigned char* b0 = bbuf + (size_t)buf * 2 * BPLANE + (size_t)(g4 * 8 + qq) * PBR_BPITCH +
+                                    (size_t)(wave * 16 + 4 * pp) * 2;
+          const pb_v4s h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pb_lds_v4s*)b0);
+          const pb_v4s h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pb_lds_v4s*)(b0 + 4 * PBR_BPITCH));
+          const pb_v4s m0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pb_lds_v4s*)(b0 + BPLANE));
+          const pb_v4s m1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pb_lds_v4s*)(b0 + BPLANE + 4 * PBR_BPITCH));
+          bh = (pb_bf16x8){h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+          bm = (pb_bf16x8){m0[0], m0[1], m0[2], m0[3], m1[0], m1[1], m1[2], m1[3]};
+        }
+        // A fragments of K step ks out of the resident planes, in two batches (registers), as in the kernels above
+        const unsigned char* ap = abuf + (size_t)col * AP + (size_t)ks * 64 + g4 * 16;
+        constexpr int HB = (MT + 1) / 2;
+#pragma unroll
+        for (int hb = 0; hb < 2; ++hb) {
+          pb_bf16x8 fh[HB], fm[HB];
+#pragma unroll
+          for (int j = 0; j < HB; ++j) {
+            const int i = hb * HB + j < MT ? hb * HB + j : MT - 1;
+            fh[j] = *reinterpret_cast<const pb_bf16x8*>(ap + (size_t)i * 16 * AP);
+            fm[j] = *reinterpret_cast<const pb_bf16x8*>(ap + APLANE + (size_t)i * 16 * AP);
+          }
+#pragma unroll
+          for (int j = 0; j < HB; ++j) {
+            const int i = hb * HB + j;
+            if (i < MT) {
+              acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[j], bh, acc[i], 0, 0, 0);
+              acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[j], bm, acc[i], 0, 0, 0);
+              acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fm[j], bh, acc[i], 0, 0, 0);
+            }
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        if (++ks == ksteps) {
+          // ---- epilogue of group g, the code of the kernels above: acc[i][r] = P at row r0 + 16 i + 4 (lane >> 4) + r,
+          // column 16 s0 + (lane & 15); the wave parks one tile at a time in its own 1 KiB and reads it back row-wise
+          const int s0 = g * PBR_WAVES + wave;
+          const bool has = s0 < strips;
+          const int pcol = s0 * 16 + pch * 4;
+          const int slot = s0 % PB_WAVES;
+          const bool later = has && wave >= PB_WAVES;      // wave-uniform
+          if (later) pend_slot = slot;
+          constexpr int H0 = (MT + 1) / 2;                 // tiles per batch: the W loads of a batch are in flight together
+#pragma unroll
+          for (int hb = 0; hb < 2; ++hb) {
+            float4 wq[H0];
+#pragma unroll
+            for (int j = 0; j < H0; ++j) {
+              const int lrow = (hb * H0 + j) * 16 + prow, row = r0 + lrow;
+              const bool ok = has && lrow < trows && row < n;
+              wq[j] = *reinterpret_cast<const float4*>(W + (unsigned)(ok ? row : 0) * (unsigned)d + (unsigned)(ok ? pcol : 0));
+            }
+#pragma unroll
+            for (int j = 0; j < H0; ++j) {
+              const int i = hb * H0 + j;
+              if (i < MT) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) park[(g4 * 4 + r) * 16 + col] = acc[i][r];
+                // wave-private tile: the wave's own LDS writes precede its reads (in order), no barrier
+                const float4 pv = *reinterpret_cast<const float4*>(park + prow * 16 + pch * 4);
+                const int lrow = i * 16 + prow, row = r0 + lrow;
+                const bool ok = has && lrow < trows && row < n;      // rows of other tiles and rows >= n: never stored
+                const unsigned off = (unsigned)(ok ? row : 0) * (unsigned)d + (unsigned)(ok ? pcol : 0);
+                const float4 wv = wq[j];
+                const float cr = s_c[lrow];
+                const float4 rv = make_float4(wv.x - pv.x, wv.y - pv.y, wv.z - pv.z, wv.w - pv.w);
+                float dot = ok ? fmaf(rv.x, wv.x, fmaf(rv.y, wv.y, fmaf(rv.z, wv.z, rv.w * wv.w))) : 0.f;
+                if (ok) {
+                  if constexpr (sizeof(TO) == 4) {
+                    *reinterpret_cast<float4*>(O + off) = make_float4(cr * rv.x, cr * rv.y, cr * rv.z, cr * rv.w);
+                  } else {
+                    uint2 o;
+                    o.x = (unsigned)__builtin_bit_cast(unsigned short, (__bf16)(cr * rv.x)) |
+                          ((unsigned)__builtin_bit_cast(unsigned short, (__bf16)(cr * rv.y)) << 16);
+                    o.y = (unsigned)__builtin_bit_cast(unsigned short, (__bf16)(cr * rv.z)) |
+                          ((unsigned)__builtin_bit_cast(unsigned short, (__bf16)(cr * rv.w)) << 16);
+                    *reinterpret_cast<uint2*>(O + off) = o;
+                  }
+                }
+                dot += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(dot), 0xB1, 0xF, 0xF, true));     // quad_perm 1,0,3,2
+                dot += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(dot), 0x4E, 0xF, 0xF, true));     // quad_perm 2,3,0,1
+                if (later) pend[i] = dot;
+                else if (has && pch == 0) s_slot[slot * MT * 16 + lrow] += c2 * dot;
+                acc[i] = (pb_f32x4){0.f, 0.f, 0.f, 0.f};
+              }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+          }
+          ks = 0;
+          ++g;
+        }
+      }
+    }
+  }
+  // row dots: the slots are added in slot order, as the staged kernel adds its waves' slices
+  lds_barrier();
+  flush();
+  lds_barrier();
+  for (int i = tid; i < trows; i += PBR_THREADS) {
+    if (r0 + i < n) {
+      float s = 0.f;
+#pragma unroll
+      for (int j = 0; j < PB_WAVES; ++j) s += s_slot[j * MT * 16 + i];
+      rowdot[(size_t)b * n + r0 + i] = s;
+    }
+  }
+}
+
+// Compiler's resource report (hipcc --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage; fp32 and bf16 output
+// alike but for MT = 7; LDS is dynamic: 2 x 16 MT x pitch factor planes + 38912 W tiles + 8192 parked tiles + 64 MT row
+// scales + 384 MT row-dot slots):
+//   MT = 5   VGPRs 124        AGPRs 0  scratch 0 bytes/lane  occupancy 2 waves/SIMD
+//   MT = 6   VGPRs 134        AGPRs 0  scratch 0 bytes/lane  occupancy 2 waves/SIMD
+//   MT = 7   VGPRs 140 / 138  AGPRs 0  scratch 0 bytes/lane  occupancy 2 waves/SIMD   (196 rows: 161344 bytes of LDS)
+//   MT = 8   VGPRs 148        AGPRs 0  scratch 0 bytes/lane  occupancy 2 waves/SIMD
+// Measured on one MI355X against the staged kernel of the parent commit, both libraries loaded into one process, the
+// same inputs, alternated medians of 4 brackets of 10 launches (ms; the parent's own brackets differ by 0.005 - 0.026,
+// 0.061 at 128 rows):
+//   batch x n x d       staged   resident
+//   1024 x 196 x  768   0.936    0.516      (c2, teacher side; 1.85 GB algorithmic: 3.6 TB/s)
+//    512 x 196 x 1024   0.650    0.326      (c4)
+//   1024 x 196 x 1280   1.613    0.832      (c5)
+//   1024 x 196 x  192   0.257    0.216
+//   1024 x  80 x  768   0.255    0.151      (5 m tiles: the dispatch boundary)
+//   1024 x 128 x  768   0.354    0.226      (one row tile of 8)
+//   1024 x 256 x  768   1.316    0.757      (three row tiles)
+//      2 x 100 x  112   0.0153   0.0100
+//    300 x  80 x   16   0.0141   0.0161     (slower: stays on the staged kernel, see launch_side)
+// (With the row dots kept per wave in registers and added in 8-wave order the c2 shape took 0.493 ms in another session;
+// that order changes `rowdot` by 6.6e-8 rel-L2 and with it every later step of a training run.)  `out` and `rowdot` have
+// the bits of the staged kernel at these and six smaller shapes, fp32 and bf16.  Up to four m tiles (c1: 64 tokens)
+// were not timed and stay on the kernels above.
+template <typename TO>
+static int launch_side_resident(const float* fac, const float* w, const float* a, const float* gl, int batch, int n,
+                                int d, TO* out, float* rowdot, hipStream_t st) {
+  const int mt = (n + 15) / 16, ksteps = (n + 31) / 32;
+  int tiles = (mt + 7) / 8, m = 0;
+  size_t lds = 0;
+  for (;; ++tiles) {                                       // the fewest row tiles whose resident planes fit
+    m = (mt + tiles - 1) / tiles;
+    lds = (size_t)2 * m * 16 * pbr_apitch(ksteps) + (size_t)4 * 32 * PBR_BPITCH + (size_t)PBR_WAVES * 1024 + (size_t)m * 64 * (1 + PB_WAVES);
+    if (lds <= 160 * 1024) break;
+  }
+  const dim3 grid((unsigned)((batch + 7) / 8) * 8u * (unsigned)tiles);
+#define BASD_PB_RESIDENT(MT)                                                                                 \
+  do {                                                                                                       \
+    allow_full_lds((const void*)procrustes_bwd_side_resident_kernel<MT, TO>);                                \
+    hipLaunchKernelGGL((procrustes_bwd_side_resident_kernel<MT, TO>), grid, dim3(PBR_THREADS), lds, st, fac, w, a, gl,  \
+                       batch, n, d, tiles, out, rowdot);                                                     \
+  } while (0)
+  switch (m) {
+    case 5: BASD_PB_RESIDENT(5); break;
+    case 6: BASD_PB_RESIDENT(6); break;
+    case 7: BASD_PB_RESIDENT(7); break;
+    case 8: BASD_PB_RESIDENT(8); break;
+    default: return fail(BASD_ERR_SHAPE, "procrustes_bwd_side: no resident kernel for %d m tiles in %d row tiles", mt, tiles);
+  }
+#undef BASD_PB_RESIDENT
+  return check_launch("procrustes_bwd (resident residual product)");
+}
+
 template <typename TO>
 static int launch_side(const float* fac, const float* w, const float* a, const float* gl, int batch, int n, int d,
                        TO* out, float* rowdot, hipStream_t st) {
   const int mt = (n + 15) / 16;
+  // resident factor where it was measured faster: from five m tiles on, a single row tile (mt <= 8) only with at least
+  // 112 columns (300 x 80 x 16: 16.1 against 14.1 us -- one strip for eight waves, and the whole factor is staged first)
+  if (mt >= 9 || (mt >= 5 && d >= 112)) return launch_side_resident<TO>(fac, w, a, gl, batch, n, d, out, rowdot, st);
   // fewer than four rows of tiles: W straight from global memory; from four on W goes through LDS, where the parked
   // epilogue tiles (6 KiB) alias the A buffer
 #define BASD_PB_DIRECT(MT)                                                                                   \
