@@ -71,8 +71,10 @@
  *   basd_resample_u8, basd_ta_normalize_u8
  *                          the torchvision v2 transforms of both training views (src/data/datasets.py:80-94 clean /
  *                          evaluation view, :137-149 augmented view), which the reference runs in its loader workers
+ *   basd_cls_tally         src/evaluation/metrics.py:19-55: outputs[:, valid_indices], MulticlassAccuracy(top_k = 1 | 5)
+ *                          and criterion(outputs, labels) of one evaluation batch, accumulated on the device
  *
- * 63 entries in all (basd_version and basd_last_error included).
+ * 64 entries in all (basd_version and basd_last_error included).
  */
 #ifndef BASD_HIP_H
 #define BASD_HIP_H
@@ -602,6 +604,29 @@ int basd_resample_u8(const void* src, const int* rec, int B, int H, int W, int S
  * 3 <= S <= 1024. */
 int basd_ta_normalize_u8(const void* img, const int* ops, const double* mags, int B, int S, float mean0, float mean1,
                          float mean2, float std0, float std1, float std2, float* out, void* stream);
+
+/* Evaluation tally of one batch (reference src/evaluation/metrics.py:19-55): logits [B, C] fp32 (logits_bf16 == 0) or
+ * bf16 (!= 0), rows row_stride >= C ELEMENTS apart; keep: K distinct column indices in [0, C), any order (the class
+ * subset outputs[:, valid_indices]), or NULL with K == C for the identity; labels [B] index the SUBSET, so the target
+ * column is keep[labels[b]].  Per row, with z_j = logits[b, keep[j]], y = labels[b] and s = smoothing (taken as the
+ * float it is passed as), all in fp64 on the values as stored:
+ *   rank = #{j : z_j > z_y} + #{j < y : z_j == z_y}   -- a tie goes to the lowest subset position (argmax's rule); NaN
+ *                                                        orders above every number and equal to NaN (topk's rule);
+ *   loss = lse(z) - (1 - s) z_y - (s / K) sum_j z_j   -- nn.CrossEntropyLoss(label_smoothing = s, reduction = "none");
+ *                                                        the last term only when s != 0, so a -inf logit away from
+ *                                                        the target is legal at s = 0 and adds 0 to lse;
+ *   lse(z) = m + log(sum_j exp(z_j - m)), m = the largest non-NaN z_j, or 0 where that is infinite.
+ * A label outside [0, K) reads nothing and gives rank = K (a miss at every k) and loss = NaN; a keep entry outside
+ * [0, C) reads nothing and counts as a NaN logit.
+ * Outputs: row_rank [B] int32 and row_loss [B] fp64 (both required: they are the staging area), and tally [4] fp64,
+ * ADDED TO in place: {#(rank == 0), #(rank < top_k), sum_b loss, B}.  1 <= top_k <= K.  Two launches: one workgroup per
+ * row, then one workgroup that sums the rows in a fixed order; no floating-point atomics, so the tally is bitwise
+ * reproducible.  B == 0 is BASD_OK with nothing enqueued and tally untouched.  BASD_ERR_SHAPE (nothing enqueued): top_k
+ * outside 1 .. K, keep NULL with K != C, row_stride < C, a non-positive C or K, a missing pointer.  No allocation: legal
+ * inside a stream capture. */
+int basd_cls_tally(const void* logits, int logits_bf16, int64_t row_stride, const int64_t* labels,
+                   const int64_t* keep, int B, int C, int K, int top_k, float smoothing, int* row_rank,
+                   double* row_loss, double* tally, void* stream);
 
 #ifdef __cplusplus
 }

@@ -34,7 +34,7 @@ EXPORTS = (
     "basd_selector_weights_workspace_bytes", "basd_selector_weights", "basd_attention_fwd_long_bf16",
     "basd_attention_bwd_long_workspace_bytes", "basd_attention_bwd_long_bf16", "basd_attention_fwd_f32x3_long",
     "basd_dwconv7_ln_bf16", "basd_grn_workspace_bytes", "basd_grn_bf16", "basd_patchify_bf16",
-    "basd_resample_u8", "basd_ta_normalize_u8",
+    "basd_resample_u8", "basd_ta_normalize_u8", "basd_cls_tally",
 )
 
 
@@ -104,6 +104,7 @@ _SIGNATURES = {
     "basd_patchify_bf16": (_P, _I, _I, _I, _I, _I64, _I64, _I64, _I64, _I, _I, _P, _P),
     "basd_resample_u8": (_P, _P, _I, _I, _I, _I, _P, _P),
     "basd_ta_normalize_u8": (_P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P),
+    "basd_cls_tally": (_P, _I, _I64, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P),
 }
 
 
@@ -1333,3 +1334,36 @@ def ta_normalize_u8(images: torch.Tensor, ops: torch.Tensor | None, mags: torch.
     _check(lib().basd_ta_normalize_u8(_ptr(images), _ptr(ops), _ptr(mags), b, s, f(mean[0]), f(mean[1]), f(mean[2]),
                                       f(std[0]), f(std[1]), f(std[2]), _ptr(out), _stream()), "basd_ta_normalize_u8")
     return out
+
+
+# --------------------------------------------------------------------------- evaluation tally (csrc/eval_tally.hip)
+def cls_tally_supported(logits: torch.Tensor) -> bool:
+    """logits basd_cls_tally reads in place: [B, C] fp32 / bf16 on the device, unit column stride, rows at least C
+    elements apart (any padding behind a row is never read)"""
+    return (logits.is_cuda and logits.dim() == 2 and logits.dtype in (torch.float32, torch.bfloat16)
+            and logits.shape[1] >= 1 and (logits.shape[1] == 1 or logits.stride(1) == 1)
+            and (logits.shape[0] <= 1 or logits.stride(0) >= logits.shape[1]))
+
+
+def cls_tally(logits: torch.Tensor, labels: torch.Tensor, tally: torch.Tensor, *, keep: torch.Tensor | None = None,
+              top_k: int, smoothing: float = 0.0):
+    """logits [B, C] fp32 / bf16 (read in place, any row stride >= C), labels [B] integer indices into the subset,
+    keep: None | [K] int64 distinct columns, tally [4] fp64 = {hits@1, hits@top_k, summed loss, rows}, ADDED TO in place
+    -> (row_rank [B] int32, row_loss [B] fp64); semantics in include/basd_hip.h.  No host sync."""
+    _need_cuda(logits, labels, tally, keep)
+    assert cls_tally_supported(logits), (tuple(logits.shape), logits.stride(), logits.dtype)
+    b, c = logits.shape
+    assert labels.shape == (b,) and not labels.dtype.is_floating_point, (tuple(labels.shape), labels.dtype)
+    assert tally.dtype == torch.float64 and tally.shape == (4,) and tally.is_contiguous()
+    labels = labels.to(torch.int64).contiguous()
+    k = c
+    if keep is not None:
+        assert keep.dtype == torch.int64 and keep.dim() == 1 and keep.is_contiguous(), (keep.dtype, tuple(keep.shape))
+        k = keep.shape[0]
+    row_rank = torch.empty(b, dtype=torch.int32, device=logits.device)
+    row_loss = torch.empty(b, dtype=torch.float64, device=logits.device)
+    stride = logits.stride(0) if b > 1 else c
+    _check(lib().basd_cls_tally(_ptr(logits), int(logits.dtype == torch.bfloat16), ctypes.c_int64(stride), _ptr(labels),
+                                _ptr(keep), b, c, k, int(top_k), ctypes.c_float(smoothing), _ptr(row_rank),
+                                _ptr(row_loss), _ptr(tally), _stream()), "basd_cls_tally")
+    return row_rank, row_loss

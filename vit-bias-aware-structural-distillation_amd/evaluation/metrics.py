@@ -8,7 +8,9 @@ Operator surface of reference ``src/evaluation/metrics.py`` (``evaluate_model`` 
 * the evaluation datasets come from the Hugging Face hub in the reference (network); ``run_eval_suite`` therefore takes
   the loaders from the caller: ``{dataset name: loader | (loader, valid_indices)}``, batches with the reference's eval
   contract ``{"pixel_values", "label"}`` (``src/data/datasets.py:97-123``);
-* everything runs on the model's own device (the reference hard-codes ``.cuda()``).
+* everything runs on the model's own device (the reference hard-codes ``.cuda()``);
+* with a plain ``nn.CrossEntropyLoss`` and device logits the per-batch accounting (class subset, top-1 / top-5 hits,
+  loss) is one C entry, ``basd_cls_tally``: fp64 on the logits as the model stored them, ties to the lowest class.
 """
 from __future__ import annotations
 
@@ -32,6 +34,17 @@ def _sync(device: torch.device) -> None:
         torch.cuda.synchronize(device)
 
 
+def _tally_ops(criterion: nn.Module):
+    """The kernel provider if ``criterion`` is nn.CrossEntropyLoss in its default form (the test of
+    ``BASDLoss._fused_ce``) and the provider has the fused tally; None: the torch accounting."""
+    from ..losses._ops import get_ops
+    if not (type(criterion) is nn.CrossEntropyLoss and criterion.weight is None and criterion.reduction == "mean"
+            and criterion.ignore_index < 0):
+        return None
+    ops = get_ops()
+    return ops if getattr(ops, "cls_tally", None) is not None else None
+
+
 @torch.no_grad()
 def evaluate_model(model: nn.Module, data_loader, criterion: nn.Module, *, num_classes: int,
                    valid_indices: list[int] | None = None) -> dict[str, Any]:
@@ -41,13 +54,22 @@ def evaluate_model(model: nn.Module, data_loader, criterion: nn.Module, *, num_c
     dev = _device_of(model)
     tally = torch.zeros(4, dtype=torch.float64, device=dev)        # hits@1, hits@5, summed loss, samples
     keep = None if valid_indices is None else torch.as_tensor(valid_indices, device=dev)
+    ops = _tally_ops(criterion)
+    keep64 = None if keep is None or ops is None else keep.long().contiguous()      # the kernel's index type
     views = getattr(data_loader, "device_views", None)      # raw uint8 batches: pixel_values are built on the device
     for batch in data_loader:
         if views is not None:
             batch = views({k: v.to(dev, non_blocking=True) for k, v in batch.items()})
         x = batch["pixel_values"].to(dev, non_blocking=True)
         y = batch["label"].to(dev, non_blocking=True)
-        logits = model(x).float()
+        logits = model(x)
+        top_k = min(5, num_classes, logits.shape[1] if keep is None else keep.numel())
+        if (ops is not None and top_k >= 1 and y.dim() == 1 and ops.handles(logits)
+                and ops.cls_tally_supported(logits)):
+            # subset, top-1 / top-5 hits and the loss in one pass over the logits as stored (fp32 or bf16)
+            ops.cls_tally(logits, y, tally, keep=keep64, top_k=top_k, smoothing=criterion.label_smoothing)
+            continue
+        logits = logits.float()
         if keep is not None:
             logits = logits.index_select(1, keep)
         top = logits.topk(min(5, num_classes, logits.shape[1]), dim=1).indices     # a class subset may have < 5 columns
