@@ -71,10 +71,13 @@
  *   basd_resample_u8, basd_ta_normalize_u8
  *                          the torchvision v2 transforms of both training views (src/data/datasets.py:80-94 clean /
  *                          evaluation view, :137-149 augmented view), which the reference runs in its loader workers
+ *   basd_resample_u8_packed
+ *                          the resize / crop / flip of those views for images of different sizes (directory splits),
+ *                          packed into one byte buffer
  *   basd_cls_tally         src/evaluation/metrics.py:19-55: outputs[:, valid_indices], MulticlassAccuracy(top_k = 1 | 5)
  *                          and criterion(outputs, labels) of one evaluation batch, accumulated on the device
  *
- * 64 entries in all (basd_version and basd_last_error included).
+ * 65 entries in all (basd_version and basd_last_error included).
  */
 #ifndef BASD_HIP_H
 #define BASD_HIP_H
@@ -592,6 +595,21 @@ int basd_patchify_bf16(const void* x, int B, int C, int H, int W, int64_t sb, in
  * Every index is clamped into the canvas and the resized image: a bad record cannot read out of bounds.
  * 3 <= S <= 1024, 1 <= H, W <= 16384. */
 int basd_resample_u8(const void* src, const int* rec, int B, int H, int W, int S, void* out, void* stream);
+
+/* basd_resample_u8 for samples of different sizes.  pixels: one flat uint8 device buffer of pixels_bytes bytes; sample b
+ * is a planar [3, h_b, w_b] image that starts at byte geom[b][0].  geom [B, 3] int64 on the device: {offset, h, w}.
+ * rec [B, 9] int32 as above, its canvas being the sample's own h_b x w_b.  out [B, 3, S, S] uint8, 4-byte aligned (odd S
+ * leaves a sample's first byte unaligned: byte head and tail, 32-bit words between).  Per output byte the arithmetic is
+ * that of basd_resample_u8 with (H, W) = (h_b, w_b): bit-equal to that entry run on the sample alone.
+ * One workgroup per (sample, band of 16 output rows), all three channels: the taps of the S columns and of the band's
+ * rows (window start, count, weight sum, the first 8 normalised weights) are built once per workgroup in LDS,
+ * 44 (S + 16) bytes; wider filters recompute the weights past the eighth.
+ * A sample is read only if offset >= 0, 1 <= h, w <= 16384 and offset + 3 h w <= pixels_bytes (64-bit arithmetic);
+ * otherwise nothing of it is read and its output is all zeros.  Record fields are clamped as in basd_resample_u8.
+ * Allocates nothing and does not synchronise.  3 <= S <= 1024; B < 0, a null pointer or a negative pixels_bytes is
+ * BASD_ERR_SHAPE. */
+int basd_resample_u8_packed(const void* pixels, int64_t pixels_bytes, const int64_t* geom, const int* rec, int B, int S,
+                            void* out, void* stream);
 
 /* One TrivialAugmentWide operation per image, then ToDtype(float32, scale=True) and Normalize: img [B, 3, S, S] uint8,
  * ops [B] int32 (index into TA_WIDE_OPS: Identity, ShearX, ShearY, TranslateX, TranslateY, Rotate, Brightness, Color,

@@ -8,7 +8,14 @@
 
     python scripts/time_input_pipeline.py [--batch 256] [--iters 30] [--cpu-samples 64] [--skip-cpu]
 
-One JSON line per configuration (32 px from 32 x 32 sources, 224 px from 256 x 256 sources)."""
+One JSON line per configuration (32 px from 32 x 32 sources, 224 px from 256 x 256 sources).
+
+    python scripts/time_input_pipeline.py --packed [--batch 256] [--iters 30] [--rounds 5]
+
+basd_resample_u8_packed instead: (1) the uniform 256 x 256 -> 224 batch in packed form against basd_resample_u8 on the
+same records, both views, the two entries timed alternately in one process (``rounds`` medians each, and the spread of
+the old entry's medians); (2) one synthetic ImageNet-like batch (fixed seed, short side 333 .. 500, aspect up to 4:3),
+new entry only, with the achieved bytes / s."""
 import argparse
 import json
 import os
@@ -51,15 +58,79 @@ def cpu_images_per_second(src: int, size: int, ratio: float, samples: int) -> fl
     return samples / (time.perf_counter() - t0)
 
 
+def packed_ab(args):
+    import random
+
+    import basd_amd._native as native
+    from basd_amd.data import DeviceDualView
+    from basd_amd.data.device_views import augment_records, clean_records, pack_images
+    b, size, ratio = args.batch, 224, 0.875
+    views = DeviceDualView(size, MEAN, STD, MEAN, STD, crop_ratio=ratio)
+
+    def prepare(images):
+        pixels, geometry = pack_images(images)
+        vp = torch.stack([views.draw(im.shape[1], im.shape[2], torch.Generator().manual_seed(i))
+                          for i, im in enumerate(images)])
+        dev = [t.cuda() for t in (pixels, geometry, clean_records(geometry, size, ratio), augment_records(vp, size))]
+
+        def run():
+            return (native.resample_u8_packed(dev[0], dev[1], dev[2], size),
+                    native.resample_u8_packed(dev[0], dev[1], dev[3], size))
+        return dev, run
+
+    g = torch.Generator().manual_seed(1)
+    uniform = torch.randint(0, 256, (b, 3, 256, 256), generator=g, dtype=torch.uint8)
+    dev, new = prepare(list(uniform))
+    images = uniform.cuda()
+
+    def old():
+        return native.resample_u8(images, dev[2], size), native.resample_u8(images, dev[3], size)
+
+    equal = all(torch.equal(x, y) for x, y in zip(old(), new()))
+    t_old, t_new = [], []
+    for _ in range(args.rounds):
+        t_old.append(median_ms(old, args.iters))
+        t_new.append(median_ms(new, args.iters))
+    traffic = 2 * uniform.numel() + 2 * b * 3 * size * size
+    print(json.dumps({"case": "uniform 256x256 -> 224, both views", "batch": b, "bit_equal": equal,
+                      "resample_u8_ms": [round(t, 4) for t in t_old],
+                      "resample_u8_packed_ms": [round(t, 4) for t in t_new],
+                      "old_median_ms": round(statistics.median(t_old), 4),
+                      "old_spread_ms": round(max(t_old) - min(t_old), 4),
+                      "new_median_ms": round(statistics.median(t_new), 4),
+                      "new_GBps": round(traffic / statistics.median(t_new) / 1e6, 1)}), flush=True)
+
+    rng = random.Random(0)
+    mixed = []
+    for i in range(b):
+        short = rng.randint(333, 500)
+        long_side = int(short * rng.uniform(1.0, 4.0 / 3.0))
+        h, w = (short, long_side) if rng.random() < 0.5 else (long_side, short)
+        mixed.append(torch.randint(0, 256, (3, h, w), generator=g, dtype=torch.uint8))
+    dev, new = prepare(mixed)
+    t_mixed = [median_ms(new, args.iters) for _ in range(args.rounds)]
+    traffic = 2 * dev[0].numel() + 2 * b * 3 * size * size
+    print(json.dumps({"case": "mixed sizes (short side 333 .. 500, aspect <= 4:3) -> 224, both views", "batch": b,
+                      "packed_bytes": dev[0].numel(), "pcie_bytes_packed": dev[0].numel() + b * (3 * 8 + 2 * 36 + 7 * 8 + 8),
+                      "pcie_bytes_fp32_views": 8 * b * 3 * size * size,
+                      "resample_u8_packed_ms": [round(t, 4) for t in t_mixed],
+                      "median_ms": round(statistics.median(t_mixed), 4),
+                      "GBps": round(traffic / statistics.median(t_mixed) / 1e6, 1)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--cpu-samples", type=int, default=64)
     ap.add_argument("--skip-cpu", action="store_true")
+    ap.add_argument("--packed", action="store_true", help="time basd_resample_u8_packed against basd_resample_u8")
+    ap.add_argument("--rounds", type=int, default=5, help="--packed: medians per entry, taken alternately")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("time_input_pipeline.py needs the GPU for the kernel side")
+    if args.packed:
+        return packed_ab(args)
     import basd_amd._native as native
     from basd_amd.data import DeviceDualView
     b = args.batch

@@ -34,7 +34,7 @@ EXPORTS = (
     "basd_selector_weights_workspace_bytes", "basd_selector_weights", "basd_attention_fwd_long_bf16",
     "basd_attention_bwd_long_workspace_bytes", "basd_attention_bwd_long_bf16", "basd_attention_fwd_f32x3_long",
     "basd_dwconv7_ln_bf16", "basd_grn_workspace_bytes", "basd_grn_bf16", "basd_patchify_bf16",
-    "basd_resample_u8", "basd_ta_normalize_u8", "basd_cls_tally",
+    "basd_resample_u8", "basd_ta_normalize_u8", "basd_cls_tally", "basd_resample_u8_packed",
 )
 
 
@@ -103,6 +103,7 @@ _SIGNATURES = {
     "basd_grn_bf16": (_P, _P, _P, _I, _I, _I, _F, _P, _I64, _P),
     "basd_patchify_bf16": (_P, _I, _I, _I, _I, _I64, _I64, _I64, _I64, _I, _I, _P, _P),
     "basd_resample_u8": (_P, _P, _I, _I, _I, _I, _P, _P),
+    "basd_resample_u8_packed": (_P, _I64, _P, _P, _I, _I, _P, _P),
     "basd_ta_normalize_u8": (_P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P),
     "basd_cls_tally": (_P, _I, _I64, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P),
 }
@@ -1315,6 +1316,25 @@ def resample_u8(images: torch.Tensor, records: torch.Tensor, image_size: int) ->
     out = torch.empty(b, 3, image_size, image_size, dtype=torch.uint8, device=images.device)
     _check(lib().basd_resample_u8(_ptr(images), _ptr(records), b, h, w, image_size, _ptr(out), _stream()),
            "basd_resample_u8")
+    return out
+
+
+PACKED_BAND_ROWS = 16          # output rows per workgroup of basd_resample_u8_packed (PK_ROWS in csrc/dual_view.hip)
+
+
+def resample_u8_packed(pixels: torch.Tensor, geometry: torch.Tensor, records: torch.Tensor, image_size: int) -> torch.Tensor:
+    """pixels [N] uint8 (sample b: planar [3, h_b, w_b] from byte geometry[b, 0]), geometry [B, 3] int64 {offset, h, w},
+    records [B, 9] int32 as for ``resample_u8`` with the sample's own size as the canvas -> [B, 3, S, S] uint8, per
+    sample what ``resample_u8`` gives on it alone.  A sample that does not lie inside ``pixels`` comes out zero."""
+    _need_cuda(pixels, geometry, records)
+    assert pixels.dtype == torch.uint8 and pixels.dim() == 1 and pixels.is_contiguous()
+    b = geometry.shape[0]
+    assert geometry.dtype == torch.int64 and geometry.shape == (b, 3) and geometry.is_contiguous()
+    assert records.dtype == torch.int32 and records.shape == (b, 9) and records.is_contiguous()
+    assert dual_view_supported(image_size), image_size
+    out = torch.empty(b, 3, image_size, image_size, dtype=torch.uint8, device=pixels.device)
+    _check(lib().basd_resample_u8_packed(_ptr(pixels), ctypes.c_int64(pixels.numel()), _ptr(geometry), _ptr(records), b,
+                                         image_size, _ptr(out), _stream()), "basd_resample_u8_packed")
     return out
 
 

@@ -1,6 +1,7 @@
 // Both training views from one uint8 batch (data/device_views.py; reference src/data/datasets.py:80-94, 137-149 runs
 // torchvision v2 in the loader workers):
 //   basd_resample_u8      window -> antialiased bilinear resize -> offset crop -> horizontal flip, uint8 out
+//   basd_resample_u8_packed  the same per sample, for samples of different sizes packed into one byte buffer
 //   basd_ta_normalize_u8  one TrivialAugmentWide operation (data/transforms.py, apply_ta_op) + ToDtype + Normalize, fp32 out
 // The arithmetic follows the CPU functions operation by operation: where they round a product before adding (the affine
 // coordinates, the blends) so do these kernels, hence no contraction in this file; the two resize passes accumulate with
@@ -95,6 +96,149 @@ __global__ void __launch_bounds__(256) resample_u8_kernel(const unsigned char* _
     *reinterpret_cast<unsigned*>(out + base) = word;
   } else {
     for (int64_t e = base; e < total; ++e) out[e] = (unsigned char)resample_px(src, rec, H, W, S, e);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Samples of different sizes packed into one byte buffer.  One workgroup per (sample, band of PK_ROWS output rows), all
+// three channels.  The taps of the S output columns and of the band's rows are worked out once per workgroup into LDS
+// (window start, tap count, weight sum, the first XW weights already divided by the sum: the same bits resample_px
+// recomputes per byte); the pixels then only read the tables.  A lane owns one output BYTE, so that the lanes of a
+// wave walk a row: the column table is read without bank conflicts and the source bytes of neighbouring lanes are
+// neighbours.  Four lanes put their bytes together for one 32-bit store.
+constexpr int PK_THREADS = 256;
+constexpr int PK_ROWS = 16;
+
+__host__ __device__ constexpr int pk_lds_bytes(int S) { return (S + PK_ROWS) * (2 * 16 + 3 * 4); }
+
+struct AxisTable {          // n entries, in this order in LDS (the float4 arrays first: 16-byte aligned)
+  float4* w03;              // normalised weights 0 .. 3 (0 beyond cnt)
+  float4* w47;              // 4 .. 7
+  float* tot;
+  int* lo;
+  int* cnt;
+};
+
+__device__ __forceinline__ void axis_entry(const AxisTable& T, int k, int v, int n_in, int n_out) {
+  const Taps t = aa_taps(v, n_in, n_out);
+  const float tot = aa_total(t);
+  float w[XW];
+#pragma unroll
+  for (int j = 0; j < XW; ++j) w[j] = j < t.cnt ? aa_weight(t, j) / tot : 0.0f;
+  T.w03[k] = make_float4(w[0], w[1], w[2], w[3]);
+  T.w47[k] = make_float4(w[4], w[5], w[6], w[7]);
+  T.tot[k] = tot;
+  T.lo[k] = t.lo;
+  T.cnt[k] = t.cnt;
+}
+
+__global__ void __launch_bounds__(PK_THREADS) resample_u8_packed_kernel(const unsigned char* __restrict__ pixels,
+                                                                        int64_t pixels_bytes,
+                                                                        const int64_t* __restrict__ geom,
+                                                                        const int* __restrict__ rec, int S, int bands,
+                                                                        unsigned char* __restrict__ out) {
+  extern __shared__ float4 pk_lds[];
+  const int tid = threadIdx.x;
+  const int b = blockIdx.x / bands, band = blockIdx.x - b * bands;
+  const int y0 = band * PK_ROWS, rows = min(PK_ROWS, S - y0);
+
+  AxisTable col, row;
+  col.w03 = pk_lds;
+  col.w47 = col.w03 + S;
+  row.w03 = col.w47 + S;
+  row.w47 = row.w03 + PK_ROWS;
+  col.tot = reinterpret_cast<float*>(row.w47 + PK_ROWS);
+  row.tot = col.tot + S;
+  col.lo = reinterpret_cast<int*>(row.tot + PK_ROWS);
+  row.lo = col.lo + S;
+  col.cnt = row.lo + PK_ROWS;
+  row.cnt = col.cnt + S;
+
+  // a sample that does not lie inside the buffer is never read: its output is zero
+  const int64_t off = geom[b * 3], H64 = geom[b * 3 + 1], W64 = geom[b * 3 + 2];
+  bool valid = off >= 0 && H64 >= 1 && H64 <= 16384 && W64 >= 1 && W64 <= 16384;
+  if (valid) {
+    const int64_t need = 3 * H64 * W64;                         // at most 3 * 2^28
+    valid = need <= pixels_bytes && off <= pixels_bytes - need;
+  }
+  const int H = valid ? (int)H64 : 1, W = valid ? (int)W64 : 1;
+
+  const int* R = rec + (int64_t)b * REC;                        // clamped as in resample_px
+  const int top = min(max(R[0], 0), H - 1), left = min(max(R[1], 0), W - 1);
+  const int h = min(max(R[2], 1), H - top), w = min(max(R[3], 1), W - left);
+  const int nh = max(R[4], 1), nw = max(R[5], 1);
+  const int off_y = R[6], off_x = R[7];
+  const bool flip = R[8] != 0;
+
+  if (valid) {
+    for (int k = tid; k < S + rows; k += PK_THREADS) {
+      if (k < S) axis_entry(col, k, min(max(off_x + k, 0), nw - 1), w, nw);
+      else axis_entry(row, k - S, min(max(off_y + y0 + (k - S), 0), nh - 1), h, nh);
+    }
+  }
+  __syncthreads();
+
+  const unsigned char* src = pixels + (valid ? off : 0);
+  const int len = rows * S;                                     // bytes of one channel of the band: contiguous in out
+  for (int c = 0; c < 3; ++c) {
+    const int64_t g0 = (((int64_t)b * 3 + c) * S + y0) * S;     // first byte; not 4-byte aligned when S is odd
+    const int lead = (int)(g0 & 3);                             // lanes walk from the aligned address below g0
+    const unsigned char* plane0 = src + ((int64_t)c * H + top) * W + left;
+    for (int p0 = 0; p0 < lead + len; p0 += PK_THREADS) {
+      const int p = p0 + tid - lead;                            // byte of the band, (p + lead) % 4 == tid % 4
+      const bool mine = p >= 0 && p < len;
+      unsigned v = 0;
+      if (mine && valid) {
+        const int y = p / S, x = p - y * S;
+        const int k = flip ? S - 1 - x : x;
+        const int cx = col.cnt[k], cy = row.cnt[y];
+        if (cx >= 1 && cy >= 1) {
+          const float4 a = col.w03[k], bq = col.w47[k];
+          const float wx[XW] = {a.x, a.y, a.z, a.w, bq.x, bq.y, bq.z, bq.w};
+          const float4 ya = row.w03[y], yb = row.w47[y];
+          const float wy8[XW] = {ya.x, ya.y, ya.z, ya.w, yb.x, yb.y, yb.z, yb.w};
+          Taps tx = {}, ty = {};                                    // only filters of more than XW taps need them
+          float tot_x = 0.0f, tot_y = 0.0f;
+          if (cx > XW) {
+            tx = aa_taps(min(max(off_x + k, 0), nw - 1), w, nw);
+            tot_x = col.tot[k];
+          }
+          if (cy > XW) {
+            ty = aa_taps(min(max(off_y + y0 + y, 0), nh - 1), h, nh);
+            tot_y = row.tot[y];
+          }
+          const unsigned char* plane = plane0 + (int64_t)row.lo[y] * W + col.lo[k];
+          float acc = 0.0f;
+          for (int i = 0; i < cy; ++i) {
+            const unsigned char* line = plane + (int64_t)i * W;
+            float hs = (float)line[0] * wx[0];
+#pragma unroll
+            for (int j = 1; j < XW; ++j)
+              if (j < cx) hs = fmaf((float)line[j], wx[j], hs);
+            for (int j = XW; j < cx; ++j) hs = fmaf((float)line[j], aa_weight(tx, j) / tot_x, hs);
+            float wy = 0.0f;
+#pragma unroll
+            for (int j = 0; j < XW; ++j)
+              if (i == j) wy = wy8[j];
+            if (i >= XW) wy = aa_weight(ty, i) / tot_y;
+            acc = i == 0 ? hs * wy : fmaf(hs, wy, acc);
+          }
+          v = (unsigned)fminf(fmaxf(rintf(acc), 0.0f), 255.0f);
+        }
+      }
+      // lanes 4 m .. 4 m + 3 hold the bytes of one aligned word of out
+      unsigned word = v;
+      word |= (unsigned)__shfl_down((int)v, 1, 64) << 8;
+      word |= (unsigned)__shfl_down((int)v, 2, 64) << 16;
+      word |= (unsigned)__shfl_down((int)v, 3, 64) << 24;
+      const int q = tid & 3;
+      const bool whole = p - q >= 0 && p - q + 4 <= len;        // the same answer in the four lanes
+      if (whole) {
+        if (q == 0) *reinterpret_cast<unsigned*>(out + g0 + p) = word;
+      } else if (mine) {
+        out[g0 + p] = (unsigned char)v;                         // the band's byte head and tail
+      }
+    }
   }
 }
 
@@ -307,6 +451,24 @@ extern "C" int basd_resample_u8(const void* src, const int* rec, int B, int H, i
   hipLaunchKernelGGL(resample_u8_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream,
                      (const unsigned char*)src, rec, H, W, S, (unsigned char*)out, total);
   return check_launch("resample_u8");
+}
+
+extern "C" int basd_resample_u8_packed(const void* pixels, int64_t pixels_bytes, const int64_t* geom, const int* rec,
+                                       int B, int S, void* out, void* stream) {
+  using namespace basd;
+  if (B == 0) return BASD_OK;
+  if (B < 0 || !dual_view_size_ok(S)) return fail(BASD_ERR_SHAPE, "resample_u8_packed: B = %d, S = %d (3 .. 1024)", B, S);
+  if (pixels == nullptr || geom == nullptr || rec == nullptr || out == nullptr || pixels_bytes < 0)
+    return fail(BASD_ERR_SHAPE, "resample_u8_packed: null pointer or negative pixels_bytes");
+  if (((uintptr_t)out & 3) != 0 || ((uintptr_t)rec & 3) != 0 || ((uintptr_t)geom & 7) != 0)
+    return fail(BASD_ERR_SHAPE, "resample_u8_packed: out and rec must be 4-byte aligned, geom 8-byte aligned");
+  const int bands = (S + PK_ROWS - 1) / PK_ROWS;
+  const int64_t grid = (int64_t)B * bands;
+  if (grid > 0x7fffffffLL) return fail(BASD_ERR_SHAPE, "resample_u8_packed: %lld workgroups", (long long)grid);
+  hipLaunchKernelGGL(resample_u8_packed_kernel, dim3((unsigned)grid), dim3(PK_THREADS), (size_t)pk_lds_bytes(S),
+                     (hipStream_t)stream, (const unsigned char*)pixels, pixels_bytes, geom, rec, S, bands,
+                     (unsigned char*)out);
+  return check_launch("resample_u8_packed");
 }
 
 extern "C" int basd_ta_normalize_u8(const void* img, const int* ops, const double* mags, int B, int S, float mean0,

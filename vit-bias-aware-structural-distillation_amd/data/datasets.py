@@ -25,7 +25,7 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
-from .device_views import DeviceDualView, DeviceEvalView
+from .device_views import DeviceDualView, DeviceEvalView, augment_records, clean_records, pack_images
 from .transforms import AugmentTransform, EvalTransform
 
 _NUM_WORKERS = 8
@@ -148,11 +148,37 @@ def _collate(samples):
     return out
 
 
-def _loader(ds, batch_size, *, shuffle, drop_last, num_workers, seed):
+class _PackedCollate:
+    """``device_views="packed"``: the batch's images, whatever their sizes, as one flat uint8 buffer + geometry, with
+    the records of both views built here on the host (data/device_views.py); the other keys as ``_collate``"""
+
+    def __init__(self, image_size: int, crop_ratio: float):
+        self.image_size, self.crop_ratio = int(image_size), float(crop_ratio)
+
+    def __call__(self, samples):
+        pixels, geometry = pack_images([s["image"] for s in samples])
+        out = {"pixels": pixels, "geometry": geometry,
+               "clean_rec": clean_records(geometry, self.image_size, self.crop_ratio)}
+        out.update(_collate([{k: v for k, v in s.items() if k != "image"} for s in samples]))
+        if "view_params" in out:
+            out["aug_rec"] = augment_records(out["view_params"], self.image_size)
+        return out
+
+
+def _loader(ds, batch_size, *, shuffle, drop_last, num_workers, seed, collate_fn=_collate):
     g = torch.Generator().manual_seed(seed)
     return DataLoader(ds, batch_size=batch_size, shuffle=shuffle, num_workers=num_workers, drop_last=drop_last,
-                      pin_memory=torch.cuda.is_available(), persistent_workers=num_workers > 0, collate_fn=_collate,
+                      pin_memory=torch.cuda.is_available(), persistent_workers=num_workers > 0, collate_fn=collate_fn,
                       generator=g)
+
+
+def _device_views_mode(device_views):
+    """``False`` | ``True`` (uniform uint8 batches, .npz splits) | ``"packed"`` (images of any sizes, any split)"""
+    if isinstance(device_views, str):
+        if device_views != "packed":
+            raise ValueError(f"device_views takes False, True or 'packed', got {device_views!r}")
+        return "packed"
+    return bool(device_views)
 
 
 def _require_npz(ds: LocalImageSplit, dataset_name: str) -> None:
@@ -162,16 +188,21 @@ def _require_npz(ds: LocalImageSplit, dataset_name: str) -> None:
 
 
 def create_eval_loader(dataset_name: str, *, image_size: int, batch_size: int, mean, std, crop_ratio: float,
-                       num_workers: int = _NUM_WORKERS, class_names=None, device_views: bool = False) -> DataLoader:
+                       num_workers: int = _NUM_WORKERS, class_names=None, device_views=False) -> DataLoader:
     """reference :97-123: ``{"pixel_values", "label"}`` batches of the evaluation split, not shuffled.
     ``device_views``: the loader yields raw ``{"image" uint8, "label"}`` batches and carries the object that builds
-    ``pixel_values`` on the device as ``loader.device_views`` (``evaluate_model`` applies it)."""
+    ``pixel_values`` on the device as ``loader.device_views`` (``evaluate_model`` applies it).  ``"packed"``: packed
+    batches ``{"pixels", "geometry", "clean_rec", "label"}``, for directory splits too."""
+    device_views = _device_views_mode(device_views)
     info = dataset_info(dataset_name)
     ds = LocalImageSplit(dataset_name, info["eval_split"], class_names=class_names or info["class_names"])
     if device_views:
-        _require_npz(ds, dataset_name)
+        packed = device_views == "packed"
+        if not packed:
+            _require_npz(ds, dataset_name)
         views = DeviceEvalView(image_size, mean, std, crop_ratio)
-        loader = _loader(ds, batch_size, shuffle=False, drop_last=False, num_workers=num_workers, seed=0)
+        loader = _loader(ds, batch_size, shuffle=False, drop_last=False, num_workers=num_workers, seed=0,
+                         collate_fn=_PackedCollate(image_size, crop_ratio) if packed else _collate)
         loader.device_views = views
         return loader
     tf = build_eval_transform(image_size, mean=mean, std=std, crop_ratio=crop_ratio)
@@ -228,7 +259,9 @@ def create_dataloaders(config, *, teacher_stats, num_workers: int = _NUM_WORKERS
     """reference :126-178: (train loader of dual-view batches, evaluation loader).  ``teacher_stats`` = (mean, std) the
     frozen teacher was trained with (``TeacherModel.mean / .std``).  ``device_views`` (default:
     ``config.data.device_views``, else off): the workers ship uint8 images and augmentation parameters, and the loaders
-    carry the objects that build the views on the device as ``loader.device_views`` (data/device_views.py)."""
+    carry the objects that build the views on the device as ``loader.device_views`` (data/device_views.py).
+    ``device_views="packed"`` (``data.device_views: packed``) does the same for images of different sizes: directory
+    splits and ``.npz`` splits alike, as packed batches."""
     name = config.data.dataset
     info = dataset_info(name)
     mean, std = get_channel_stats(name)
@@ -240,16 +273,20 @@ def create_dataloaders(config, *, teacher_stats, num_workers: int = _NUM_WORKERS
     seed = int(config.run.get("seed", 0)) if hasattr(config, "run") else 0
     train = LocalImageSplit(name, info["train_split"])
     if device_views is None:
-        device_views = bool(config.data.get("device_views", False))
+        device_views = config.data.get("device_views", False)
+    device_views = _device_views_mode(device_views)
+    packed = device_views == "packed"
     if device_views:
-        _require_npz(train, name)
+        if not packed:
+            _require_npz(train, name)
         views = DeviceDualView(image_size, mean, std, teacher_mean, teacher_std, crop_ratio)
         train.transform = _RawDualView(views, seed)
     else:
         train.transform = _DualView(clean_tf, aug_tf, seed)
-    train_loader = _loader(train, config.data.batch_size, shuffle=True, drop_last=True, num_workers=num_workers, seed=seed)
+    train_loader = _loader(train, config.data.batch_size, shuffle=True, drop_last=True, num_workers=num_workers, seed=seed,
+                           collate_fn=_PackedCollate(image_size, crop_ratio) if packed else _collate)
     if device_views:
         train_loader.device_views = views
     val_loader = create_eval_loader(name, image_size=image_size, batch_size=config.data.batch_size, mean=mean, std=std,
-                                    crop_ratio=crop_ratio, num_workers=num_workers, device_views=bool(device_views))
+                                    crop_ratio=crop_ratio, num_workers=num_workers, device_views=device_views)
     return train_loader, val_loader
