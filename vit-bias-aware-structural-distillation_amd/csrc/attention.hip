@@ -19,23 +19,9 @@
 //                 transposing LDS read ds_read_b64_tr_b16 on the same eight keys -- no transpose of P or V;
 //   the 16 x 64 output tile is staged through LDS so that every lane stores 16 contiguous bytes.
 // Arithmetic: fp32 logits and probabilities like a flash kernel (P rounded to bf16 for the second MFMA).
-#include "basd_common.h"
+#include "basd_frag.h"
 
 namespace basd {
-
-typedef float at_f32x4 __attribute__((ext_vector_type(4)));
-typedef short at_bf16x8 __attribute__((ext_vector_type(8)));
-typedef short at_v4s __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) at_v4s at_lds_v4s;
-
-
-typedef float at_f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 at_bf16x2 __attribute__((ext_vector_type(2)));
-// two fp32 -> packed bf16 (round to nearest even): one v_cvt_pk_bf16_f32
-__device__ __forceinline__ unsigned int pack_bf16(float a, float b) {
-  at_bf16x2 r = __builtin_convertvector((at_f32x2){a, b}, at_bf16x2);
-  return *reinterpret_cast<unsigned int*>(&r);
-}
 
 __device__ __forceinline__ unsigned short f32_to_bf16_rne(float f) {
   unsigned int u = __float_as_uint(f);
@@ -121,19 +107,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   for (int qt = wave; qt < nqt; qt += 4) {
     const int q0 = qt * 16;
     // Q fragments of this tile: query q0 + li, d = 32 ks + 8 g .. + 7 (fetched one tile ahead)
-    at_bf16x8 qf[NDS];
+    bf16x8 qf[NDS];
 #pragma unroll
-    for (int ks = 0; ks < NDS; ++ks) qf[ks] = *reinterpret_cast<at_bf16x8*>(&qnext[ks]);
+    for (int ks = 0; ks < NDS; ++ks) qf[ks] = *reinterpret_cast<bf16x8*>(&qnext[ks]);
     load_q(qt + 4, qnext);
     // ---- S^T tiles
-    at_f32x4 s[NKT];
+    f32x4 s[NKT];
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt) {
-      at_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < NDS; ++ks) {
         const uint4 kk = *reinterpret_cast<const uint4*>(Ks + (16 * kt + li) * AT_LD + 32 * ks + 8 * g);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const at_bf16x8*>(&kk), qf[ks], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8*>(&kk), qf[ks], acc, 0, 0, 0);
       }
       s[kt] = acc;
       if ((kt & 3) == 3) __builtin_amdgcn_sched_barrier(0);     // keep at most four tiles of K fragments in flight
@@ -212,9 +198,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // log-sum-exp of the scaled logits (natural log): what the backward kernel recomputes P from
     if (lse != nullptr && g == 0 && q0 + li < T) lse[((size_t)b * H + h) * T + q0 + li] = fmaf(mx, scale, __logf(sum));
     // ---- O = P V
-    at_f32x4 o[NDT];
+    f32x4 o[NDT];
 #pragma unroll
-    for (int dt = 0; dt < NDT; ++dt) o[dt] = (at_f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int dt = 0; dt < NDT; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) {
       const int K1 = (2 * ks + 1 < NKT) ? 2 * ks + 1 : 0;      // constant after unrolling
@@ -223,15 +209,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       pw.y = pack_bf16(s[2 * ks][2] * inv, s[2 * ks][3] * inv);
       pw.z = (2 * ks + 1 < NKT) ? pack_bf16(s[K1][0] * inv, s[K1][1] * inv) : 0u;
       pw.w = (2 * ks + 1 < NKT) ? pack_bf16(s[K1][2] * inv, s[K1][3] * inv) : 0u;
-      const at_bf16x8 pa = *reinterpret_cast<const at_bf16x8*>(&pw);
+      const bf16x8 pa = *reinterpret_cast<const bf16x8*>(&pw);
       // B fragment: column d = 16 dt + li, keys {32 ks + 4 g + e} and {32 ks + 16 + 4 g + e}, e = 0..3
+      // tr_split of basd_frag.h written out on the kernel's own li (through the helper the generated code differs)
       const int qq = li >> 2, pp = li & 3;
 #pragma unroll
       for (int dt = 0; dt < NDT; ++dt) {
         const unsigned short* a0 = Vs + (32 * ks + 4 * g + qq) * AT_LD + 16 * dt + 4 * pp;
-        const at_v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((at_lds_v4s*)a0);
-        const at_v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((at_lds_v4s*)(a0 + 16 * AT_LD));
-        const at_bf16x8 vb = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)a0);
+        const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(a0 + 16 * AT_LD));
+        const bf16x8 vb = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
         o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa, vb, o[dt], 0, 0, 0);
       }
     }

@@ -34,44 +34,14 @@
 // CU); NP = 3: 248 VGPRs, no scratch, 61 440 B of LDS.  Measured (MI355X, kernel trace, B 256, T 197, H 3): 63.5 us per
 // launch, 2.45 TB/s over the algorithmic 155.5 MB (the two-key-pairs-per-wave, one-wave-per-SIMD version: 85 us); B 64,
 // T 65, H 3: 8.5 us (11.1).  Tried and kept out: 8 waves for NP = 3 (8.1 .. 9.0 us: no better than 4).
-#include "basd_common.h"
+#include "basd_frag.h"
 
 namespace basd {
-
-typedef float ab_f32x4 __attribute__((ext_vector_type(4)));
-typedef short ab_bf16x8 __attribute__((ext_vector_type(8)));
-typedef short ab_v4s __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) ab_v4s ab_lds_v4s;
-typedef float ab_f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 ab_bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int AB_HD = 64;
 constexpr int AB_LD = AB_HD + 8;          // bf16 row stride of the Q / dO / K images (144 B)
 constexpr int AB_SLD = 36;                // bf16 row stride of the wave-private dS^T tile (72 B: 8-byte stores of 16 lanes hit 32 banks)
 constexpr int AB_QLD = 68;                // fp32 row stride of the dQ image (272 B)
-
-__device__ __forceinline__ unsigned int ab_pack(float a, float b) {
-  ab_bf16x2 r = __builtin_convertvector((ab_f32x2){a, b}, ab_bf16x2);
-  return *reinterpret_cast<unsigned int*>(&r);
-}
-
-// 8 rows {row0 .. row0+3, row0+16 .. row0+19} of column col0 + (lane & 15): the k order of two stacked 16-row
-// accumulator tiles (4 (lane >> 4) + r in each)
-__device__ __forceinline__ ab_bf16x8 ab_tr_split(const unsigned short* tile, int ld, int row0, int col0, int lane) {
-  const int li = lane & 15, qq = li >> 2, pp = li & 3;
-  const unsigned short* a0 = tile + (row0 + qq) * ld + col0 + 4 * pp;
-  const ab_v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ab_lds_v4s*)a0);
-  const ab_v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ab_lds_v4s*)(a0 + 16 * ld));
-  return (ab_bf16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-// 8 CONSECUTIVE rows row0 .. row0+7 of column col0 + (lane & 15)
-__device__ __forceinline__ ab_bf16x8 ab_tr_cons(const unsigned short* tile, int ld, int row0, int col0, int lane) {
-  const int li = lane & 15, qq = li >> 2, pp = li & 3;
-  const unsigned short* a0 = tile + (row0 + qq) * ld + col0 + 4 * pp;
-  const ab_v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ab_lds_v4s*)a0);
-  const ab_v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ab_lds_v4s*)(a0 + 4 * ld));
-  return (ab_bf16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
 
 template <int NP, int NW>   // pairs of 16-row tiles: T <= 32 * NP; waves per workgroup (NW > NP never work: barriers only)
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2))) void attention_bwd_kernel(
@@ -120,7 +90,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     }
   }
   // B operands of S / dP: lane holds key 32 wave + 16 t + li, d = 32 ks + 8 g .. + 7 (16-byte global loads)
-  ab_bf16x8 kb[2][2], vb[2][2];
+  bf16x8 kb[2][2], vb[2][2];
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -132,8 +102,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
         kv = *reinterpret_cast<const uint4*>(p + (size_t)H * AB_HD);
         vv = *reinterpret_cast<const uint4*>(p + (size_t)2 * H * AB_HD);
       }
-      kb[t][ks] = *reinterpret_cast<const ab_bf16x8*>(&kv);
-      vb[t][ks] = *reinterpret_cast<const ab_bf16x8*>(&vv);
+      kb[t][ks] = *reinterpret_cast<const bf16x8*>(&kv);
+      vb[t][ks] = *reinterpret_cast<const bf16x8*>(&vv);
     }
 
   // ---- Q and dO images (rows >= T zero), delta = rowsum(dO * O), -LSE / scale
@@ -164,24 +134,24 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
   // A operand of dQ^T += K^T dS^T: lane holds d = 16 dt + li, keys 8 g .. + 7 of the pair.  The K fragments above ARE
   // the pair's row-major tile (row 16 t + li, columns 32 ks + 8 g .. + 7): it goes through a wave-private tile inside
   // the (not yet used) dQ image and comes back through the transposing read
-  ab_bf16x8 kt[4] = {};
+  bf16x8 kt[4] = {};
   if (wave < NP) {
     unsigned short* kst = reinterpret_cast<unsigned short*>(dQs) + wave * 32 * AB_LD;
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
-        *reinterpret_cast<ab_bf16x8*>(kst + (16 * t + li) * AB_LD + 32 * ks + 8 * g) = kb[t][ks];
+        *reinterpret_cast<bf16x8*>(kst + (16 * t + li) * AB_LD + 32 * ks + 8 * g) = kb[t][ks];
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) kt[dt] = ab_tr_cons(kst, AB_LD, 8 * g, 16 * dt, lane);
+    for (int dt = 0; dt < 4; ++dt) kt[dt] = tr_cons(kst, AB_LD, 8 * g, 16 * dt, lane);
   }
-  ab_f32x4 dkt[2][4], dvt[2][4];                     // dK^T / dV^T [key tile][d tile]: rows d = 4 g + r, column key li
+  f32x4 dkt[2][4], dvt[2][4];                     // dK^T / dV^T [key tile][d tile]: rows d = 4 g + r, column key li
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) {
-      dkt[t][dt] = (ab_f32x4){0.f, 0.f, 0.f, 0.f};
-      dvt[t][dt] = (ab_f32x4){0.f, 0.f, 0.f, 0.f};
+      dkt[t][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      dvt[t][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
   __syncthreads();                                   // the images are complete; every kt read has returned
 
@@ -194,52 +164,52 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     if (live) {
       const int q0 = 32 * qp;
       // A operands (row reads): query q0 + 16 t + li, d = 32 ks + 8 g .. + 7
-      ab_bf16x8 qa[2][2], da[2][2];
+      bf16x8 qa[2][2], da[2][2];
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-          qa[t][ks] = *reinterpret_cast<const ab_bf16x8*>(Qs + (q0 + 16 * t + li) * AB_LD + 32 * ks + 8 * g);
-          da[t][ks] = *reinterpret_cast<const ab_bf16x8*>(dOs + (q0 + 16 * t + li) * AB_LD + 32 * ks + 8 * g);
+          qa[t][ks] = *reinterpret_cast<const bf16x8*>(Qs + (q0 + 16 * t + li) * AB_LD + 32 * ks + 8 * g);
+          da[t][ks] = *reinterpret_cast<const bf16x8*>(dOs + (q0 + 16 * t + li) * AB_LD + 32 * ks + 8 * g);
         }
       // row constants of the two query tiles: rows 4 g + r
-      ab_f32x4 c_lse[2], c_del[2];
+      f32x4 c_lse[2], c_del[2];
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        c_lse[t] = *reinterpret_cast<const ab_f32x4*>(nlse + q0 + 16 * t + 4 * g);
-        c_del[t] = *reinterpret_cast<const ab_f32x4*>(ndel + q0 + 16 * t + 4 * g);
+        c_lse[t] = *reinterpret_cast<const f32x4*>(nlse + q0 + 16 * t + 4 * g);
+        c_del[t] = *reinterpret_cast<const f32x4*>(ndel + q0 + 16 * t + 4 * g);
       }
       // transposed operands (column reads): d = 16 dt + li, queries {q0 + 4 g + r} and {q0 + 16 + 4 g + r}
-      ab_bf16x8 qT[4], dT[4];
+      bf16x8 qT[4], dT[4];
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
-        qT[dt] = ab_tr_split(Qs, AB_LD, q0 + 4 * g, 16 * dt, lane);
-        dT[dt] = ab_tr_split(dOs, AB_LD, q0 + 4 * g, 16 * dt, lane);
+        qT[dt] = tr_split(Qs, AB_LD, q0 + 4 * g, 16 * dt, lane);
+        dT[dt] = tr_split(dOs, AB_LD, q0 + 4 * g, 16 * dt, lane);
       }
       // the pair's rows of the dQ image, as the initial accumulators of dQ^T below: row = query 16 tq + li, FOUR
       // CONSECUTIVE d (16 dt + 4 g + r) per lane, 16-byte accesses.  No other wave is on this query pair during the
       // step.  Step 0 starts from zero and so overwrites (it covers every pair that holds tokens: the image is never
       // zeroed).
-      ab_f32x4 dq[2][4];
+      f32x4 dq[2][4];
       float* dqrow = dQs + (q0 + li) * AB_QLD + 4 * g;
 #pragma unroll
       for (int tq = 0; tq < 2; ++tq)
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt) dq[tq][dt] = (ab_f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int dt = 0; dt < 4; ++dt) dq[tq][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
       if (step != 0) {
 #pragma unroll
         for (int tq = 0; tq < 2; ++tq)
 #pragma unroll
           for (int dt = 0; dt < 4; ++dt)
-            dq[tq][dt] = *reinterpret_cast<const ab_f32x4*>(dqrow + 16 * tq * AB_QLD + 16 * dt);
+            dq[tq][dt] = *reinterpret_cast<const f32x4*>(dqrow + 16 * tq * AB_QLD + 16 * dt);
       }
       // S' and dP' of the 32 x 32 block: [query tile tq][key tile tk]
-      ab_f32x4 s[2][2], dp[2][2];
+      f32x4 s[2][2], dp[2][2];
 #pragma unroll
       for (int tq = 0; tq < 2; ++tq)
 #pragma unroll
         for (int tk = 0; tk < 2; ++tk) {
-          ab_f32x4 a = c_lse[tq], d = c_del[tq];
+          f32x4 a = c_lse[tq], d = c_del[tq];
 #pragma unroll
           for (int ks = 0; ks < 2; ++ks) {
             a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[tq][ks], kb[tk][ks], a, 0, 0, 0);
@@ -249,7 +219,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
           dp[tq][tk] = d;
         }
       // P and dS; packed as B operands: element j of lane group g <-> query 16 (j >> 2) + 4 g + (j & 3)
-      ab_bf16x8 pB[2], sB[2];
+      bf16x8 pB[2], sB[2];
 #pragma unroll
       for (int tk = 0; tk < 2; ++tk) {
         unsigned int pw[4], sw[4];
@@ -261,16 +231,16 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
             p[r] = __builtin_amdgcn_exp2f(c2 * s[tq][tk][r]);
             ds[r] = scale * p[r] * dp[tq][tk][r];
           }
-          pw[2 * tq] = ab_pack(p[0], p[1]);
-          pw[2 * tq + 1] = ab_pack(p[2], p[3]);
-          sw[2 * tq] = ab_pack(ds[0], ds[1]);
-          sw[2 * tq + 1] = ab_pack(ds[2], ds[3]);
+          pw[2 * tq] = pack_bf16(p[0], p[1]);
+          pw[2 * tq + 1] = pack_bf16(p[2], p[3]);
+          sw[2 * tq] = pack_bf16(ds[0], ds[1]);
+          sw[2 * tq + 1] = pack_bf16(ds[2], ds[3]);
           // dS^T tile for dQ: row = key 16 tk + li, columns = queries 16 tq + 4 g .. + 3 (one 8-byte store)
           *reinterpret_cast<uint2*>(mytile + (16 * tk + li) * AB_SLD + 16 * tq + 4 * g) =
               make_uint2(sw[2 * tq], sw[2 * tq + 1]);
         }
-        pB[tk] = *reinterpret_cast<const ab_bf16x8*>(pw);
-        sB[tk] = *reinterpret_cast<const ab_bf16x8*>(sw);
+        pB[tk] = *reinterpret_cast<const bf16x8*>(pw);
+        sB[tk] = *reinterpret_cast<const bf16x8*>(sw);
       }
       // dV^T += dO^T P,  dK^T += Q^T dS
 #pragma unroll
@@ -284,11 +254,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
       // operations complete in order)
 #pragma unroll
       for (int tq = 0; tq < 2; ++tq) {
-        const ab_bf16x8 sa = ab_tr_cons(mytile, AB_SLD, 8 * g, 16 * tq, lane);
+        const bf16x8 sa = tr_cons(mytile, AB_SLD, 8 * g, 16 * tq, lane);
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
           dq[tq][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kt[dt], sa, dq[tq][dt], 0, 0, 0);
-          *reinterpret_cast<ab_f32x4*>(dqrow + 16 * tq * AB_QLD + 16 * dt) = dq[tq][dt];
+          *reinterpret_cast<f32x4*>(dqrow + 16 * tq * AB_QLD + 16 * dt) = dq[tq][dt];
         }
       }
     }
@@ -307,9 +277,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
         *reinterpret_cast<uint2*>(kst + (16 * tk + li) * AB_LD + 16 * dt + 4 * g) =
-            make_uint2(ab_pack(dkt[tk][dt][0], dkt[tk][dt][1]), ab_pack(dkt[tk][dt][2], dkt[tk][dt][3]));
+            make_uint2(pack_bf16(dkt[tk][dt][0], dkt[tk][dt][1]), pack_bf16(dkt[tk][dt][2], dkt[tk][dt][3]));
         *reinterpret_cast<uint2*>(vst + (16 * tk + li) * AB_LD + 16 * dt + 4 * g) =
-            make_uint2(ab_pack(dvt[tk][dt][0], dvt[tk][dt][1]), ab_pack(dvt[tk][dt][2], dvt[tk][dt][3]));
+            make_uint2(pack_bf16(dvt[tk][dt][0], dvt[tk][dt][1]), pack_bf16(dvt[tk][dt][2], dvt[tk][dt][3]));
       }
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -329,10 +299,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     const float4 a = *reinterpret_cast<const float4*>(dQs + r * AB_QLD + c8 * 8);
     const float4 c = *reinterpret_cast<const float4*>(dQs + r * AB_QLD + c8 * 8 + 4);
     uint4 w;
-    w.x = ab_pack(a.x, a.y);
-    w.y = ab_pack(a.z, a.w);
-    w.z = ab_pack(c.x, c.y);
-    w.w = ab_pack(c.z, c.w);
+    w.x = pack_bf16(a.x, a.y);
+    w.y = pack_bf16(a.z, a.w);
+    w.z = pack_bf16(c.x, c.y);
+    w.w = pack_bf16(c.z, c.w);
     *reinterpret_cast<uint4*>(dbase + (size_t)r * row + c8 * 8) = w;
   }
 }

@@ -26,41 +26,12 @@
 // dQ: the four waves' 32 x hd contributions meet in LDS and are added in wave order; the block's sum goes to a
 // per-key-block fp32 partial in the workspace (vector stores), and attn_long_dq_kernel adds the partials in key-block
 // order and writes the bf16 dQ slice of dqkv.  No atomics: the gradient is bitwise reproducible.
-#include "basd_common.h"
+#include "basd_frag.h"
 
 namespace basd {
 
-typedef float al_f32x4 __attribute__((ext_vector_type(4)));
-typedef short al_bf16x8 __attribute__((ext_vector_type(8)));
-typedef short al_v4s __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) al_v4s al_lds_v4s;
-typedef float al_f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 al_bf16x2 __attribute__((ext_vector_type(2)));
-
 constexpr int AL_MAXT = 1024;
 constexpr float AL_LOG2E = 1.4426950408889634f;
-
-__device__ __forceinline__ unsigned int al_pack(float a, float b) {
-  al_bf16x2 r = __builtin_convertvector((al_f32x2){a, b}, al_bf16x2);
-  return *reinterpret_cast<unsigned int*>(&r);
-}
-
-// 8 rows {row0 .. row0+3, row0+16 .. row0+19} of column col0 + (lane & 15)
-__device__ __forceinline__ al_bf16x8 al_tr_split(const unsigned short* tile, int ld, int row0, int col0, int lane) {
-  const int li = lane & 15, qq = li >> 2, pp = li & 3;
-  const unsigned short* a0 = tile + (row0 + qq) * ld + col0 + 4 * pp;
-  const al_v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((al_lds_v4s*)a0);
-  const al_v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((al_lds_v4s*)(a0 + 16 * ld));
-  return (al_bf16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-// 8 CONSECUTIVE rows row0 .. row0+7 of column col0 + (lane & 15)
-__device__ __forceinline__ al_bf16x8 al_tr_cons(const unsigned short* tile, int ld, int row0, int col0, int lane) {
-  const int li = lane & 15, qq = li >> 2, pp = li & 3;
-  const unsigned short* a0 = tile + (row0 + qq) * ld + col0 + 4 * pp;
-  const al_v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((al_lds_v4s*)a0);
-  const al_v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((al_lds_v4s*)(a0 + 4 * ld));
-  return (al_bf16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
 
 // ------------------------------------------------------------------------------------------------------ forward ----
 template <int HD>
@@ -101,19 +72,19 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(const unsigned short
   };
   load_kv(0);
   // Q fragments of this wave's tile: query q0 + li, d = 32 ks + 8 g .. + 7 (zero beyond T and beyond hd)
-  al_bf16x8 qf[NDS];
+  bf16x8 qf[NDS];
 #pragma unroll
   for (int ks = 0; ks < NDS; ++ks) {
     uint4 v = make_uint4(0, 0, 0, 0);
     if (q0 + li < T && 32 * ks + 8 * g < HD)
       v = *reinterpret_cast<const uint4*>(base + (size_t)(q0 + li) * row + 32 * ks + 8 * g);
-    qf[ks] = *reinterpret_cast<const al_bf16x8*>(&v);
+    qf[ks] = *reinterpret_cast<const bf16x8*>(&v);
   }
   const float sl2 = scale * AL_LOG2E;
   float m_run = -3.0e38f, l_run = 0.f;               // per query column li (same value in the four lane groups)
-  al_f32x4 o[NDT];
+  f32x4 o[NDT];
 #pragma unroll
-  for (int dt = 0; dt < NDT; ++dt) o[dt] = (al_f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int dt = 0; dt < NDT; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
   const int ntiles = (T + KB - 1) / KB;
   for (int j = 0; j < ntiles; ++j) {
     const int k0 = j * KB;
@@ -130,13 +101,13 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(const unsigned short
     lds_barrier();
     if (j + 1 < ntiles) load_kv(k0 + KB);            // in flight during this tile's products
     // ---- S^T of the 4 key tiles
-    al_f32x4 s[4];
+    f32x4 s[4];
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) {
-      al_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < NDS; ++ks) {
-        const al_bf16x8 kk = *reinterpret_cast<const al_bf16x8*>(Ks + (16 * kt + li) * LD + 32 * ks + 8 * g);
+        const bf16x8 kk = *reinterpret_cast<const bf16x8*>(Ks + (16 * kt + li) * LD + 32 * ks + 8 * g);
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kk, qf[ks], acc, 0, 0, 0);
       }
       s[kt] = acc;
@@ -179,14 +150,14 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(const unsigned short
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       uint4 pw;
-      pw.x = al_pack(s[2 * ks][0], s[2 * ks][1]);
-      pw.y = al_pack(s[2 * ks][2], s[2 * ks][3]);
-      pw.z = al_pack(s[2 * ks + 1][0], s[2 * ks + 1][1]);
-      pw.w = al_pack(s[2 * ks + 1][2], s[2 * ks + 1][3]);
-      const al_bf16x8 pa = *reinterpret_cast<const al_bf16x8*>(&pw);
+      pw.x = pack_bf16(s[2 * ks][0], s[2 * ks][1]);
+      pw.y = pack_bf16(s[2 * ks][2], s[2 * ks][3]);
+      pw.z = pack_bf16(s[2 * ks + 1][0], s[2 * ks + 1][1]);
+      pw.w = pack_bf16(s[2 * ks + 1][2], s[2 * ks + 1][3]);
+      const bf16x8 pa = *reinterpret_cast<const bf16x8*>(&pw);
 #pragma unroll
       for (int dt = 0; dt < NDT; ++dt) {
-        const al_bf16x8 vb = al_tr_split(Vs, LD, 32 * ks + 4 * g, 16 * dt, lane);
+        const bf16x8 vb = tr_split(Vs, LD, 32 * ks + 4 * g, 16 * dt, lane);
         o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa, vb, o[dt], 0, 0, 0);
       }
     }
@@ -200,7 +171,7 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(const unsigned short
     const float i0 = __shfl(inv, 4 * g + r, 64), i1 = __shfl(inv, 4 * g + r + 1, 64);
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt) {
-      const unsigned int w = al_pack(o[dt][r] * i0, o[dt][r + 1] * i1);
+      const unsigned int w = pack_bf16(o[dt][r] * i0, o[dt][r + 1] * i1);
       Ow[(4 * g + r) * LD + 16 * dt + li] = (unsigned short)(w & 0xffffu);
       Ow[(4 * g + r + 1) * LD + 16 * dt + li] = (unsigned short)(w >> 16);
     }
@@ -285,27 +256,27 @@ __global__ __launch_bounds__(256) void attn_long_qmean_kernel(const unsigned sho
   const size_t row = (size_t)3 * H * HD;
   const unsigned short* base = qkv + (size_t)b * T * row + (size_t)h * HD;
   const float* lrow = lse + (size_t)bh * T;
-  al_bf16x8 kf[NDS];
+  bf16x8 kf[NDS];
 #pragma unroll
   for (int ks = 0; ks < NDS; ++ks) {
     uint4 v = make_uint4(0, 0, 0, 0);
     if (k0 + li < T && 32 * ks + 8 * g < HD)
       v = *reinterpret_cast<const uint4*>(base + (size_t)(k0 + li) * row + (size_t)H * HD + 32 * ks + 8 * g);
-    kf[ks] = *reinterpret_cast<const al_bf16x8*>(&v);
+    kf[ks] = *reinterpret_cast<const bf16x8*>(&v);
   }
   const float sl2 = scale * AL_LOG2E;
   float csum[4] = {0.f, 0.f, 0.f, 0.f};
   for (int qs = 0; qs < T; qs += 16) {
     const int q = qs + li;
-    al_bf16x8 qf[NDS];
+    bf16x8 qf[NDS];
 #pragma unroll
     for (int ks = 0; ks < NDS; ++ks) {
       uint4 v = make_uint4(0, 0, 0, 0);
       if (q < T && 32 * ks + 8 * g < HD) v = *reinterpret_cast<const uint4*>(base + (size_t)q * row + 32 * ks + 8 * g);
-      qf[ks] = *reinterpret_cast<const al_bf16x8*>(&v);
+      qf[ks] = *reinterpret_cast<const bf16x8*>(&v);
     }
     const float nl = (q < T) ? lrow[q] * AL_LOG2E : 0.f;
-    al_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < NDS; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[ks], qf[ks], acc, 0, 0, 0);
     // acc[r]: key k0 + 4 g + r, query q
@@ -396,7 +367,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   float* mydq = dqs + wave * 32 * QLD;
 
   // ---- this wave's 32 keys: B operands of S / dP (key kbase + 16 t + li, d = 32 ks + 8 g ..) and of dQ = dS K
-  al_bf16x8 kb[2][NDS], vb[2][NDS], kt[NDT];
+  bf16x8 kb[2][NDS], vb[2][NDS], kt[NDT];
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -408,8 +379,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         kv = *reinterpret_cast<const uint4*>(p + (size_t)H * HD);
         vv = *reinterpret_cast<const uint4*>(p + (size_t)2 * H * HD);
       }
-      kb[t][ks] = *reinterpret_cast<const al_bf16x8*>(&kv);
-      vb[t][ks] = *reinterpret_cast<const al_bf16x8*>(&vv);
+      kb[t][ks] = *reinterpret_cast<const bf16x8*>(&kv);
+      vb[t][ks] = *reinterpret_cast<const bf16x8*>(&vv);
     }
   for (int idx = lane; idx < 32 * NCH; idx += 64) {
     const int r = idx / NCH, c8 = idx - r * NCH;
@@ -420,15 +391,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   }
   __builtin_amdgcn_s_waitcnt(0xc07f);                // lgkmcnt(0): a wave's LDS operations complete in order
 #pragma unroll
-  for (int dt = 0; dt < NDT; ++dt) kt[dt] = al_tr_cons(mytile, LD, 8 * g, 16 * dt, lane);
+  for (int dt = 0; dt < NDT; ++dt) kt[dt] = tr_cons(mytile, LD, 8 * g, 16 * dt, lane);
   __builtin_amdgcn_s_waitcnt(0xc07f);
-  al_f32x4 dkt[2][NDT], dvt[2][NDT];                 // dK^T / dV^T [key tile][d tile]: rows d = 16 dt + 4 g + r
+  f32x4 dkt[2][NDT], dvt[2][NDT];                 // dK^T / dV^T [key tile][d tile]: rows d = 16 dt + 4 g + r
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt) {
-      dkt[t][dt] = (al_f32x4){0.f, 0.f, 0.f, 0.f};
-      dvt[t][dt] = (al_f32x4){0.f, 0.f, 0.f, 0.f};
+      dkt[t][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      dvt[t][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
 
   // ---- 32-query slices: Q / dO chunks and the row constants prefetched one slice ahead
@@ -472,34 +443,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     }
     lds_barrier();
     if (sl + 1 < nslices) load_slice(q0 + 32);
-    al_f32x4 dq[2][NDT];
+    f32x4 dq[2][NDT];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int dt = 0; dt < NDT; ++dt) dq[t][dt] = (al_f32x4){0.f, 0.f, 0.f, 0.f};
+      for (int dt = 0; dt < NDT; ++dt) dq[t][dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     if (active) {
       // A operands (row reads): query 16 t + li, d = 32 ks + 8 g ..
-      al_bf16x8 qa[2][NDS], da[2][NDS];
+      bf16x8 qa[2][NDS], da[2][NDS];
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int ks = 0; ks < NDS; ++ks) {
-          qa[t][ks] = *reinterpret_cast<const al_bf16x8*>(Qs + (16 * t + li) * LD + 32 * ks + 8 * g);
-          da[t][ks] = *reinterpret_cast<const al_bf16x8*>(dOs + (16 * t + li) * LD + 32 * ks + 8 * g);
+          qa[t][ks] = *reinterpret_cast<const bf16x8*>(Qs + (16 * t + li) * LD + 32 * ks + 8 * g);
+          da[t][ks] = *reinterpret_cast<const bf16x8*>(dOs + (16 * t + li) * LD + 32 * ks + 8 * g);
         }
-      al_f32x4 c_lse[2], c_del[2];
+      f32x4 c_lse[2], c_del[2];
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        c_lse[t] = *reinterpret_cast<const al_f32x4*>(nlse + 16 * t + 4 * g);
-        c_del[t] = *reinterpret_cast<const al_f32x4*>(ndel + 16 * t + 4 * g);
+        c_lse[t] = *reinterpret_cast<const f32x4*>(nlse + 16 * t + 4 * g);
+        c_del[t] = *reinterpret_cast<const f32x4*>(ndel + 16 * t + 4 * g);
       }
       // S' and dP' of the 32 x 32 block [query tile tq][key tile tk]: rows = queries 4 g + r, column = key li
-      al_f32x4 s[2][2], dp[2][2];
+      f32x4 s[2][2], dp[2][2];
 #pragma unroll
       for (int tq = 0; tq < 2; ++tq)
 #pragma unroll
         for (int tk = 0; tk < 2; ++tk) {
-          al_f32x4 a = c_lse[tq], d = c_del[tq];
+          f32x4 a = c_lse[tq], d = c_del[tq];
 #pragma unroll
           for (int ks = 0; ks < NDS; ++ks) {
             a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[tq][ks], kb[tk][ks], a, 0, 0, 0);
@@ -509,13 +480,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
           dp[tq][tk] = d;
         }
       // transposed operands (column reads): d = 16 dt + li, queries {4 g + r} and {16 + 4 g + r}
-      al_bf16x8 qT[NDT], dT[NDT];
+      bf16x8 qT[NDT], dT[NDT];
 #pragma unroll
       for (int dt = 0; dt < NDT; ++dt) {
-        qT[dt] = al_tr_split(Qs, LD, 4 * g, 16 * dt, lane);
-        dT[dt] = al_tr_split(dOs, LD, 4 * g, 16 * dt, lane);
+        qT[dt] = tr_split(Qs, LD, 4 * g, 16 * dt, lane);
+        dT[dt] = tr_split(dOs, LD, 4 * g, 16 * dt, lane);
       }
-      al_bf16x8 pB[2], sB[2];
+      bf16x8 pB[2], sB[2];
 #pragma unroll
       for (int tk = 0; tk < 2; ++tk) {
         unsigned int pw[4], sw[4];
@@ -527,10 +498,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             p[r] = __builtin_amdgcn_exp2f(c2 * s[tq][tk][r]);
             ds[r] = scale * p[r] * dp[tq][tk][r];
           }
-          pw[2 * tq] = al_pack(p[0], p[1]);
-          pw[2 * tq + 1] = al_pack(p[2], p[3]);
-          sw[2 * tq] = al_pack(ds[0], ds[1]);
-          sw[2 * tq + 1] = al_pack(ds[2], ds[3]);
+          pw[2 * tq] = pack_bf16(p[0], p[1]);
+          pw[2 * tq + 1] = pack_bf16(p[2], p[3]);
+          sw[2 * tq] = pack_bf16(ds[0], ds[1]);
+          sw[2 * tq + 1] = pack_bf16(ds[2], ds[3]);
           // dS tile for dQ: row = query 16 tq + 4 g + r, column = key 16 tk + li
 #pragma unroll
           for (int r = 0; r < 4; r += 2) {
@@ -539,8 +510,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             mytile[(16 * tq + 4 * g + r + 1) * SLD + 16 * tk + li] = (unsigned short)(w >> 16);
           }
         }
-        pB[tk] = *reinterpret_cast<const al_bf16x8*>(pw);
-        sB[tk] = *reinterpret_cast<const al_bf16x8*>(sw);
+        pB[tk] = *reinterpret_cast<const bf16x8*>(pw);
+        sB[tk] = *reinterpret_cast<const bf16x8*>(sw);
       }
       // dV^T += dO^T P,  dK^T += Q^T dS
 #pragma unroll
@@ -554,7 +525,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       __builtin_amdgcn_s_waitcnt(0xc07f);
 #pragma unroll
       for (int tq = 0; tq < 2; ++tq) {
-        const al_bf16x8 sa = *reinterpret_cast<const al_bf16x8*>(mytile + (16 * tq + li) * SLD + 8 * g);
+        const bf16x8 sa = *reinterpret_cast<const bf16x8*>(mytile + (16 * tq + li) * SLD + 8 * g);
 #pragma unroll
         for (int dt = 0; dt < NDT; ++dt)
           dq[tq][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(sa, kt[dt], dq[tq][dt], 0, 0, 0);
@@ -601,10 +572,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
         for (int dt = 0; dt < NDT; ++dt) {
           uint2 wk, wv;
-          wk.x = al_pack(dkt[tk][dt][0], dkt[tk][dt][1]);
-          wk.y = al_pack(dkt[tk][dt][2], dkt[tk][dt][3]);
-          wv.x = al_pack(dvt[tk][dt][0], dvt[tk][dt][1]);
-          wv.y = al_pack(dvt[tk][dt][2], dvt[tk][dt][3]);
+          wk.x = pack_bf16(dkt[tk][dt][0], dkt[tk][dt][1]);
+          wk.y = pack_bf16(dkt[tk][dt][2], dkt[tk][dt][3]);
+          wv.x = pack_bf16(dvt[tk][dt][0], dvt[tk][dt][1]);
+          wv.y = pack_bf16(dvt[tk][dt][2], dvt[tk][dt][3]);
           *reinterpret_cast<uint2*>(pk + 16 * dt) = wk;
           *reinterpret_cast<uint2*>(pv + 16 * dt) = wv;
         }
@@ -635,10 +606,10 @@ __global__ __launch_bounds__(256) void attn_long_dq_kernel(const float* __restri
       c.x += v.x; c.y += v.y; c.z += v.z; c.w += v.w;
     }
     uint4 w;
-    w.x = al_pack(a.x, a.y);
-    w.y = al_pack(a.z, a.w);
-    w.z = al_pack(c.x, c.y);
-    w.w = al_pack(c.z, c.w);
+    w.x = pack_bf16(a.x, a.y);
+    w.y = pack_bf16(a.z, a.w);
+    w.z = pack_bf16(c.x, c.y);
+    w.w = pack_bf16(c.z, c.w);
     *reinterpret_cast<uint4*>(dqkv + (((size_t)b * T + t) * 3 * H + h) * HD + 8 * c8) = w;
   }
 }

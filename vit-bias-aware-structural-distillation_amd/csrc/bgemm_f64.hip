@@ -10,11 +10,10 @@
 // 2x2 MFMA tiles), K chunks of 16 staged through LDS in fp64, k-major so the
 // A/B fragments (one f64 per lane: A[i = lane&15][k = lane>>4]) are read from
 // consecutive addresses.
-#include "basd_common.h"
+#include "basd_frag.h"
 
 namespace basd {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 constexpr int BT = 64;      // tile
 constexpr int BK = 16;      // K chunk
 constexpr int BLD = BT + 2; // LDS row stride (doubles)

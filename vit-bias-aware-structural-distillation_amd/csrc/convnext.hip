@@ -11,26 +11,9 @@
 //                         downsample layers): pure data movement.
 //
 // None of them is matrix-core work.  A lane owns 8 contiguous channels (one 16-byte load) everywhere.
-#include "basd_common.h"
+#include "basd_frag.h"
 
 namespace basd {
-
-__device__ __forceinline__ void cn_unpack8(const uint4& v, float (&f)[8]) {
-  const unsigned int w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f[2 * i] = __uint_as_float(w[i] << 16);
-    f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-  }
-}
-__device__ __forceinline__ unsigned int cn_pack2(float a, float b) {
-  __hip_bfloat16 x = __float2bfloat16(a), y = __float2bfloat16(b);    // round to nearest even
-  return (unsigned int)(*reinterpret_cast<unsigned short*>(&x)) |
-         ((unsigned int)(*reinterpret_cast<unsigned short*>(&y)) << 16);
-}
-__device__ __forceinline__ uint4 cn_pack8(const float (&f)[8]) {
-  return make_uint4(cn_pack2(f[0], f[1]), cn_pack2(f[2], f[3]), cn_pack2(f[4], f[5]), cn_pack2(f[6], f[7]));
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Depthwise 7 x 7 + LayerNorm.
@@ -106,11 +89,11 @@ __global__ __launch_bounds__(DW_THREADS) void dwconv7_ln_kernel(
       float wf[7][8];
 #pragma unroll
       for (int dx = 0; dx < 7; ++dx)
-        cn_unpack8(*reinterpret_cast<const uint4*>(w49 + (size_t)(dy * 7 + dx) * C + lc * 8), wf[dx]);
+        unpack8(*reinterpret_cast<const uint4*>(w49 + (size_t)(dy * 7 + dx) * C + lc * 8), wf[dx]);
 #pragma unroll
       for (int j = 0; j < DW_S + 6; ++j) {
         float xf[8];
-        cn_unpack8(raw[j], xf);
+        unpack8(raw[j], xf);
 #pragma unroll
         for (int s = 0; s < DW_S; ++s) {
           const int dx = j - s;                                        // compile-time after unrolling
@@ -173,7 +156,7 @@ __global__ __launch_bounds__(DW_THREADS) void dwconv7_ln_kernel(
 #pragma unroll
     for (int i = 0; i < 8; ++i) o[i] = acc[s][i] * rstd * gv[i] + ev[i];
     unsigned short* yp = yrow + (int64_t)(w0 + s) * ld_out;
-    *reinterpret_cast<uint4*>(yp + lc * 8) = cn_pack8(o);
+    *reinterpret_cast<uint4*>(yp + lc * 8) = pack8(o);
     if (lc < npad) *reinterpret_cast<uint4*>(yp + C + lc * 8) = make_uint4(0, 0, 0, 0);
   }
 }
@@ -208,14 +191,14 @@ __global__ __launch_bounds__(256) void grn_stats_kernel(const unsigned short* __
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         float f[8];
-        cn_unpack8(v[u], f);
+        unpack8(v[u], f);
 #pragma unroll
         for (int i = 0; i < 8; ++i) s[i] = fmaf(f[i], f[i], s[i]);
       }
     }
     for (; r < r1; r += RS) {
       float f[8];
-      cn_unpack8(*reinterpret_cast<const uint4*>(p + (int64_t)r * C), f);
+      unpack8(*reinterpret_cast<const uint4*>(p + (int64_t)r * C), f);
 #pragma unroll
       for (int i = 0; i < 8; ++i) s[i] = fmaf(f[i], f[i], s[i]);
     }
@@ -266,10 +249,10 @@ __global__ __launch_bounds__(256) void grn_apply_kernel(unsigned short* __restri
     const int c = (v % c8) * 8;
     uint4* p = reinterpret_cast<uint4*>(base + (int64_t)v * 8);
     float f[8];
-    cn_unpack8(*p, f);
+    unpack8(*p, f);
 #pragma unroll
     for (int i = 0; i < 8; ++i) f[i] = f[i] + fmaf(a[c + i], f[i], bsh[c + i]);
-    *p = cn_pack8(f);
+    *p = pack8(f);
   }
 }
 

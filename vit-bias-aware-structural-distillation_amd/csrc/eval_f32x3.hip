@@ -16,22 +16,14 @@
 //                         fp32 logits (no bf16 rounding), fp32 softmax, P split against V split; T <= 272
 //   attn_f32x3_long_kernel  the same arithmetic tiled over key blocks of 128 with an online softmax: 1 <= T <= 1024
 //   ln_f32_kernel         s = residual + gamma_ls x (optional), y = LayerNorm(s): fp32 s, fp32 y and / or the image
-#include "basd_common.h"
+#include "basd_frag.h"
 
 namespace basd {
 
-typedef float ev_f32x4 __attribute__((ext_vector_type(4)));
-typedef short ev_bf16x8 __attribute__((ext_vector_type(8)));
-typedef short ev_v4s __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) ev_v4s ev_lds_v4s;
-
-__device__ __forceinline__ unsigned short ev_bf16(float v) { return __builtin_bit_cast(unsigned short, (__bf16)v); }
-__device__ __forceinline__ float ev_f32(unsigned short b) { return __uint_as_float(((unsigned int)b) << 16); }
-
 // (hi, lo) of one fp32 value
 __device__ __forceinline__ void ev_split(float v, unsigned short& hi, unsigned short& lo) {
-  hi = ev_bf16(v);
-  lo = ev_bf16(v - ev_f32(hi));
+  hi = f32_to_bf16_bits(v);
+  lo = f32_to_bf16_bits(v - bf16_bits_to_f32(hi));
 }
 
 // hi / lo halves of four values as two 8-byte words
@@ -136,11 +128,11 @@ __global__ __launch_bounds__(256) void gemm_f32x3_kernel(const unsigned short* _
     pre[4 * i + 3] = eg_keep(*reinterpret_cast<const uint4*>(xp + kp), okx);                     \
   }
 
-  ev_f32x4 acc[4][4];
+  f32x4 acc[4][4];
 #pragma unroll
   for (int a = 0; a < 4; ++a)
 #pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = (ev_f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int b = 0; b < 4; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   const int nk = kp / 32;
   EG_LOAD(0)
@@ -157,14 +149,14 @@ __global__ __launch_bounds__(256) void gemm_f32x3_kernel(const unsigned short* _
     if (t + 1 < nk) {
       EG_LOAD(32 * (t + 1))
     }
-    ev_bf16x8 wh[4], wl[4], xh[4], xl[4];
+    bf16x8 wh[4], wl[4], xh[4], xl[4];
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
       const int rw = (wn * 64 + a * 16 + li) * EG_LD + 8 * g, rx = (wm * 64 + a * 16 + li) * EG_LD + 8 * g;
-      wh[a] = *reinterpret_cast<const ev_bf16x8*>(sm + rw);
-      wl[a] = *reinterpret_cast<const ev_bf16x8*>(sm + EG_TILE + rw);
-      xh[a] = *reinterpret_cast<const ev_bf16x8*>(sm + 2 * EG_TILE + rx);
-      xl[a] = *reinterpret_cast<const ev_bf16x8*>(sm + 3 * EG_TILE + rx);
+      wh[a] = *reinterpret_cast<const bf16x8*>(sm + rw);
+      wl[a] = *reinterpret_cast<const bf16x8*>(sm + EG_TILE + rw);
+      xh[a] = *reinterpret_cast<const bf16x8*>(sm + 2 * EG_TILE + rx);
+      xl[a] = *reinterpret_cast<const bf16x8*>(sm + 3 * EG_TILE + rx);
     }
 #pragma unroll
     for (int a = 0; a < 4; ++a)
@@ -254,7 +246,7 @@ __global__ __launch_bounds__(512) void attn_f32x3_kernel(const float* __restrict
 
   stage(1);
   // Q fragments: query q0 + li, d = 32 ks + 8 g .. + 7
-  ev_bf16x8 qh[NDS], ql[NDS];
+  bf16x8 qh[NDS], ql[NDS];
 #pragma unroll
   for (int ks = 0; ks < NDS; ++ks) {
     float v[8];
@@ -275,16 +267,16 @@ __global__ __launch_bounds__(512) void attn_f32x3_kernel(const float* __restrict
   }
   __syncthreads();
 
-  ev_f32x4 s[NKT];
+  f32x4 s[NKT];
   if (active) {
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt) {
-      ev_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < NDS; ++ks) {
         const int off = (16 * kt + li) * LD + 32 * ks + 8 * g;
-        const ev_bf16x8 kh = *reinterpret_cast<const ev_bf16x8*>(Sh + off);
-        const ev_bf16x8 kl = *reinterpret_cast<const ev_bf16x8*>(Sl + off);
+        const bf16x8 kh = *reinterpret_cast<const bf16x8*>(Sh + off);
+        const bf16x8 kl = *reinterpret_cast<const bf16x8*>(Sl + off);
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kl, qh[ks], acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kh, ql[ks], acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kh, qh[ks], acc, 0, 0, 0);
@@ -323,9 +315,9 @@ __global__ __launch_bounds__(512) void attn_f32x3_kernel(const float* __restrict
   __syncthreads();                                   // V staged
   if (!active) return;
 
-  ev_f32x4 o[NDT];
+  f32x4 o[NDT];
 #pragma unroll
-  for (int dt = 0; dt < NDT; ++dt) o[dt] = (ev_f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int dt = 0; dt < NDT; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int ks = 0; ks < NKS; ++ks) {
     float pv[8];
@@ -334,7 +326,7 @@ __global__ __launch_bounds__(512) void attn_f32x3_kernel(const float* __restrict
       pv[r] = s[2 * ks][r];
       pv[4 + r] = (2 * ks + 1 < NKT) ? s[(2 * ks + 1 < NKT) ? 2 * ks + 1 : 0][r] : 0.f;
     }
-    ev_bf16x8 ph, pl;
+    bf16x8 ph, pl;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       unsigned short hi, lo;
@@ -342,16 +334,17 @@ __global__ __launch_bounds__(512) void attn_f32x3_kernel(const float* __restrict
       ph[e] = (short)hi;
       pl[e] = (short)lo;
     }
+    // tr_split of basd_frag.h on both planes, written out on the kernel's own li (the helper changes the generated code)
     const int qq = li >> 2, pp = li & 3;
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt) {
       const int off = (32 * ks + 4 * g + qq) * LD + 16 * dt + 4 * pp;
-      const ev_v4s h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ev_lds_v4s*)(Sh + off));
-      const ev_v4s h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ev_lds_v4s*)(Sh + off + 16 * LD));
-      const ev_v4s l0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ev_lds_v4s*)(Sl + off));
-      const ev_v4s l1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ev_lds_v4s*)(Sl + off + 16 * LD));
-      const ev_bf16x8 vh = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-      const ev_bf16x8 vl = {l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
+      const v4s h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(Sh + off));
+      const v4s h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(Sh + off + 16 * LD));
+      const v4s l0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(Sl + off));
+      const v4s l1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(Sl + off + 16 * LD));
+      const bf16x8 vh = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+      const bf16x8 vl = {l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
       o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pl, vh, o[dt], 0, 0, 0);
       o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ph, vl, o[dt], 0, 0, 0);
       o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ph, vh, o[dt], 0, 0, 0);
@@ -435,7 +428,7 @@ __global__ __launch_bounds__(512) void attn_f32x3_long_kernel(const float* __res
     }
   }
   // Q fragments: query q0 + li, d = 32 ks + 8 g .. + 7
-  ev_bf16x8 qh[NDS], ql[NDS];
+  bf16x8 qh[NDS], ql[NDS];
 #pragma unroll
   for (int ks = 0; ks < NDS; ++ks) {
     float v[8];
@@ -456,9 +449,9 @@ __global__ __launch_bounds__(512) void attn_f32x3_long_kernel(const float* __res
   }
 
   float m_run = -3.0e38f, l_run = 0.f;               // of query q0 + li (the same value in the four lane groups)
-  ev_f32x4 o[NDT];
+  f32x4 o[NDT];
 #pragma unroll
-  for (int dt = 0; dt < NDT; ++dt) o[dt] = (ev_f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int dt = 0; dt < NDT; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
   const int nblocks = (T + KB - 1) / KB;
   for (int j = 0; j < nblocks; ++j) {
     const int k0 = j * KB;
@@ -482,15 +475,15 @@ __global__ __launch_bounds__(512) void attn_f32x3_long_kernel(const float* __res
     if (!active) continue;
 
     // ---- S^T of the 8 key tiles
-    ev_f32x4 s[NKT];
+    f32x4 s[NKT];
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt) {
-      ev_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < NDS; ++ks) {
         const int off = (16 * kt + li) * LD + 32 * ks + 8 * g;
-        const ev_bf16x8 kh = *reinterpret_cast<const ev_bf16x8*>(Kh + off);
-        const ev_bf16x8 kl = *reinterpret_cast<const ev_bf16x8*>(Kl + off);
+        const bf16x8 kh = *reinterpret_cast<const bf16x8*>(Kh + off);
+        const bf16x8 kl = *reinterpret_cast<const bf16x8*>(Kl + off);
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kl, qh[ks], acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kh, ql[ks], acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kh, qh[ks], acc, 0, 0, 0);
@@ -536,7 +529,7 @@ __global__ __launch_bounds__(512) void attn_f32x3_long_kernel(const float* __res
     // ---- O += P V
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) {
-      ev_bf16x8 ph, pl;
+      bf16x8 ph, pl;
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         unsigned short hi, lo;
@@ -544,16 +537,17 @@ __global__ __launch_bounds__(512) void attn_f32x3_long_kernel(const float* __res
         ph[e] = (short)hi;
         pl[e] = (short)lo;
       }
+      // tr_split of basd_frag.h on both planes, written out on the kernel's own li (the helper changes the generated code)
       const int qq = li >> 2, pp = li & 3;
 #pragma unroll
       for (int dt = 0; dt < NDT; ++dt) {
         const int off = (32 * ks + 4 * g + qq) * LD + 16 * dt + 4 * pp;
-        const ev_v4s h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ev_lds_v4s*)(Vh + off));
-        const ev_v4s h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ev_lds_v4s*)(Vh + off + 16 * LD));
-        const ev_v4s l0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ev_lds_v4s*)(Vl + off));
-        const ev_v4s l1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ev_lds_v4s*)(Vl + off + 16 * LD));
-        const ev_bf16x8 vh = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-        const ev_bf16x8 vl = {l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
+        const v4s h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(Vh + off));
+        const v4s h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(Vh + off + 16 * LD));
+        const v4s l0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(Vl + off));
+        const v4s l1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(Vl + off + 16 * LD));
+        const bf16x8 vh = {h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+        const bf16x8 vl = {l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
         o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pl, vh, o[dt], 0, 0, 0);
         o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ph, vl, o[dt], 0, 0, 0);
         o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ph, vh, o[dt], 0, 0, 0);

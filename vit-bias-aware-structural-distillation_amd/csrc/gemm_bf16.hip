@@ -19,14 +19,9 @@
 // bf16 rounding of the output); its derivative in the backward epilogue: the exact form via Abramowitz-Stegun 7.1.26;
 // fp32 accumulation, one rounding to bf16 at the store.
 #include <type_traits>
-#include "basd_common.h"
+#include "basd_frag.h"
 
 namespace basd {
-
-typedef float gf32x4 __attribute__((ext_vector_type(4)));
-typedef short gbf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short gu16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int gu32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int GBM = 256;   // tile rows (m)
 constexpr int GBK = 64;    // K step
@@ -88,18 +83,13 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
   return fmaf(x * 0.3989422804014327f, e, 0.5f * (1.0f + copysignf(erf_abs, x)));
 }
 
-__device__ __forceinline__ unsigned short f32_to_bf16_bits(float v) {
-  return __builtin_bit_cast(unsigned short, (__bf16)v);
-}
-
-
 // Epilogue shared by both kernels.  The accumulator tile of a wave is [n][m] with 4 consecutive n per lane: stored
 // straight from registers that is an 8-byte store per (lane, tile), 16 rows x 32 B per wave instruction -- partial
 // lines, 18 us per 256 x 256 tile (as much as 13 K steps).  Instead every wave parks its 128 x (BN / 4) bf16 results
 // in a private LDS region (row stride + 16 B against bank conflicts; the operand ring is dead by now) and writes
 // them out as 16 bytes per lane, whole 128-byte (BN = 256) row segments per 8 lanes.
 template <int BN, int NT, int EPI>
-__device__ __forceinline__ void gemm_epilogue(gf32x4 (&acc)[NT][8], unsigned char* lds, const unsigned short* bias,
+__device__ __forceinline__ void gemm_epilogue(f32x4 (&acc)[NT][8], unsigned char* lds, const unsigned short* bias,
                                               unsigned short* aux, unsigned short* Y, int M, int N, int m0, int n0,
                                               int wm, int wn, int lane, int wave) {
   constexpr int WN = BN / 4;                       // columns of a wave
@@ -134,14 +124,14 @@ __device__ __forceinline__ void gemm_epilogue(gf32x4 (&acc)[NT][8], unsigned cha
     const int nl = i * 16 + 4 * (lane >> 4);       // local column of this lane's 4 values
     float bv[4] = {0.f, 0.f, 0.f, 0.f};
     if ((EPI == 1 || EPI == 2 || EPI == 3) && bias != nullptr) {
-      const gu16x4 b4 = *reinterpret_cast<const gu16x4*>(bias + n0 + wn * WN + nl);
+      const u16x4 b4 = *reinterpret_cast<const u16x4*>(bias + n0 + wn * WN + nl);
 #pragma unroll
       for (int r = 0; r < 4; ++r) bv[r] = bf16_bits_to_f32(b4[r]);
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      gu16x4* cell = reinterpret_cast<gu16x4*>(region + (j * 16 + (lane & 15)) * ROWB + nl * 2);
-      gu16x4 o, pre;
+      u16x4* cell = reinterpret_cast<u16x4*>(region + (j * 16 + (lane & 15)) * ROWB + nl * 2);
+      u16x4 o, pre;
       if (EPI == 4) pre = *cell;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -160,8 +150,8 @@ __device__ __forceinline__ void gemm_epilogue(gf32x4 (&acc)[NT][8], unsigned cha
       const int nl = i * 16 + 4 * (lane >> 4);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        gu16x4* cell = reinterpret_cast<gu16x4*>(region + (j * 16 + (lane & 15)) * ROWB + nl * 2);
-        gu16x4 p = *cell;
+        u16x4* cell = reinterpret_cast<u16x4*>(region + (j * 16 + (lane & 15)) * ROWB + nl * 2);
+        u16x4 p = *cell;
 #pragma unroll
         for (int r = 0; r < 4; ++r) p[r] = f32_to_bf16_bits(gelu_fwd(bf16_bits_to_f32(p[r])));
         *cell = p;
@@ -221,11 +211,11 @@ __global__ __launch_bounds__(512) void gemm_bf16_nt_kernel(const unsigned short*
                                      (void __attribute__((address_space(3)))*)dst, 16, 0, 0);
   };
 
-  gf32x4 acc[NT][8];
+  f32x4 acc[NT][8];
 #pragma unroll
   for (int i = 0; i < NT; ++i)
 #pragma unroll
-    for (int j = 0; j < 8; ++j) acc[i][j] = (gf32x4){0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < 8; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   // fragment read offset inside a sub-tile: row lane & 15, 16-byte k chunk lane >> 4
   const int frag_off = gemm_swz((lane & 15) * 64 + (lane >> 4) * 16);
@@ -250,13 +240,13 @@ __global__ __launch_bounds__(512) void gemm_bf16_nt_kernel(const unsigned short*
     // whose matrix work is 1024; spread out they hide behind the MFMA groups of the SIMD's other wave.
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
-      gbf16x8 wf[NT], xf[8];
+      bf16x8 wf[NT], xf[8];
 #pragma unroll
       for (int i = 0; i < NT; ++i)
-        wf[i] = *reinterpret_cast<const gbf16x8*>(base + (b_sub0 + i * 2 + kb) * 1024);
+        wf[i] = *reinterpret_cast<const bf16x8*>(base + (b_sub0 + i * 2 + kb) * 1024);
 #pragma unroll
       for (int j = 0; j < 8; ++j)
-        xf[j] = *reinterpret_cast<const gbf16x8*>(base + (a_sub0 + j * 2 + kb) * 1024);
+        xf[j] = *reinterpret_cast<const bf16x8*>(base + (a_sub0 + j * 2 + kb) * 1024);
 #pragma unroll
       for (int i = 0; i < NT; ++i) {
         // group g of the step's 2 NT groups issues the pieces [g NPIECE / G, (g + 1) NPIECE / G): one each at
@@ -328,11 +318,11 @@ __global__ __launch_bounds__(512) void gemm_bf16_ring_kernel(const unsigned shor
                                      (void __attribute__((address_space(3)))*)dst, 16, 0, 0);
   };
 
-  gf32x4 acc[NT][8];
+  f32x4 acc[NT][8];
 #pragma unroll
   for (int i = 0; i < NT; ++i)
 #pragma unroll
-    for (int j = 0; j < 8; ++j) acc[i][j] = (gf32x4){0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < 8; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
   const int frag_off = gemm_swz((lane & 15) * 64 + (lane >> 4) * 16);
   const int a_sub0 = (wm * 8) * 2, b_sub0 = (wn * NT) * 2;
 
@@ -351,11 +341,11 @@ __global__ __launch_bounds__(512) void gemm_bf16_ring_kernel(const unsigned shor
     const int u0 = 2 * t + 3;
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
-      gbf16x8 wf[NT], xf[8];
+      bf16x8 wf[NT], xf[8];
 #pragma unroll
-      for (int i = 0; i < NT; ++i) wf[i] = *reinterpret_cast<const gbf16x8*>(bbase + (b_sub0 + i * 2 + kb) * 1024);
+      for (int i = 0; i < NT; ++i) wf[i] = *reinterpret_cast<const bf16x8*>(bbase + (b_sub0 + i * 2 + kb) * 1024);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) xf[j] = *reinterpret_cast<const gbf16x8*>(abase + (a_sub0 + j * 2 + kb) * 1024);
+      for (int j = 0; j < 8; ++j) xf[j] = *reinterpret_cast<const bf16x8*>(abase + (a_sub0 + j * 2 + kb) * 1024);
 #pragma unroll
       for (int i = 0; i < NT; ++i) {
         __builtin_amdgcn_sched_barrier(0);
@@ -406,7 +396,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_ring_kernel(const unsigned shor
 // EPI 5: fp32 output of pitch N, columns >= N are not stored (the weight matrix is padded to the tile width, the output
 // is not): two 16-byte stores per 8 columns.
 template <int EPI>
-__device__ __forceinline__ void gemm_epilogue_direct(gf32x4 (&acc)[4][8], const unsigned short* bias,
+__device__ __forceinline__ void gemm_epilogue_direct(f32x4 (&acc)[4][8], const unsigned short* bias,
                                                      unsigned short* aux, unsigned short* Y, int M, int N, int row0,
                                                      int col0, int lane) {
   typedef unsigned int eu32x2 __attribute__((ext_vector_type(2)));
@@ -434,9 +424,9 @@ __device__ __forceinline__ void gemm_epilogue_direct(gf32x4 (&acc)[4][8], const 
           float* dst = Y32 + (size_t)row * N + col;
 #pragma unroll
           for (int k = 0; k < 2; ++k)
-            __builtin_nontemporal_store((gu32x4){__float_as_uint(v[2 * h + k][0]), __float_as_uint(v[2 * h + k][1]),
+            __builtin_nontemporal_store((u32x4){__float_as_uint(v[2 * h + k][0]), __float_as_uint(v[2 * h + k][1]),
                                                  __float_as_uint(v[2 * h + k][2]), __float_as_uint(v[2 * h + k][3])},
-                                        reinterpret_cast<gu32x4*>(dst + 4 * k));
+                                        reinterpret_cast<u32x4*>(dst + 4 * k));
         }
       }
     }
@@ -459,9 +449,6 @@ __device__ __forceinline__ void gemm_epilogue_direct(gf32x4 (&acc)[4][8], const 
       }
     }
   }
-  auto pack2 = [](float lo, float hi) -> unsigned int {
-    return (unsigned int)f32_to_bf16_bits(lo) | ((unsigned int)f32_to_bf16_bits(hi) << 16);
-  };
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     float v[4][4];
@@ -496,17 +483,18 @@ __device__ __forceinline__ void gemm_epilogue_direct(gf32x4 (&acc)[4][8], const 
             f[2 * k + 1] *= gelu_erf_grad(__uint_as_float(w4[k] & 0xffff0000u));
           }
         }
-        uint4 o = make_uint4(pack2(f[0], f[1]), pack2(f[2], f[3]), pack2(f[4], f[5]), pack2(f[6], f[7]));
+        uint4 o = make_uint4(pack_bf16_bits(f[0], f[1]), pack_bf16_bits(f[2], f[3]), pack_bf16_bits(f[4], f[5]),
+                             pack_bf16_bits(f[6], f[7]));
         if (EPI == 3) {
-          __builtin_nontemporal_store((gu32x4){o.x, o.y, o.z, o.w}, reinterpret_cast<gu32x4*>(aux + off + h * 32));   // pre-activation, rounded
+          __builtin_nontemporal_store((u32x4){o.x, o.y, o.z, o.w}, reinterpret_cast<u32x4*>(aux + off + h * 32));   // pre-activation, rounded
           const unsigned int w4[4] = {o.x, o.y, o.z, o.w};
           unsigned int g4[4];
 #pragma unroll
           for (int k = 0; k < 4; ++k)
-            g4[k] = pack2(gelu_fwd(__uint_as_float(w4[k] << 16)), gelu_fwd(__uint_as_float(w4[k] & 0xffff0000u)));
+            g4[k] = pack_bf16_bits(gelu_fwd(__uint_as_float(w4[k] << 16)), gelu_fwd(__uint_as_float(w4[k] & 0xffff0000u)));
           o = make_uint4(g4[0], g4[1], g4[2], g4[3]);
         }
-        __builtin_nontemporal_store((gu32x4){o.x, o.y, o.z, o.w}, reinterpret_cast<gu32x4*>(Y + off + h * 32));
+        __builtin_nontemporal_store((u32x4){o.x, o.y, o.z, o.w}, reinterpret_cast<u32x4*>(Y + off + h * 32));
       }
     }
   }
@@ -623,7 +611,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pring_kernel(const unsigned sho
   };
   auto wrap = [](int s) { return s >= NSLOT ? s - NSLOT : s; };
 
-  gf32x4 acc[NT][8];
+  f32x4 acc[NT][8];
   const int frag_off = gemm_swz((lane & 15) * 64 + (lane >> 4) * 16);
   const int a_sub0 = (wm * 8) * 2, b_sub0 = (wn * NT) * 2;
 
@@ -640,19 +628,19 @@ __global__ __launch_bounds__(512) void gemm_bf16_pring_kernel(const unsigned sho
   //           step's A slot, free since the barrier)
   // ONE instance of this code in the kernel (a single loop over segments and K steps, every step issues): with peeled
   // variants the accumulators went through 128-register phi webs and spilled.
-  gbf16x8 xf[8], wa[NT], wb[NT];
-  auto read_w = [&](gbf16x8 (&w)[NT], int slot, int kb) {
+  bf16x8 xf[8], wa[NT], wb[NT];
+  auto read_w = [&](bf16x8 (&w)[NT], int slot, int kb) {
     const unsigned char* base = g_lds + slot * UNIT + frag_off;
 #pragma unroll
-    for (int i = 0; i < NT; ++i) w[i] = *reinterpret_cast<const gbf16x8*>(base + (b_sub0 + i * 2 + kb) * 1024);
+    for (int i = 0; i < NT; ++i) w[i] = *reinterpret_cast<const bf16x8*>(base + (b_sub0 + i * 2 + kb) * 1024);
   };
   auto read_x = [&](int j0, int slot, int kb) {
     const unsigned char* base = g_lds + slot * UNIT + frag_off;
 #pragma unroll
-    for (int j = j0; j < j0 + 4; ++j) xf[j] = *reinterpret_cast<const gbf16x8*>(base + (a_sub0 + j * 2 + kb) * 1024);
+    for (int j = j0; j < j0 + 4; ++j) xf[j] = *reinterpret_cast<const bf16x8*>(base + (a_sub0 + j * 2 + kb) * 1024);
   };
   // 16 MFMAs w[0..3] x xf[j0..j0+3]; before_group(i) runs in front of MFMA group i, after_first() behind group 0
-  auto half = [&](gbf16x8 (&w)[NT], int j0, auto&& after_first, auto&& before_group) {
+  auto half = [&](bf16x8 (&w)[NT], int j0, auto&& after_first, auto&& before_group) {
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
       __builtin_amdgcn_sched_barrier(0);
@@ -694,7 +682,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pring_kernel(const unsigned sho
 #pragma unroll
     for (int i = 0; i < NT; ++i)
 #pragma unroll
-      for (int j = 0; j < 8; ++j) acc[i][j] = (gf32x4){0.f, 0.f, 0.f, 0.f};
+      for (int j = 0; j < 8; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const bool has_next = o + 1 < ntiles;
     // the tile whose first units the last two K steps issue; behind the last tile they re-read this tile's first K steps
     // into ring slots nobody multiplies (keeps every step identical; drained before the kernel ends)

@@ -14,25 +14,12 @@
 // load each: chunk = lane_in_group + c * G).  Row statistics are reduced inside the wave with DPP
 // row operations and v_permlane16/32_swap: no LDS, no barrier in the row loop (the first version
 // of this kernel reduced through LDS with four barriers per row and ran at 1.9 TB/s).
-#include "basd_common.h"
+#include "basd_frag.h"
 
 namespace basd {
 
 typedef unsigned int ln_u32x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ void unpack8(const uint4& v, float (&f)[8]) {
-  const unsigned int w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f[2 * i] = __uint_as_float(w[i] << 16);
-    f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-  }
-}
-__device__ __forceinline__ unsigned int pack2(float a, float b) {
-  __hip_bfloat16 x = __float2bfloat16(a), y = __float2bfloat16(b);    // round to nearest even, NaN safe
-  return (unsigned int)(*reinterpret_cast<unsigned short*>(&x)) |
-         ((unsigned int)(*reinterpret_cast<unsigned short*>(&y)) << 16);
-}
 __device__ __forceinline__ float round_bf16(float a) {
   __hip_bfloat16 x = __float2bfloat16(a);
   return bf16_bits_to_f32(*reinterpret_cast<unsigned short*>(&x));

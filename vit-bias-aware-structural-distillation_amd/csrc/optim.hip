@@ -2,7 +2,7 @@
 // (schedulefree 1.4.1 AdamWScheduleFree, train mode; reference call site
 // src/training/trainer.py:54-58,158-159).  HBM-bound: reads y, g, z, v and
 // writes y, z, v once (28 B per parameter), 16 B per lane.
-#include "basd_common.h"
+#include "basd_frag.h"
 
 namespace basd {
 
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256) void transpose_table_kernel(const float* __res
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int c = c0 + ty + 8 * i, r = r0 + tx;                // output row = source column
-    if (c < cols && r < rows) dst[(int64_t)c * rows + r] = __builtin_bit_cast(unsigned short, (__bf16)tile[tx][ty + 8 * i]);
+    if (c < cols && r < rows) dst[(int64_t)c * rows + r] = f32_to_bf16_bits(tile[tx][ty + 8 * i]);
   }
 }
 

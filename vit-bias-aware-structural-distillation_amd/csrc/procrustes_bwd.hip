@@ -31,14 +31,9 @@
 // bottleneck, but 259 spilled registers at the 168-register budget of three waves per SIMD: 1.78 ms).
 // From five m tiles on (n > 64) these kernels are replaced by procrustes_bwd_side_resident_kernel below (0.94 -> 0.52 ms
 // at the shape above); they remain for n <= 64 and for up to 128 rows with fewer than 112 columns.
-#include "basd_common.h"
+#include "basd_frag.h"
 
 namespace basd {
-
-typedef short pb_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float pb_f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 pb_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float pb_f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int PB_ROWB = 80;                 // bytes per staged A row (32 bf16 = 64 + 16 pad)
 constexpr int PB_WAVES = 6;                 // waves per workgroup: two workgroups per CU at three waves per SIMD (168 VGPRs)
@@ -46,9 +41,9 @@ constexpr int PB_THREADS = 64 * PB_WAVES;
 
 // (hi, mid) bf16 split of two floats, packed: hi = bf16(x) (round to nearest even), mid = bf16(x - hi)
 __device__ __forceinline__ void pb_split2(float x0, float x1, unsigned int& hi, unsigned int& mid) {
-  const pb_bf16x2 h = __builtin_convertvector((pb_f32x2){x0, x1}, pb_bf16x2);
-  const pb_f32x2 hf = __builtin_convertvector(h, pb_f32x2);
-  const pb_bf16x2 m = __builtin_convertvector((pb_f32x2){x0 - hf.x, x1 - hf.y}, pb_bf16x2);
+  const bf16x2 h = __builtin_convertvector((f32x2){x0, x1}, bf16x2);
+  const f32x2 hf = __builtin_convertvector(h, f32x2);
+  const bf16x2 m = __builtin_convertvector((f32x2){x0 - hf.x, x1 - hf.y}, bf16x2);
   hi = __builtin_bit_cast(unsigned int, h);
   mid = __builtin_bit_cast(unsigned int, m);
 }
@@ -147,13 +142,13 @@ __global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
     fetch_b(0);
     stage_store(0, 0);
     __syncthreads();
-    pb_f32x4 acc[MT];
+    f32x4 acc[MT];
 #pragma unroll
-    for (int i = 0; i < MT; ++i) acc[i] = (pb_f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < MT; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
     for (int ks = 0; ks < ksteps; ++ks) {
       const int buf = ks & 1;
       const int kb = ks * 32 + (lane >> 4) * 8;
-      pb_bf16x8 bh, bm;
+      bf16x8 bh, bm;
       {
         float x[8];
         if ((ks + 1) * 32 > n) {                           // uniform: the last K step, rows beyond n
@@ -167,8 +162,8 @@ __global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
         uint4 hi, mid;
         pb_split2(x[0], x[1], hi.x, mid.x); pb_split2(x[2], x[3], hi.y, mid.y);
         pb_split2(x[4], x[5], hi.z, mid.z); pb_split2(x[6], x[7], hi.w, mid.w);
-        bh = __builtin_bit_cast(pb_bf16x8, hi);
-        bm = __builtin_bit_cast(pb_bf16x8, mid);
+        bh = __builtin_bit_cast(bf16x8, hi);
+        bm = __builtin_bit_cast(bf16x8, mid);
       }
       const bool more = ks + 1 < ksteps;
       if (more) {                                          // next step's operands: loads only, consumed after the MFMAs
@@ -183,12 +178,12 @@ __global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
       constexpr int HB = (MT + 1) / 2;
 #pragma unroll
       for (int hb = 0; hb < 2; ++hb) {
-        pb_bf16x8 fh[HB], fm[HB];
+        bf16x8 fh[HB], fm[HB];
 #pragma unroll
         for (int j = 0; j < HB; ++j) {
           const int i = hb * HB + j < MT ? hb * HB + j : MT - 1;
-          fh[j] = *reinterpret_cast<const pb_bf16x8*>(ap + (size_t)i * 16 * PB_ROWB);
-          fm[j] = *reinterpret_cast<const pb_bf16x8*>(ap + PLANE + (size_t)i * 16 * PB_ROWB);
+          fh[j] = *reinterpret_cast<const bf16x8*>(ap + (size_t)i * 16 * PB_ROWB);
+          fm[j] = *reinterpret_cast<const bf16x8*>(ap + PLANE + (size_t)i * 16 * PB_ROWB);
         }
 #pragma unroll
         for (int j = 0; j < HB; ++j) {
@@ -245,10 +240,8 @@ __global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
               *reinterpret_cast<float4*>(O + off) = make_float4(cr * rv.x, cr * rv.y, cr * rv.z, cr * rv.w);
             } else {
               uint2 o;
-              o.x = (unsigned)__builtin_bit_cast(unsigned short, (__bf16)(cr * rv.x)) |
-                    ((unsigned)__builtin_bit_cast(unsigned short, (__bf16)(cr * rv.y)) << 16);
-              o.y = (unsigned)__builtin_bit_cast(unsigned short, (__bf16)(cr * rv.z)) |
-                    ((unsigned)__builtin_bit_cast(unsigned short, (__bf16)(cr * rv.w)) << 16);
+              o.x = pack_bf16_bits(cr * rv.x, cr * rv.y);
+              o.y = pack_bf16_bits(cr * rv.z, cr * rv.w);
               *reinterpret_cast<uint2*>(O + off) = o;
             }
           }
@@ -269,8 +262,6 @@ __global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
   }
 }
 
-typedef short pb_v4s __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) pb_v4s pb_lds_v4s;
 constexpr int PB_BPITCH = 208;              // bytes between the k rows of the staged W tile (96 bf16 = 192 + 16 pad)
 
 // The same kernel with the B operand (W) staged through LDS -- see the comment at `bload` below.  One operand buffer each
@@ -394,25 +385,25 @@ __global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
     stage_store(0, 0);
     bstore();
     __syncthreads();
-    pb_f32x4 acc[MT];
+    f32x4 acc[MT];
 #pragma unroll
-    for (int i = 0; i < MT; ++i) acc[i] = (pb_f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < MT; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
     for (int ks = 0; ks < ksteps; ++ks) {
       const bool more = ks + 1 < ksteps;
       if (more) {                                          // next step's operands: loads only, stored after the MFMAs
         bload(ks + 1);
         stage_load(ks + 1);
       }
-      pb_bf16x8 bh, bm;
-      {
+      bf16x8 bh, bm;
+      {                                                    // tr_cons of basd_frag.h on the hi and mid planes (byte pitch)
         const int li = lane & 15, qq = li >> 2, pp = li & 3;
         const unsigned char* b0 = bbuf + (size_t)((lane >> 4) * 8 + qq) * PB_BPITCH + (size_t)(wave * 16 + 4 * pp) * 2;
-        const pb_v4s h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pb_lds_v4s*)b0);
-        const pb_v4s h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pb_lds_v4s*)(b0 + 4 * PB_BPITCH));
-        const pb_v4s m0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pb_lds_v4s*)(b0 + 32 * PB_BPITCH));
-        const pb_v4s m1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pb_lds_v4s*)(b0 + 32 * PB_BPITCH + 4 * PB_BPITCH));
-        bh = (pb_bf16x8){h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-        bm = (pb_bf16x8){m0[0], m0[1], m0[2], m0[3], m1[0], m1[1], m1[2], m1[3]};
+        const v4s h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)b0);
+        const v4s h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(b0 + 4 * PB_BPITCH));
+        const v4s m0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(b0 + 32 * PB_BPITCH));
+        const v4s m1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(b0 + 32 * PB_BPITCH + 4 * PB_BPITCH));
+        bh = (bf16x8){h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+        bm = (bf16x8){m0[0], m0[1], m0[2], m0[3], m1[0], m1[1], m1[2], m1[3]};
       }
       // A fragments in two batches of (MT + 1) / 2 tiles: all 16-byte fragment reads of a batch are issued together (one
       // exposed LDS latency per batch; a fence per tile pair exposed it MT / 2 times per K step: 4.8 k cycles per step
@@ -422,12 +413,12 @@ __global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
       constexpr int HB = (MT + 1) / 2;
 #pragma unroll
       for (int hb = 0; hb < 2; ++hb) {
-        pb_bf16x8 fh[HB], fm[HB];
+        bf16x8 fh[HB], fm[HB];
 #pragma unroll
         for (int j = 0; j < HB; ++j) {
           const int i = hb * HB + j < MT ? hb * HB + j : MT - 1;
-          fh[j] = *reinterpret_cast<const pb_bf16x8*>(ap + (size_t)i * 16 * PB_ROWB);
-          fm[j] = *reinterpret_cast<const pb_bf16x8*>(ap + PLANE + (size_t)i * 16 * PB_ROWB);
+          fh[j] = *reinterpret_cast<const bf16x8*>(ap + (size_t)i * 16 * PB_ROWB);
+          fm[j] = *reinterpret_cast<const bf16x8*>(ap + PLANE + (size_t)i * 16 * PB_ROWB);
         }
 #pragma unroll
         for (int j = 0; j < HB; ++j) {
@@ -485,10 +476,8 @@ __global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
               *reinterpret_cast<float4*>(O + off) = make_float4(cr * rv.x, cr * rv.y, cr * rv.z, cr * rv.w);
             } else {
               uint2 o;
-              o.x = (unsigned)__builtin_bit_cast(unsigned short, (__bf16)(cr * rv.x)) |
-                    ((unsigned)__builtin_bit_cast(unsigned short, (__bf16)(cr * rv.y)) << 16);
-              o.y = (unsigned)__builtin_bit_cast(unsigned short, (__bf16)(cr * rv.z)) |
-                    ((unsigned)__builtin_bit_cast(unsigned short, (__bf16)(cr * rv.w)) << 16);
+              o.x = pack_bf16_bits(cr * rv.x, cr * rv.y);
+              o.y = pack_bf16_bits(cr * rv.z, cr * rv.w);
               *reinterpret_cast<uint2*>(O + off) = o;
             }
           }
@@ -670,7 +659,7 @@ __global__ __launch_bounds__(PBR_THREADS) __attribute__((amdgpu_waves_per_eu(2, 
   wstore(wr[0], 0, 0, 0);                                  // step 0; visible after the barrier of step 0
   wnext(wr[0]);                                            // step PF
 
-  pb_f32x4 acc[MT];
+  f32x4 acc[MT];
   const int col = lane & 15, g4 = lane >> 4;
   const int prow = lane >> 2, pch = lane & 3;              // epilogue's row-wise walk: 16 rows x 4 chunks of 4 columns
   // Row dots in the order of the staged kernel, whose wave s % 6 adds strip s to its own slice, strips ascending, and
@@ -681,7 +670,7 @@ __global__ __launch_bounds__(PBR_THREADS) __attribute__((amdgpu_waves_per_eu(2, 
   float pend[MT];
   int pend_slot = -1;                                      // wave-uniform: >= 0 while dots are waiting
 #pragma unroll
-  for (int i = 0; i < MT; ++i) { acc[i] = (pb_f32x4){0.f, 0.f, 0.f, 0.f}; pend[i] = 0.f; }
+  for (int i = 0; i < MT; ++i) { acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f}; pend[i] = 0.f; }
   auto flush = [&]() {
     if (pend_slot >= 0) {
       if (pch == 0) {
@@ -705,29 +694,29 @@ __global__ __launch_bounds__(PBR_THREADS) __attribute__((amdgpu_waves_per_eu(2, 
           wstore(wr[(u + 1) % PBR_PF], buf ^ 1, wrap ? g + 1 : g, wrap ? 0 : ks + 1);   // the next step, loaded PF steps ago
           wnext(wr[(u + 1) % PBR_PF]);                     // the step PF after it
         }
-        pb_bf16x8 bh, bm;
-        {
+        bf16x8 bh, bm;
+        {                                                  // tr_cons of basd_frag.h on the hi and mid planes (byte pitch)
           const int qq = col >> 2, pp = col & 3;
           const unsigned char* b0 = bbuf + (size_t)buf * 2 * BPLANE + (size_t)(g4 * 8 + qq) * PBR_BPITCH +
                                     (size_t)(wave * 16 + 4 * pp) * 2;
-          const pb_v4s h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pb_lds_v4s*)b0);
-          const pb_v4s h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pb_lds_v4s*)(b0 + 4 * PBR_BPITCH));
-          const pb_v4s m0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pb_lds_v4s*)(b0 + BPLANE));
-          const pb_v4s m1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pb_lds_v4s*)(b0 + BPLANE + 4 * PBR_BPITCH));
-          bh = (pb_bf16x8){h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-          bm = (pb_bf16x8){m0[0], m0[1], m0[2], m0[3], m1[0], m1[1], m1[2], m1[3]};
+          const v4s h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)b0);
+          const v4s h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(b0 + 4 * PBR_BPITCH));
+          const v4s m0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(b0 + BPLANE));
+          const v4s m1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(b0 + BPLANE + 4 * PBR_BPITCH));
+          bh = (bf16x8){h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+          bm = (bf16x8){m0[0], m0[1], m0[2], m0[3], m1[0], m1[1], m1[2], m1[3]};
         }
         // A fragments of K step ks out of the resident planes, in two batches (registers), as in the kernels above
         const unsigned char* ap = abuf + (size_t)col * AP + (size_t)ks * 64 + g4 * 16;
         constexpr int HB = (MT + 1) / 2;
 #pragma unroll
         for (int hb = 0; hb < 2; ++hb) {
-          pb_bf16x8 fh[HB], fm[HB];
+          bf16x8 fh[HB], fm[HB];
 #pragma unroll
           for (int j = 0; j < HB; ++j) {
             const int i = hb * HB + j < MT ? hb * HB + j : MT - 1;
-            fh[j] = *reinterpret_cast<const pb_bf16x8*>(ap + (size_t)i * 16 * AP);
-            fm[j] = *reinterpret_cast<const pb_bf16x8*>(ap + APLANE + (size_t)i * 16 * AP);
+            fh[j] = *reinterpret_cast<const bf16x8*>(ap + (size_t)i * 16 * AP);
+            fm[j] = *reinterpret_cast<const bf16x8*>(ap + APLANE + (size_t)i * 16 * AP);
           }
 #pragma unroll
           for (int j = 0; j < HB; ++j) {
@@ -779,10 +768,8 @@ __global__ __launch_bounds__(PBR_THREADS) __attribute__((amdgpu_waves_per_eu(2, 
                     *reinterpret_cast<float4*>(O + off) = make_float4(cr * rv.x, cr * rv.y, cr * rv.z, cr * rv.w);
                   } else {
                     uint2 o;
-                    o.x = (unsigned)__builtin_bit_cast(unsigned short, (__bf16)(cr * rv.x)) |
-                          ((unsigned)__builtin_bit_cast(unsigned short, (__bf16)(cr * rv.y)) << 16);
-                    o.y = (unsigned)__builtin_bit_cast(unsigned short, (__bf16)(cr * rv.z)) |
-                          ((unsigned)__builtin_bit_cast(unsigned short, (__bf16)(cr * rv.w)) << 16);
+                    o.x = pack_bf16_bits(cr * rv.x, cr * rv.y);
+                    o.y = pack_bf16_bits(cr * rv.z, cr * rv.w);
                     *reinterpret_cast<uint2*>(O + off) = o;
                   }
                 }
@@ -790,7 +777,7 @@ __global__ __launch_bounds__(PBR_THREADS) __attribute__((amdgpu_waves_per_eu(2, 
                 dot += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(dot), 0x4E, 0xF, 0xF, true));     // quad_perm 2,3,0,1
                 if (later) pend[i] = dot;
                 else if (has && pch == 0) s_slot[slot * MT * 16 + lrow] += c2 * dot;
-                acc[i] = (pb_f32x4){0.f, 0.f, 0.f, 0.f};
+                acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
               }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -1045,25 +1032,25 @@ __global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
     stage_store(0);
     bstore();
     __syncthreads();
-    pb_f32x4 acc[MT];
+    f32x4 acc[MT];
 #pragma unroll
-    for (int i = 0; i < MT; ++i) acc[i] = (pb_f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < MT; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
     for (int ks = 0; ks < ksteps; ++ks) {
       const bool more = ks + 1 < ksteps;
       if (more) {                                          // next step's operands: loads only, stored after the MFMAs
         bload(ks + 1);
         stage_load(ks + 1);
       }
-      pb_bf16x8 bh, bm;
-      {
+      bf16x8 bh, bm;
+      {                                                    // tr_cons of basd_frag.h on the hi and mid planes (byte pitch)
         const int li = lane & 15, qq = li >> 2, pp = li & 3;
         const unsigned char* b0 = bbuf + (size_t)((lane >> 4) * 8 + qq) * PB_BPITCH + (size_t)(wave * 16 + 4 * pp) * 2;
-        const pb_v4s h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pb_lds_v4s*)b0);
-        const pb_v4s h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pb_lds_v4s*)(b0 + 4 * PB_BPITCH));
-        const pb_v4s m0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pb_lds_v4s*)(b0 + 32 * PB_BPITCH));
-        const pb_v4s m1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pb_lds_v4s*)(b0 + 32 * PB_BPITCH + 4 * PB_BPITCH));
-        bh = (pb_bf16x8){h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-        bm = (pb_bf16x8){m0[0], m0[1], m0[2], m0[3], m1[0], m1[1], m1[2], m1[3]};
+        const v4s h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)b0);
+        const v4s h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(b0 + 4 * PB_BPITCH));
+        const v4s m0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(b0 + 32 * PB_BPITCH));
+        const v4s m1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(b0 + 32 * PB_BPITCH + 4 * PB_BPITCH));
+        bh = (bf16x8){h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+        bm = (bf16x8){m0[0], m0[1], m0[2], m0[3], m1[0], m1[1], m1[2], m1[3]};
       }
       // A fragments in two batches of four tiles (one exposed LDS latency per batch; the fence keeps the second
       // batch's reads from being hoisted on top of the first: registers)
@@ -1071,12 +1058,12 @@ __global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
       constexpr int HB = MT / 2;
 #pragma unroll
       for (int hb = 0; hb < 2; ++hb) {
-        pb_bf16x8 fh[HB], fm[HB];
+        bf16x8 fh[HB], fm[HB];
 #pragma unroll
         for (int j = 0; j < HB; ++j) {
           const int i = hb * HB + j;
-          fh[j] = *reinterpret_cast<const pb_bf16x8*>(ap + (size_t)i * 16 * PB_ROWB);
-          fm[j] = *reinterpret_cast<const pb_bf16x8*>(ap + PLANE + (size_t)i * 16 * PB_ROWB);
+          fh[j] = *reinterpret_cast<const bf16x8*>(ap + (size_t)i * 16 * PB_ROWB);
+          fm[j] = *reinterpret_cast<const bf16x8*>(ap + PLANE + (size_t)i * 16 * PB_ROWB);
         }
 #pragma unroll
         for (int j = 0; j < HB; ++j) {
@@ -1127,10 +1114,8 @@ __global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
             *reinterpret_cast<float4*>(O + off) = make_float4(cr * rv.x, cr * rv.y, cr * rv.z, cr * rv.w);
           } else {
             uint2 o;
-            o.x = (unsigned)__builtin_bit_cast(unsigned short, (__bf16)(cr * rv.x)) |
-                  ((unsigned)__builtin_bit_cast(unsigned short, (__bf16)(cr * rv.y)) << 16);
-            o.y = (unsigned)__builtin_bit_cast(unsigned short, (__bf16)(cr * rv.z)) |
-                  ((unsigned)__builtin_bit_cast(unsigned short, (__bf16)(cr * rv.w)) << 16);
+            o.x = pack_bf16_bits(cr * rv.x, cr * rv.y);
+            o.y = pack_bf16_bits(cr * rv.z, cr * rv.w);
             *reinterpret_cast<uint2*>(O + off) = o;
           }
         }

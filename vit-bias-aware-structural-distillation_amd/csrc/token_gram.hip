@@ -7,12 +7,9 @@
 // Workgroup = 512 threads (8 waves), 64-row tiles, grid-stride; the fp64 Gram
 // accumulators (lower-triangular 16x16 tiles) stay in registers across all the
 // tiles of a workgroup and are added to HBM once (fp64 atomics, <= 256 WGs).
-#include "basd_common.h"
+#include "basd_frag.h"
 
 namespace basd {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TM = 64;       // rows per tile
 constexpr int KC = 32;       // K chunk of the projection
@@ -191,7 +188,6 @@ extern "C" int basd_token_gram(const void* x, int x_dtype, int64_t rows, int d_i
 // (20 lower-triangular tiles per wave) persist in registers across all the tiles of a workgroup.
 namespace basd {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int TM2 = 128;          // rows per workgroup tile
 constexpr int KC2 = 32;           // K chunk
 constexpr int PROW = 80;          // bytes per (split, col) row of the staged P chunk (64 + 16 pad)

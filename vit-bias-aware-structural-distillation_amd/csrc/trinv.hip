@@ -12,7 +12,7 @@
 // gather of the right-hand sides is needed.  Columns >= rank of L_p are replaced by
 // unit columns (their rows of out are zeroed: pseudo-inverse semantics).
 #include <stdlib.h>
-#include "basd_common.h"
+#include "basd_frag.h"
 
 namespace basd {
 
@@ -83,12 +83,11 @@ __global__ __launch_bounds__(768) void trinv_kernel(const double* __restrict__ l
 //      v_mfma_f64_16x16x4_f64 chains), which only reads finished block columns > j of X and
 //      column j of W: 11 levels with two barriers each instead of 192 steps.
 // Same input / output contract as trinv_kernel.
-typedef double f64x4t __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ int blk_off(int bi, int bj) { return (bi * (bi + 1) / 2 + bj) * 256; }
 
 // C (16x16, registers) += A (block at a_off) * B (block at b_off), blocks row-major [16][16] in LDS
-__device__ __forceinline__ f64x4t blk_mma(const double* __restrict__ X, int a_off, int b_off, f64x4t acc, int lane) {
+__device__ __forceinline__ f64x4 blk_mma(const double* __restrict__ X, int a_off, int b_off, f64x4 acc, int lane) {
   const int lr = lane & 15, lq = lane >> 4;
 #pragma unroll
   for (int kk = 0; kk < 4; ++kk) {
@@ -167,7 +166,7 @@ __global__ __launch_bounds__(768) void trinv_blocked_kernel(const double* __rest
     while ((bi + 1) * (bi + 2) / 2 <= b) ++bi;
     const int bj = b - bi * (bi + 1) / 2;
     if (bi == bj) continue;                                  // uniform per wave
-    f64x4t acc = {0.0, 0.0, 0.0, 0.0};
+    f64x4 acc = {0.0, 0.0, 0.0, 0.0};
     acc = blk_mma(X, b * 256, blk_off(bj, bj), acc, lane);   // all operand reads precede the stores below
 #pragma unroll
     for (int reg = 0; reg < 4; ++reg) X[b * 256 + (lq + 4 * reg) * 16 + lr] = acc[reg];
@@ -176,7 +175,7 @@ __global__ __launch_bounds__(768) void trinv_blocked_kernel(const double* __rest
   // ---- 3. block columns from the right: X_ij = - sum_k X_ik W_kj
   for (int j = nb - 2; j >= 0; --j) {
     const int i = j + 1 + wave;
-    f64x4t acc = {0.0, 0.0, 0.0, 0.0};
+    f64x4 acc = {0.0, 0.0, 0.0, 0.0};
     if (i < nb) {
       for (int k = j + 1; k <= i; ++k) acc = blk_mma(X, blk_off(i, k), blk_off(k, j), acc, lane);
     }

@@ -14,27 +14,13 @@
 // v_mfma_f32_16x16x32_bf16 per (n, k) tile.  Partial results are added with fp32 atomics (dW / db
 // zero-initialised by the caller); the atomics are 27 % of the kernel (ablation), 512 workgroups
 // is the measured optimum between that tail and load parallelism.
-#include "basd_common.h"
+#include "basd_frag.h"
 
 namespace basd {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short v4s __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) v4s lds_v4s;
 
 constexpr int WG_TN = 64;        // output rows (n) per workgroup
 constexpr int WG_MC = 64;        // m rows per chunk
 constexpr int DY_LD = 72;        // LDS row stride of the dY chunk, in bf16 (144 B)
-
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned short* tile, int ld, int row0, int col0, int lane) {
-  // 8 consecutive rows (row0 .. row0+7) of column col0 + (lane & 15): two 4-row transposing reads
-  const int i = lane & 15, q = i >> 2, p = i & 3;
-  const unsigned short* a0 = tile + (row0 + q) * ld + col0 + 4 * p;
-  const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)a0);
-  const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(a0 + 4 * ld));
-  return (bf16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
 
 template <int KT>   // k tiles of 16 per workgroup: TK = 16 * KT
 __global__ __launch_bounds__(256) void wgrad_bf16_kernel(const unsigned short* __restrict__ dy,
@@ -120,10 +106,10 @@ __global__ __launch_bounds__(256) void wgrad_bf16_kernel(const unsigned short* _
       const int row0 = ks * 32 + 8 * (lane >> 4);
       bf16x8 a[4];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) a[i] = tr_frag(dYs, DY_LD, row0, i * 16, lane);
+      for (int i = 0; i < 4; ++i) a[i] = tr_cons(dYs, DY_LD, row0, i * 16, lane);
 #pragma unroll
       for (int t = 0; t < KW; ++t) {
-        const bf16x8 b = tr_frag(Xs, X_LD, row0, (wave * KW + t) * 16, lane);
+        const bf16x8 b = tr_cons(Xs, X_LD, row0, (wave * KW + t) * 16, lane);
 #pragma unroll
         for (int i = 0; i < 4; ++i) acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], b, acc[i][t], 0, 0, 0);
       }
