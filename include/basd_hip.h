@@ -76,8 +76,10 @@
  *                          packed into one byte buffer
  *   basd_cls_tally         src/evaluation/metrics.py:19-55: outputs[:, valid_indices], MulticlassAccuracy(top_k = 1 | 5)
  *                          and criterion(outputs, labels) of one evaluation batch, accumulated on the device
+ *   basd_mixup_cutmix      src/training/trainer.py:89-92,138: RandomChoice([MixUp, CutMix]) of one batch and its soft
+ *                          targets, written into the captured step's input buffers in one launch
  *
- * 65 entries in all (basd_version and basd_last_error included).
+ * 66 entries in all (basd_version and basd_last_error included).
  */
 #ifndef BASD_HIP_H
 #define BASD_HIP_H
@@ -645,6 +647,31 @@ int basd_ta_normalize_u8(const void* img, const int* ops, const double* mags, in
 int basd_cls_tally(const void* logits, int logits_bf16, int64_t row_stride, const int64_t* labels,
                    const int64_t* keep, int B, int C, int K, int top_k, float smoothing, int* row_rank,
                    double* row_loss, double* tally, void* stream);
+
+/* MixUp or CutMix of one batch with its soft targets (reference src/training/trainer.py:89-92,138, torchvision v2's
+ * RandomChoice([MixUp, CutMix])): images [B, C_img, H, W] contiguous, fp32 (img_bf16 == 0) or bf16 (!= 0); labels [B]
+ * int64 on the device; out_images like images, out_targets [B, num_classes] fp32.  The random draws (mode, lam, box) are
+ * the caller's, on the host.  The partner of sample i is sample (i - 1) mod B; the rolled batch is never materialised.
+ *   mode 0, MixUp:   out_images[i] = lerp(x[i-1], x[i], lam) with torch's formula in fp32, a + w (b - a) for |w| < 0.5,
+ *                    b - (b - a) (1 - w) otherwise; bf16 images are blended in fp32 and rounded once, to nearest even.
+ *                    lam = 0 / 1 returns x[i-1] / x[i] exactly.
+ *   mode 1, CutMix:  out_images[i] = x[i-1] on rows y0 .. y1 - 1, columns x0 .. x1 - 1 of every channel and x[i]
+ *                    elsewhere: bit copies, every pixel written exactly once.  The box is half-open and already clipped,
+ *                    0 <= y0 <= y1 <= H, 0 <= x0 <= x1 <= W; an empty box copies the images through (lam is then 1).
+ *                    lam is the weight of the TARGETS only, 1 - box area / (H W).  The box is ignored in mode 0.
+ *   targets:         out_targets[i, c] = lerp(onehot(y[i-1])[c], onehot(y[i])[c], lam), same formula: every element of
+ *                    the B x num_classes buffer is written, zeros included; y[i] == y[i-1] gives exactly 1.  A label
+ *                    outside [0, num_classes) matches no column and writes nothing out of bounds.
+ * One launch: up to 2048 workgroups walk the flat image array in 16-byte vectors (one-element vectors when images /
+ * out_images are not 16-byte aligned; element loads of the partner when C_img H W is no multiple of the vector; the
+ * elements behind the last whole vector one by one), a CutMix vector reading only the source(s) its pixels come from;
+ * min(B, 256) workgroups behind them write the target rows.  No workspace, no allocation, no synchronisation: legal
+ * inside a stream capture.  BASD_ERR_SHAPE, checked on the host before anything is enqueued: B < 1, num_classes < 1, an
+ * empty image, C_img H W >= 2^31, mode outside {0, 1}, a box outside [0, H] x [0, W] (mode 1), a null pointer, a pointer
+ * not aligned to its element, or out_images overlapping images (the partner row would be read after it was written). */
+int basd_mixup_cutmix(const void* images, int img_bf16, int B, int C_img, int H, int W, const int64_t* labels,
+                      int num_classes, int mode, float lam, int y0, int y1, int x0, int x1, void* out_images,
+                      float* out_targets, void* stream);
 
 #ifdef __cplusplus
 }

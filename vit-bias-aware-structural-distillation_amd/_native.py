@@ -35,6 +35,7 @@ EXPORTS = (
     "basd_attention_bwd_long_workspace_bytes", "basd_attention_bwd_long_bf16", "basd_attention_fwd_f32x3_long",
     "basd_dwconv7_ln_bf16", "basd_grn_workspace_bytes", "basd_grn_bf16", "basd_patchify_bf16",
     "basd_resample_u8", "basd_ta_normalize_u8", "basd_cls_tally", "basd_resample_u8_packed",
+    "basd_mixup_cutmix",
 )
 
 
@@ -106,6 +107,7 @@ _SIGNATURES = {
     "basd_resample_u8_packed": (_P, _I64, _P, _P, _I, _I, _P, _P),
     "basd_ta_normalize_u8": (_P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P),
     "basd_cls_tally": (_P, _I, _I64, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P),
+    "basd_mixup_cutmix": (_P, _I, _I, _I, _I, _I, _P, _I, _I, _F, _I, _I, _I, _I, _P, _P, _P),
 }
 
 
@@ -1387,3 +1389,33 @@ def cls_tally(logits: torch.Tensor, labels: torch.Tensor, tally: torch.Tensor, *
                                 _ptr(keep), b, c, k, int(top_k), ctypes.c_float(smoothing), _ptr(row_rank),
                                 _ptr(row_loss), _ptr(tally), _stream()), "basd_cls_tally")
     return row_rank, row_loss
+
+
+# --------------------------------------------------------------------------- MixUp / CutMix + soft targets (csrc/mixup.hip)
+MIXUP, CUTMIX = 0, 1
+
+
+def mixup_supported(images: torch.Tensor) -> bool:
+    """batches basd_mixup_cutmix takes: [B, C, H, W] fp32 / bf16, contiguous, on the device, at least one element"""
+    return (images.is_cuda and images.dim() == 4 and images.dtype in (torch.float32, torch.bfloat16)
+            and images.numel() > 0 and images.is_contiguous())
+
+
+def mixup_cutmix(images: torch.Tensor, labels: torch.Tensor, num_classes: int, mode: int, lam: float, box,
+                 out: torch.Tensor, out_targets: torch.Tensor):
+    """images [B, C, H, W] fp32 / bf16, labels [B] int64, mode MIXUP | CUTMIX, lam the blend weight (MixUp) or the
+    box-area-corrected weight of the targets (CutMix), box = (y0, y1, x0, x1) half-open and clipped (ignored for MixUp)
+    -> out (like images, must not overlap them), out_targets [B, num_classes] fp32, both written in full by one launch;
+    semantics in include/basd_hip.h.  No host sync."""
+    _need_cuda(images, labels, out, out_targets)
+    assert mixup_supported(images), (tuple(images.shape), images.stride(), images.dtype)
+    b, c, h, w = images.shape
+    assert labels.dtype == torch.int64 and labels.shape == (b,) and labels.is_contiguous(), (labels.dtype, tuple(labels.shape))
+    assert out.shape == images.shape and out.dtype == images.dtype and out.is_contiguous(), (tuple(out.shape), out.dtype)
+    assert out_targets.shape == (b, num_classes) and out_targets.dtype == torch.float32 and out_targets.is_contiguous(), \
+        (tuple(out_targets.shape), out_targets.dtype)
+    y0, y1, x0, x1 = (int(v) for v in box)
+    _check(lib().basd_mixup_cutmix(_ptr(images), int(images.dtype == torch.bfloat16), b, c, h, w, _ptr(labels),
+                                   int(num_classes), int(mode), ctypes.c_float(lam), y0, y1, x0, x1, _ptr(out),
+                                   _ptr(out_targets), _stream()), "basd_mixup_cutmix")
+    return out, out_targets
