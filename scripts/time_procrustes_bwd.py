@@ -4,8 +4,10 @@ shape, e.g. the 384 px ones (--batch 256 --n 576, --n 729: the row-tiled kernel)
 device-event brackets of --iters calls, the two paths alternated in one process.
 
 --side times basd_procrustes_bwd_side alone (one side of the backward: fac [n, n] x W [n, d], fp32 output) at
---batch / --n / --d and prints the median of the brackets; BASD_LIB=<another build of the library> times that build, so
-two builds are compared by alternating runs of this script on one machine."""
+--batch / --n / --d (--table: at every shape of the table in csrc/procrustes_bwd.hip) and prints the median of the
+brackets; BASD_LIB=<another build of the library> times that build.  --parent <another build> loads that build into the
+same process and alternates its brackets with the in-tree build's: parent, this build, parent, ...; the spread of the
+parent's own brackets is the band inside which the two count as equal."""
 import argparse, ctypes, os, statistics, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import basd_amd._native as nat
@@ -17,6 +19,9 @@ ap.add_argument("--d-s", type=int, default=192)
 ap.add_argument("--d-t", type=int, default=768)
 ap.add_argument("--side", action="store_true", help="time basd_procrustes_bwd_side alone at --batch / --n / --d")
 ap.add_argument("--d", type=int, default=768, help="columns of W for --side")
+ap.add_argument("--parent", default=None, help="--side: another build of libbasd_hip.so, loaded into the same process; its "
+                "brackets and this build's are alternated")
+ap.add_argument("--table", action="store_true", help="--side: every shape of the table in csrc/procrustes_bwd.hip")
 ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--runs", type=int, default=3)
 args = ap.parse_args()
@@ -33,8 +38,12 @@ def bracket(f, it):
     return e0.elapsed_time(e1) / it
 
 
-if args.side:
-    batch, n, d = args.batch, args.n or 196, args.d
+# the shapes of the table in csrc/procrustes_bwd.hip, the one shape left on the staged kernel and a 576-token one
+TABLE = [(1024, 196, 768), (512, 196, 1024), (1024, 196, 1280), (1024, 196, 192), (1024, 80, 768), (1024, 128, 768),
+         (1024, 256, 768), (2, 100, 112), (300, 80, 16), (256, 576, 192)]
+
+
+def time_side(batch, n, d, parent):
     g = torch.Generator().manual_seed(0)
     w = torch.randn(batch, n, d, generator=g).cuda()
     a = torch.rand(batch, n, generator=g).cuda() + 0.1; a = (a / a.sum(-1, keepdim=True)).contiguous()
@@ -43,18 +52,42 @@ if args.side:
     out, rowdot = torch.empty_like(w), torch.empty_like(a)
     p = ctypes.c_void_p
 
-    def side():
-        nat._check(nat.lib().basd_procrustes_bwd_side(p(fac.data_ptr()), p(w.data_ptr()), p(a.data_ptr()), p(gl.data_ptr()),
-                                                      batch, n, d, p(out.data_ptr()), nat.DTYPE_F32, p(rowdot.data_ptr()),
-                                                      nat._stream()), "basd_procrustes_bwd_side")
+    def side(lib):
+        nat._check(lib.basd_procrustes_bwd_side(p(fac.data_ptr()), p(w.data_ptr()), p(a.data_ptr()), p(gl.data_ptr()),
+                                                batch, n, d, p(out.data_ptr()), nat.DTYPE_F32, p(rowdot.data_ptr()),
+                                                nat._stream()), "basd_procrustes_bwd_side")
 
-    for _ in range(3):
-        side()
+    libs = [nat.lib()] + ([parent] if parent is not None else [])
+    for lib in libs:
+        for _ in range(3):
+            side(lib)
     torch.cuda.synchronize()
-    ts = [bracket(side, args.iters) for _ in range(args.runs)]
-    gb = (2 * batch * n * d + batch * n * n) * 4 / 1e9       # W read + gradient written + factor read, once each
-    print(f"side batch {batch} n {n} d {d} ({nat.LIB_PATH}): median {statistics.median(ts):.4f} ms "
-          f"({'/'.join(f'{x:.4f}' for x in ts)}), {gb / statistics.median(ts):.2f} TB/s of {gb:.2f} GB algorithmic", flush=True)
+    med = statistics.median
+    if parent is None:
+        ts = [bracket(lambda: side(nat.lib()), args.iters) for _ in range(args.runs)]
+        gb = (2 * batch * n * d + batch * n * n) * 4 / 1e9       # W read + gradient written + factor read, once each
+        print(f"side batch {batch} n {n} d {d} ({nat.LIB_PATH}): median {med(ts):.4f} ms "
+              f"({'/'.join(f'{x:.4f}' for x in ts)}), {gb / med(ts):.2f} TB/s of {gb:.2f} GB algorithmic", flush=True)
+        return
+    # parent, this build, parent, ... alternated: the parent's own brackets give the band a difference has to leave
+    tp, tn = [], []
+    for _ in range(args.runs):
+        tp.append(bracket(lambda: side(parent), args.iters)); tn.append(bracket(lambda: side(nat.lib()), args.iters))
+    tp.append(bracket(lambda: side(parent), args.iters))
+    inside = min(tp) - 1e-4 <= med(tn) <= max(tp) + 1e-4
+    print(f"side {batch:5d} x {n:4d} x {d:5d}   parent {med(tp):.4f} ms (brackets {min(tp):.4f} - {max(tp):.4f}, spread "
+          f"{max(tp) - min(tp):.4f})   this build {med(tn):.4f} ms ({min(tn):.4f} - {max(tn):.4f})   "
+          f"{'inside' if inside else 'faster than' if med(tn) < min(tp) else 'OUTSIDE'} the parent's band", flush=True)
+
+
+if args.side:
+    parent = None
+    if args.parent:
+        parent = ctypes.CDLL(args.parent)
+        parent.basd_procrustes_bwd_side.argtypes = list(nat._SIGNATURES["basd_procrustes_bwd_side"])
+        parent.basd_procrustes_bwd_side.restype = ctypes.c_int
+    for (batch, n, d) in (TABLE if args.table else [(args.batch, args.n or 196, args.d)]):
+        time_side(batch, n, d, parent)
     sys.exit(0)
 
 shapes = [(1024, 196, 192, 768), (512, 196, 384, 1024)] if args.n is None else [(args.batch, args.n, args.d_s, args.d_t)]

@@ -12,7 +12,9 @@ from tests import _pbwd_emul
 #   (two tiles of 8 do not fit the LDS), exact tiles; 240 = three tiles of 5; 132 = 5 + 4; 128 = one tile of 8; 100 =
 #   one tile of 7; 80 = one tile of 5, the fewest m tiles the resident kernel is dispatched for; 64 = the other side of
 #   that boundary (the staged kernel).  Up to 128 rows the resident kernel needs d >= 112 as well: d = 96 and d = 16
-#   at n = 80 / 100 are the other side of that boundary.
+#   at n = 80 / 100 are the other side of that boundary.  Up to 48 rows W is not staged (the direct kernel): 20 = two m
+#   tiles with a K tail of 20 and a row tail of 4; 32 = two exact tiles, one K step; 48 = three tiles in the kernel for
+#   four, with a ragged column group.
 #   d: 16 = one strip for eight waves (n >= 132); 112 = a ragged group alone; 144 / 208 = a ragged group after a full
 #   128-column one; 768 = six full groups.
 #   batch: 300 matrices at n = 80 are more workgroups than the 256 CUs, so the grid's (matrix, tile) mapping wraps: at
@@ -21,7 +23,8 @@ from tests import _pbwd_emul
 CASES = [(1, 196, 768, False), (3, 196, 768, True), (2, 196, 112, False), (2, 196, 16, True), (1, 256, 768, True),
          (2, 256, 112, False), (2, 240, 208, False), (2, 132, 112, False), (2, 132, 16, True), (2, 128, 144, True),
          (2, 100, 112, True), (2, 100, 16, False), (300, 80, 16, False), (300, 80, 112, False), (2, 80, 112, True),
-         (2, 80, 96, False), (2, 64, 112, False), (2, 64, 16, True)]
+         (2, 80, 96, False), (2, 64, 112, False), (2, 64, 16, True), (2, 20, 16, False), (2, 32, 48, True),
+         (2, 48, 112, False)]
 
 
 def white(batch, n, d):

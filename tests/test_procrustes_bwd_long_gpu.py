@@ -1,5 +1,5 @@
 """The Procrustes backward for 257 <= n <= 1024 student tokens (and n % 4 != 0) on the row-tiled residual-product kernel
-(csrc/procrustes_bwd.hip, procrustes_bwd_side_long_kernel): the C entries against fp64 with the CPU restatement of the
+(csrc/procrustes_bwd.hip, procrustes_bwd_side_tiled_kernel with row tiles): the C entries against fp64 with the CPU restatement of the
 contract (tests/_pbwd_emul.py) as the yardstick, reproducibility, bounds, the autograd path and a 384 px training step.
 
 Yardstick: the kernel and the restatement compute the same three bf16 products with fp32 accumulation and may differ in

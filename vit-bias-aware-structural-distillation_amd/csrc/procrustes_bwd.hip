@@ -31,6 +31,9 @@
 // bottleneck, but 259 spilled registers at the 168-register budget of three waves per SIMD: 1.78 ms).
 // From five m tiles on (n > 64) these kernels are replaced by procrustes_bwd_side_resident_kernel below (0.94 -> 0.52 ms
 // at the shape above); they remain for n <= 64 and for up to 128 rows with fewer than 112 columns.
+// The file: the pieces all kernels share (pb_*, PbStage*), then the direct kernel (W from global memory: n <= 48), the
+// tiled kernel (W through LDS: one row tile up to 128 rows, row tiles of 128 from 257 rows on and for n % 4 != 0), the
+// resident kernel (5 to 16 m tiles) and the dispatch.
 #include "basd_frag.h"
 
 namespace basd {
@@ -48,18 +51,277 @@ __device__ __forceinline__ void pb_split2(float x0, float x1, unsigned int& hi, 
   mid = __builtin_bit_cast(unsigned int, m);
 }
 
+constexpr int PB_BPITCH = 208;              // bytes between the k rows of the staged W tile (96 bf16 = 192 + 16 pad)
+
+// ---- the pieces every kernel of this file is made of, each written once -------------------------------------------
+// `out` and `rowdot` have the same bits whichever kernel the dispatch picks (no atomics, a fixed slot order), so a
+// training run does not change when a dispatch boundary moves.  That holds because the arithmetic of a tile -- the
+// masked (hi, mid) split of both operands, K ascending in steps of 32 with the MFMAs in the order hi hi, hi mid, mid hi,
+// the epilogue's residual, scale, fmaf chain and quad reduction, the six row-dot slots added in order -- is THIS code
+// in every kernel.  An edit here reaches all of them; an edit that forks one of them breaks the rule.
+
+// Row scales 2 gl sqrt(a) of the rows r0 .. r0 + trows - 1 (0 for padded rows) and the zeroed [PB_WAVES][rows] row dots
+__device__ __forceinline__ void pb_rows_init(float* s_c, float* s_dot, int rows, int tid, int threads,
+                                             const float* __restrict__ a_b, float c2, int r0, int trows, int n) {
+  for (int i = tid; i < rows; i += threads) {
+#pragma unroll
+    for (int j = 0; j < PB_WAVES; ++j) s_dot[j * rows + i] = 0.f;
+    s_c[i] = (i < trows && r0 + i < n) ? c2 * __builtin_amdgcn_sqrtf(a_b[r0 + i]) : 0.f;
+  }
+}
+
+// rowdot = the PB_WAVES slices added in slice order (the caller's barrier has made them complete)
+__device__ __forceinline__ void pb_rows_sum(const float* s_dot, int rows, int tid, int threads,
+                                            float* __restrict__ rowdot_b, int r0, int trows, int n) {
+  for (int i = tid; i < trows; i += threads) {
+    if (r0 + i < n) {
+      float t = 0.f;
+#pragma unroll
+      for (int j = 0; j < PB_WAVES; ++j) t += s_dot[j * rows + i];
+      rowdot_b[r0 + i] = t;
+    }
+  }
+}
+
+// Staging of one K step of the factor's rows r0 .. r0 + 16 MT - 1 into the (hi, mid) planes at `dst` ([2 planes]
+// [MT * 16 rows][PB_ROWB]): item = (row, k octet).  load() issues the global loads only -- the callers put it BEFORE
+// the MFMAs of the current step and store() (the split and the LDS writes) after them, so the L2 round trip hides under
+// the matrix work.  Offsets are computed once per item; a K step only adds a uniform base.  Every address is clamped
+// into the matrix (rows >= n to row n - 1, the end of the last row to the last 16 / 4 bytes) and what was clamped is
+// zeroed in store().
+// VEC4: n % 4 == 0 and a 16-byte aligned factor, every load is 16 bytes wide; otherwise 4-byte loads (the rows of the
+// factor are not aligned), same values.
+// SELECT: how the clamped values are zeroed.  true: a select per element.  false: a multiply by 0 / 1 per 16 bytes,
+// applied in the last K step / for the padded rows -- the form the direct kernel was measured and profiled with.  The
+// two give the same planes for a finite factor (x * 1 = x; 0 and -0 split into planes whose products add nothing to an
+// accumulator) and differ for a non-finite one (inf * 0), so they are kept apart and not unified.
+template <int MT, bool VEC4, bool SELECT>
+struct PbStageA {
+  static constexpr int ITEMS = (MT * 16 * 4 + PB_THREADS - 1) / PB_THREADS;     // items per thread and K step
+  float v[ITEMS][8];
+  unsigned off[ITEMS];
+  unsigned a_last;
+
+  __device__ __forceinline__ void init(int tid, int r0, int n) {
+    a_last = (unsigned)n * (unsigned)n - (VEC4 ? 4u : 1u);
+#pragma unroll
+    for (int it = 0; it < ITEMS; ++it) {
+      const int item = tid + PB_THREADS * it;
+      const int row = r0 + (item >> 2), oct = item & 3;
+      off[it] = (unsigned)(row < n ? row : n - 1) * (unsigned)n + (unsigned)(oct * 8);
+    }
+  }
+  __device__ __forceinline__ void load(const float* __restrict__ A, int ks) {
+    const unsigned kbase = (unsigned)ks * 32u;
+#pragma unroll
+    for (int it = 0; it < ITEMS; ++it) {
+      const unsigned o0 = off[it] + kbase;
+      if constexpr (VEC4) {
+        const unsigned o1 = o0 + 4u;
+        const float4 v0 = *reinterpret_cast<const float4*>(A + (o0 < a_last ? o0 : a_last));
+        const float4 v1 = *reinterpret_cast<const float4*>(A + (o1 < a_last ? o1 : a_last));
+        v[it][0] = v0.x; v[it][1] = v0.y; v[it][2] = v0.z; v[it][3] = v0.w;
+        v[it][4] = v1.x; v[it][5] = v1.y; v[it][6] = v1.z; v[it][7] = v1.w;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const unsigned oj = o0 + (unsigned)j;
+          v[it][j] = A[oj < a_last ? oj : a_last];
+        }
+      }
+    }
+  }
+  __device__ __forceinline__ void store(unsigned char* dst, int tid, int r0, int n, int ks) const {
+    constexpr int PLANE = MT * 16 * PB_ROWB;
+    const bool tail = (ks + 1) * 32 > n;                   // uniform
+#pragma unroll
+    for (int it = 0; it < ITEMS; ++it) {
+      const int item = tid + PB_THREADS * it;
+      const int row = item >> 2, oct = item & 3;
+      if (item < MT * 16 * 4) {
+        const int k0 = ks * 32 + oct * 8;
+        const bool rok = r0 + row < n;
+        float x[8];
+        if constexpr (SELECT) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) x[j] = (rok && k0 + j < n) ? v[it][j] : 0.f;
+        } else {
+          const float m0 = (rok && (!tail || k0 + 4 <= n)) ? 1.f : 0.f;
+          const float m1 = (rok && (!tail || k0 + 8 <= n)) ? 1.f : 0.f;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) x[j] = v[it][j] * (j < 4 ? m0 : m1);
+        }
+        uint4 hi, mid;
+        pb_split2(x[0], x[1], hi.x, mid.x); pb_split2(x[2], x[3], hi.y, mid.y);
+        pb_split2(x[4], x[5], hi.z, mid.z); pb_split2(x[6], x[7], hi.w, mid.w);
+        const unsigned lo = (unsigned)row * PB_ROWB + (unsigned)oct * 16;
+        *reinterpret_cast<uint4*>(dst + lo) = hi;
+        *reinterpret_cast<uint4*>(dst + PLANE + lo) = mid;
+      }
+    }
+  }
+};
+
+// The W tile of a K step ([32 k rows][96 columns from c0 on] fp32, 12 KiB) goes global -> registers (16-byte loads, 384
+// contiguous bytes per row: two per thread) -> bf16 (hi, mid) planes in LDS, row-major with the k rows PB_BPITCH bytes
+// apart; a wave's B fragment comes out of the transposing read (pb_read_b_tr).  (The direct kernel fetches the fragment
+// with eight 4-byte loads per lane, 64-byte segments: 2.2 TB/s of such requests was all the 1.08 ms it took.)
+// The resident kernel stages its own, 128 columns wide and PBR_PF steps ahead (wload / wstore there).
+struct PbStageW {
+  float4 v[2];
+
+  __device__ __forceinline__ void load(const float* __restrict__ W, int tid, int ks, int c0, int n, int d) {
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      const int item = tid + PB_THREADS * it;              // 768 items = 32 rows x 24 quads
+      const int row = item / 24, q = item - row * 24;
+      const int kr = ks * 32 + row, cc = c0 + 4 * q;
+      const bool ok = kr < n && cc < d;
+      v[it] = *reinterpret_cast<const float4*>(W + (size_t)(ok ? kr : 0) * d + (ok ? cc : 0));
+      if (!ok) v[it] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+  __device__ __forceinline__ void store(unsigned char* bbuf, int tid) const {
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      const int item = tid + PB_THREADS * it;
+      const int row = item / 24, q = item - row * 24;
+      uint2 hi, mid;
+      pb_split2(v[it].x, v[it].y, hi.x, mid.x); pb_split2(v[it].z, v[it].w, hi.y, mid.y);
+      const unsigned lo = (unsigned)row * PB_BPITCH + (unsigned)q * 8;
+      *reinterpret_cast<uint2*>(bbuf + lo) = hi;
+      *reinterpret_cast<uint2*>(bbuf + 32 * PB_BPITCH + lo) = mid;
+    }
+  }
+};
+
+// B fragment of a wave out of a staged W tile: tr_cons of basd_frag.h on the hi and the mid plane, on a byte pitch.
+// Lane holds column 16 wave + li, k rows 8 g4 + 0..7; li = lane & 15 and g4 = lane >> 4 are the caller's (a helper that
+// derives them from the thread id again reorders the code around it).
+__device__ __forceinline__ void pb_read_b_tr(const unsigned char* tile, int pitch, int plane, int li, int g4, int wave,
+                                             bf16x8& bh, bf16x8& bm) {
+  const int qq = li >> 2, pp = li & 3;
+  const unsigned char* b0 = tile + (size_t)(g4 * 8 + qq) * pitch + (size_t)(wave * 16 + 4 * pp) * 2;
+  const v4s h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)b0);
+  const v4s h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(b0 + 4 * pitch));
+  const v4s m0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(b0 + plane));
+  const v4s m1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(b0 + plane + 4 * pitch));
+  bh = (bf16x8){h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+  bm = (bf16x8){m0[0], m0[1], m0[2], m0[3], m1[0], m1[1], m1[2], m1[3]};
+}
+
+// One K step of a strip: A fragments (ap = this lane's 16 bytes of m tile 0 in the hi plane; the mid plane `plane`
+// bytes, m tile i `i * tile` bytes further) in two batches of (MT + 1) / 2 tiles.  All 16-byte fragment reads of a batch
+// are issued together (one exposed LDS latency per batch; a fence per tile pair exposed it MT / 2 times per K step:
+// 4.8 k cycles per step measured with in-kernel stamps against 0.6 k of matrix work), the fence between the batches
+// keeps the scheduler from hoisting the second batch on top of the first (registers).
+template <int MT>
+__device__ __forceinline__ void pb_mfma_step(const unsigned char* ap, int plane, int tile, const bf16x8& bh,
+                                             const bf16x8& bm, f32x4 (&acc)[MT]) {
+  constexpr int HB = (MT + 1) / 2;
+#pragma unroll
+  for (int hb = 0; hb < 2; ++hb) {
+    bf16x8 fh[HB], fm[HB];
+#pragma unroll
+    for (int j = 0; j < HB; ++j) {
+      const int i = hb * HB + j < MT ? hb * HB + j : MT - 1;
+      fh[j] = *reinterpret_cast<const bf16x8*>(ap + (size_t)i * tile);
+      fm[j] = *reinterpret_cast<const bf16x8*>(ap + plane + (size_t)i * tile);
+    }
+#pragma unroll
+    for (int j = 0; j < HB; ++j) {
+      const int i = hb * HB + j;
+      if (i < MT) {
+        acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[j], bh, acc[i], 0, 0, 0);
+        acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[j], bm, acc[i], 0, 0, 0);
+        acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fm[j], bh, acc[i], 0, 0, 0);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// ---- epilogue.  acc[i][r] = P at row r0 + 16 i + 4 (lane >> 4) + r, column 16 s0 + (lane & 15): one value per lane
+// and row -- consumed in that layout the residual costs a 4-byte load, a 4-byte store and a 16-lane reduction per
+// element group (measured: 0.8 of 1.2 ms).  Instead the wave parks one 16 x 16 tile at a time in its own 1 KiB of
+// LDS and reads it back row-wise: 16 bytes per lane, 64 contiguous bytes per row segment for the W load and the
+// store, a 4-lane reduction per row.
+// One parked tile: residual of the row chunk against wv (the fp32 W of the same 4 columns), scaled by cr and stored at
+// O + off when ok; returns the chunk's <R, W>, summed over the four lanes of the row (0 when not ok).
+template <typename TO>
+__device__ __forceinline__ float pb_epilogue_tile(const f32x4& acc, float* park, int lane, const float4& wv, float cr,
+                                                  bool ok, TO* __restrict__ O, unsigned off) {
+  const int col = lane & 15, g4 = lane >> 4, prow = lane >> 2, pch = lane & 3;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) park[(g4 * 4 + r) * 16 + col] = acc[r];
+  // wave-private tile: the wave's own LDS writes precede its reads (in order), no barrier
+  const float4 pv = *reinterpret_cast<const float4*>(park + prow * 16 + pch * 4);
+  const float4 rv = make_float4(wv.x - pv.x, wv.y - pv.y, wv.z - pv.z, wv.w - pv.w);
+  float dot = ok ? fmaf(rv.x, wv.x, fmaf(rv.y, wv.y, fmaf(rv.z, wv.z, rv.w * wv.w))) : 0.f;
+  if (ok) {
+    if constexpr (sizeof(TO) == 4) {
+      *reinterpret_cast<float4*>(O + off) = make_float4(cr * rv.x, cr * rv.y, cr * rv.z, cr * rv.w);
+    } else {
+      uint2 o;
+      o.x = pack_bf16_bits(cr * rv.x, cr * rv.y);
+      o.y = pack_bf16_bits(cr * rv.z, cr * rv.w);
+      *reinterpret_cast<uint2*>(O + off) = o;
+    }
+  }
+  dot += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(dot), 0xB1, 0xF, 0xF, true));     // quad_perm 1,0,3,2
+  dot += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(dot), 0x4E, 0xF, 0xF, true));     // quad_perm 2,3,0,1
+  return dot;
+}
+
+// The MT tiles of strip s0 (`has`: the strip exists), rows r0 .. r0 + trows - 1 of the matrix (trows <= 16 MT; rows of
+// other row tiles and rows >= n are never stored), in two batches: the W loads of a batch are in flight together.
+// What differs between the kernels stays with the caller: sink(i, lrow, dot) takes the row dot of tile i, local row
+// lrow (every lane of the row's quad holds it).
+template <int MT, typename TO, typename Sink>
+__device__ __forceinline__ void pb_epilogue_strip(const f32x4 (&acc)[MT], float* park, int lane, bool has, int s0,
+                                                  int r0, int trows, int n, int d, const float* __restrict__ W,
+                                                  TO* __restrict__ O, const float* s_c, Sink&& sink) {
+  const int prow = lane >> 2, pch = lane & 3;              // row-wise walk: 16 rows x 4 chunks of 4 columns
+  const int pcol = s0 * 16 + pch * 4;
+  constexpr int H0 = (MT + 1) / 2;
+#pragma unroll
+  for (int hb = 0; hb < 2; ++hb) {
+    float4 wq[H0];
+#pragma unroll
+    for (int j = 0; j < H0; ++j) {
+      const int lrow = (hb * H0 + j) * 16 + prow, row = r0 + lrow;
+      const bool ok = has && lrow < trows && row < n;
+      wq[j] = *reinterpret_cast<const float4*>(W + (unsigned)(ok ? row : 0) * (unsigned)d + (unsigned)(ok ? pcol : 0));
+    }
+#pragma unroll
+    for (int j = 0; j < H0; ++j) {
+      const int i = hb * H0 + j;
+      if (i < MT) {
+        const int lrow = i * 16 + prow, row = r0 + lrow;
+        const bool ok = has && lrow < trows && row < n;
+        const unsigned off = (unsigned)(ok ? row : 0) * (unsigned)d + (unsigned)(ok ? pcol : 0);      // 32-bit: n d < 2^31
+        sink(i, lrow, pb_epilogue_tile<TO>(acc[i], park, lane, wq[j], s_c[lrow], ok, O, off));
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// ---- the direct form: up to three m tiles (n <= 48) ---------------------------------------------------------------------
+// W straight from global memory as the B fragment, the factor double buffered; LDS: 4 planes of a K step + the row dots
+// and scales, the parked epilogue tiles (6 KiB) alias the operand buffers, which are idle then (MT >= 2: they fit).
+template <int MT>
+constexpr size_t pb_direct_lds() { return (size_t)4 * MT * 16 * PB_ROWB + (size_t)MT * 16 * 4 * (PB_WAVES + 1); }
+
 template <int MT, typename TO>      // MT = m tiles (16 rows each) >= ceil(n / 16)
 __global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3))) void procrustes_bwd_side_kernel(
     const float* __restrict__ fac, const float* __restrict__ w, const float* __restrict__ a,
     const float* __restrict__ gl, int n, int d, TO* __restrict__ out, float* __restrict__ rowdot) {
   extern __shared__ __align__(16) unsigned char smem[];
   constexpr int PLANE = MT * 16 * PB_ROWB;                 // one bf16 plane of one K step
-  constexpr int ITEMS = (MT * 16 * 4 + PB_THREADS - 1) / PB_THREADS;         // staging items (row, k octet) per thread and K step
   unsigned char* abuf = smem;                              // [2 buffers][2 planes][MT * 16 rows][PB_ROWB]
   float* s_dotw = reinterpret_cast<float*>(smem + 4 * PLANE);  // [waves][MT * 16] row dots, one slice per wave
-  float* s_c = s_dotw + PB_WAVES * MT * 16;                           // [MT * 16] row scales 2 gl sqrt(a)
-  float* s_park = reinterpret_cast<float*>(abuf);              // [waves][16 rows][16 columns] epilogue tile: the operand
-                                                               // buffers are idle then (80 KiB per workgroup: two per CU)
+  float* s_c = s_dotw + PB_WAVES * MT * 16;                    // [MT * 16] row scales 2 gl sqrt(a)
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float* A = fac + (size_t)b * n * n;
   const float* W = w + (size_t)b * n * d;
@@ -67,58 +329,9 @@ __global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
   const int ksteps = (n + 31) >> 5;
   const int strips = d >> 4;
   const float c2 = 2.f * gl[b];
-  for (int i = tid; i < MT * 16; i += PB_THREADS) {
-#pragma unroll
-    for (int wv_ = 0; wv_ < PB_WAVES; ++wv_) s_dotw[wv_ * MT * 16 + i] = 0.f;
-    s_c[i] = i < n ? c2 * __builtin_amdgcn_sqrtf(a[(size_t)b * n + i]) : 0.f;
-  }
-
-  // Staging of one K step of A in two halves: the global loads (branch-free: rows / columns beyond n read a clamped,
-  // valid address and are zeroed by a select) are issued BEFORE the MFMAs of the current step, the split into the two
-  // bf16 planes and the LDS writes follow them -- the L2 round trip hides under the matrix work.
-  // n % 4 == 0 and a 16-byte aligned factor (checked by the C entry): every load is 16 bytes wide.  Offsets are
-  // computed once per item = (row, k octet); a K step only adds a uniform base.  Loads that would leave the matrix
-  // (rows >= n of the padded m tiles, the columns >= n of the last K step) are clamped to its last 16 bytes and the
-  // values zeroed by a mask -- applied in the last K step / for the padded rows only.
-  float4 sa[ITEMS][2];
-  unsigned sa_off[ITEMS];
-  const unsigned a_last = (unsigned)n * (unsigned)n - 4u;
-#pragma unroll
-  for (int it = 0; it < ITEMS; ++it) {
-    const int item = tid + PB_THREADS * it;
-    const int row = item >> 2, oct = item & 3;
-    sa_off[it] = (unsigned)(row < n ? row : n - 1) * (unsigned)n + (unsigned)(oct * 8);
-  }
-  auto stage_load = [&](int ks) {
-    const unsigned kbase = (unsigned)ks * 32u;
-#pragma unroll
-    for (int it = 0; it < ITEMS; ++it) {
-      const unsigned o0 = sa_off[it] + kbase, o1 = o0 + 4u;
-      sa[it][0] = *reinterpret_cast<const float4*>(A + (o0 < a_last ? o0 : a_last));
-      sa[it][1] = *reinterpret_cast<const float4*>(A + (o1 < a_last ? o1 : a_last));
-    }
-  };
-  auto stage_store = [&](int ks, int buf) {
-    unsigned char* dst = abuf + (size_t)buf * 2 * PLANE;
-    const bool tail = (ks + 1) * 32 > n;                   // uniform
-#pragma unroll
-    for (int it = 0; it < ITEMS; ++it) {
-      const int item = tid + PB_THREADS * it;
-      const int row = item >> 2, oct = item & 3;
-      if (item < MT * 16 * 4) {
-        float4 v0 = sa[it][0], v1 = sa[it][1];
-        const int k0 = ks * 32 + oct * 8;
-        const float m0 = (row < n && (!tail || k0 + 4 <= n)) ? 1.f : 0.f;
-        const float m1 = (row < n && (!tail || k0 + 8 <= n)) ? 1.f : 0.f;
-        uint4 hi, mid;
-        pb_split2(v0.x * m0, v0.y * m0, hi.x, mid.x); pb_split2(v0.z * m0, v0.w * m0, hi.y, mid.y);
-        pb_split2(v1.x * m1, v1.y * m1, hi.z, mid.z); pb_split2(v1.z * m1, v1.w * m1, hi.w, mid.w);
-        const unsigned lo = (unsigned)row * PB_ROWB + (unsigned)oct * 16;
-        *reinterpret_cast<uint4*>(dst + lo) = hi;
-        *reinterpret_cast<uint4*>(dst + PLANE + lo) = mid;
-      }
-    }
-  };
+  pb_rows_init(s_c, s_dotw, MT * 16, tid, PB_THREADS, a + (size_t)b * n, c2, 0, MT * 16, n);
+  PbStageA<MT, true, false> sa;                            // n % 4 == 0, 16-byte aligned factor (checked by the C entry)
+  sa.init(tid, 0, n);
 
   for (int g0 = 0; g0 < strips; g0 += PB_WAVES) {          // column groups of PB_WAVES strips (96 columns), one per wave
     const int s0 = g0 + wave;
@@ -138,9 +351,9 @@ __global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
       }
     };
     __syncthreads();                                       // previous group's fragment reads are done
-    stage_load(0);
+    sa.load(A, 0);
     fetch_b(0);
-    stage_store(0, 0);
+    sa.store(abuf, tid, 0, n, 0);
     __syncthreads();
     f32x4 acc[MT];
 #pragma unroll
@@ -168,222 +381,99 @@ __global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
       const bool more = ks + 1 < ksteps;
       if (more) {                                          // next step's operands: loads only, consumed after the MFMAs
         fetch_b(ks + 1);
-        stage_load(ks + 1);
+        sa.load(A, ks + 1);
       }
-      // A fragments in two batches of (MT + 1) / 2 tiles: all 16-byte fragment reads of a batch are issued together (one
-      // exposed LDS latency per batch; a fence per tile pair exposed it MT / 2 times per K step: 4.8 k cycles per step
-      // measured with in-kernel stamps against 0.6 k of matrix work), the fence between the batches keeps the
-      // scheduler from hoisting the second batch on top of the first (registers)
-      const unsigned char* ap = abuf + (size_t)buf * 2 * PLANE + (size_t)(lane & 15) * PB_ROWB + (lane >> 4) * 16;
-      constexpr int HB = (MT + 1) / 2;
-#pragma unroll
-      for (int hb = 0; hb < 2; ++hb) {
-        bf16x8 fh[HB], fm[HB];
-#pragma unroll
-        for (int j = 0; j < HB; ++j) {
-          const int i = hb * HB + j < MT ? hb * HB + j : MT - 1;
-          fh[j] = *reinterpret_cast<const bf16x8*>(ap + (size_t)i * 16 * PB_ROWB);
-          fm[j] = *reinterpret_cast<const bf16x8*>(ap + PLANE + (size_t)i * 16 * PB_ROWB);
-        }
-#pragma unroll
-        for (int j = 0; j < HB; ++j) {
-          const int i = hb * HB + j;
-          if (i < MT) {
-            acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[j], bh, acc[i], 0, 0, 0);
-            acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[j], bm, acc[i], 0, 0, 0);
-            acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fm[j], bh, acc[i], 0, 0, 0);
-          }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      if (more) stage_store(ks + 1, buf ^ 1);
+      pb_mfma_step<MT>(abuf + (size_t)buf * 2 * PLANE + (size_t)(lane & 15) * PB_ROWB + (lane >> 4) * 16, PLANE,
+                       16 * PB_ROWB, bh, bm, acc);
+      if (more) sa.store(abuf + (size_t)(buf ^ 1) * 2 * PLANE, tid, 0, n, ks + 1);
       __syncthreads();                                     // buffer `buf` may be overwritten, `buf ^ 1` is complete
     }
-    // ---- epilogue.  acc[i][r] = P at row 16 i + 4 (lane >> 4) + r, column 16 s0 + (lane & 15): one value per lane
-    // and row -- consumed in that layout the residual costs a 4-byte load, a 4-byte store and a 16-lane reduction per
-    // element group (measured: 0.8 of 1.2 ms).  Instead the wave parks one 16 x 16 tile at a time in its own 1 KiB of
-    // LDS and reads it back row-wise: 16 bytes per lane, 64 contiguous bytes per row segment for the W load and the
-    // store, a 4-lane reduction per row.  All W loads of the strip are issued before the first tile is processed.
-    float* park = s_park + wave * 256;
-    const int g4 = lane >> 4;
-    const int prow = lane >> 2, pch = lane & 3;            // row-wise walk: 16 rows x 4 chunks of 4 columns
-    const int pcol = s0 * 16 + pch * 4;
-    constexpr int H0 = (MT + 1) / 2;                       // tiles per batch: the W loads of a batch are in flight together
-#pragma unroll
-    for (int hb = 0; hb < 2; ++hb) {
-      constexpr int HN = H0;
-      float4 wq[HN];
-#pragma unroll
-      for (int j = 0; j < HN; ++j) {
-        const int i = hb * H0 + j;
-        const int row = i * 16 + prow;
-        const bool ok = has && row < n && i < MT;
-        wq[j] = *reinterpret_cast<const float4*>(W + (unsigned)(ok ? row : 0) * (unsigned)d + (unsigned)(ok ? pcol : 0));
-      }
-#pragma unroll
-      for (int j = 0; j < HN; ++j) {
-        const int i = hb * H0 + j;
-        if (i < MT) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) park[(g4 * 4 + r) * 16 + col] = acc[i][r];
-          // wave-private tile: the wave's own LDS writes precede its reads (in order), no barrier
-          const float4 pv = *reinterpret_cast<const float4*>(park + prow * 16 + pch * 4);
-          const int row = i * 16 + prow;
-          const bool ok = has && row < n;
-          const unsigned off = (unsigned)(ok ? row : 0) * (unsigned)d + (unsigned)(ok ? pcol : 0);
-          const float4 wv = wq[j];
-          const float cr = s_c[row];
-          const float4 rv = make_float4(wv.x - pv.x, wv.y - pv.y, wv.z - pv.z, wv.w - pv.w);
-          float dot = ok ? fmaf(rv.x, wv.x, fmaf(rv.y, wv.y, fmaf(rv.z, wv.z, rv.w * wv.w))) : 0.f;
-          if (ok) {
-            if constexpr (sizeof(TO) == 4) {
-              *reinterpret_cast<float4*>(O + off) = make_float4(cr * rv.x, cr * rv.y, cr * rv.z, cr * rv.w);
-            } else {
-              uint2 o;
-              o.x = pack_bf16_bits(cr * rv.x, cr * rv.y);
-              o.y = pack_bf16_bits(cr * rv.z, cr * rv.w);
-              *reinterpret_cast<uint2*>(O + off) = o;
-            }
-          }
-          dot += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(dot), 0xB1, 0xF, 0xF, true));     // quad_perm 1,0,3,2
-          dot += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(dot), 0x4E, 0xF, 0xF, true));     // quad_perm 2,3,0,1
-          if (pch == 0) s_dotw[wave * (MT * 16) + row] += c2 * dot;
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    pb_epilogue_strip<MT, TO>(acc, reinterpret_cast<float*>(abuf) + wave * 256, lane, has, s0, 0, MT * 16, n, d, W, O, s_c,
+                              [&](int, int lrow, float dot) {
+                                if ((lane & 3) == 0) s_dotw[wave * (MT * 16) + lrow] += c2 * dot;
+                              });
   }
   __syncthreads();
-  for (int i = tid; i < n; i += PB_THREADS) {
-    float t = 0.f;
-#pragma unroll
-    for (int wv_ = 0; wv_ < PB_WAVES; ++wv_) t += s_dotw[wv_ * MT * 16 + i];
-    rowdot[(size_t)b * n + i] = t;
-  }
+  pb_rows_sum(s_dotw, MT * 16, tid, PB_THREADS, rowdot + (size_t)b * n, 0, MT * 16, n);
 }
 
-constexpr int PB_BPITCH = 208;              // bytes between the k rows of the staged W tile (96 bf16 = 192 + 16 pad)
+// ---- the tiled form: W staged through LDS; a workgroup owns a row tile of MT m tiles of one matrix --------------------
+// The direct kernel with the B operand (W) staged through LDS -- see PbStageW.  One operand buffer each, two barriers per
+// K step.  Measured (1024 x [196, 196] x [196, 768], a whole matrix per workgroup): 1.04 vs 1.15 ms, the c4 shape 0.91
+// vs 1.01 -- the 4-byte fragment loads were a tenth of the time, not the bulk of it.  What is left is traffic: per
+// matrix W is read twice (operand + residual; 300 MB of W are in flight across the chip, the second read is not an L2
+// hit), the [n, n] factor once per 96-column group (8 x 154 KB), the gradient written once -- ~3 GB per launch at 3 - 4
+// TB/s.  Fewer, wider groups (12 waves, one workgroup per CU) would halve the factor's re-reads; keeping it resident
+// needs 154 KiB of bf16 planes: the resident kernel below, which took over from five m tiles on.
+// The kernel serves two dispatch ranges:
+// * WHOLE: one row tile is the whole matrix (tiles = 1, grid = batch), MT = 4 | 8: n = 49 .. 64, and up to 128 rows with
+//   fewer than 112 columns (launch_side) -- "the staged kernel" of the measurements in this file.  r0 = 0 is known to
+//   the compiler and the factor is masked in the direct kernel's form (PbStageA, SELECT = false): with r0 and the
+//   selects of the row-tiled form these shapes measured 1.4 - 3.9 % slower than before (1024 x 64 x 768: 0.1369 ->
+//   0.1388 ms, 1024 x 128 x 96: 0.0408 -> 0.0424), same bits;
+// * 257 <= n <= 1024, and every n % 4 != 0: row tiles of PBL_RT = 128 rows (MT = 8: 8 accumulator tiles per strip; a
+//   whole matrix would be 144 accumulator registers per lane at 576 rows), grid = batch x ceil(n / 128), the row tiles
+//   of a matrix adjacent in the grid so that they run together and share W in the caches (at batch-major order 256
+//   matrices x 1.8 MB of W would be re-read from HBM once per row tile).  The K loop runs over all n rows of W.
+// A row tile sees all d columns, so its row dots are complete inside the workgroup: each wave adds its column groups
+// in order into its own slice, the slices are added in wave order -- no atomics, bitwise reproducible.  Rows >= n of
+// the last tile and the K tail (n % 32) are zeroed on the way into LDS and never stored.
+// VEC4 = false (n % 4 != 0: the rows of the factor, and every matrix of the batch but the first, are not 16-byte
+// aligned -- 729 tokens of a /14 grid at 384 px) loads the factor with 4-byte loads; W, the gradient and the LDS
+// traffic are the same (d % 16 == 0 keeps their rows aligned).
+// LDS: 2 A planes + 2 W planes + 7 x 64 MT bytes of row dots / scales (MT = 8: 37376 bytes = 2 x 10240 + 2 x 6656 + 7 x
+// 512; two workgroups per CU); the parked epilogue tiles (6 KiB) alias the A planes, which are idle then.
+// Compiler's resource report (hipcc --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage; fp32 and bf16 output
+// alike; LDS is dynamic):
+//   direct <2>               VGPRs 110  AGPRs 0  scratch 0 bytes/lane  occupancy 3 waves/SIMD
+//   direct <4>               VGPRs 122  AGPRs 0  scratch 0 bytes/lane  occupancy 3 waves/SIMD
+//   tiled  <4, WHOLE>            VGPRs 108  AGPRs 0  scratch 0 bytes/lane  occupancy 3 waves/SIMD
+//   tiled  <8, WHOLE>            VGPRs 158  AGPRs 0  scratch 0 bytes/lane  occupancy 3 waves/SIMD
+//   tiled  <8, row tiles, VEC4>  VGPRs 160  AGPRs 0  scratch 0 bytes/lane  occupancy 3 waves/SIMD
+//   tiled  <8, row tiles, 4-byte loads>  VGPRs 162  AGPRs 0  scratch 0 bytes/lane  occupancy 3 waves/SIMD
+// (While the whole-matrix and the row-tiled form were two kernels: 106 / 158 for the former at MT = 4 / 8, 156 / 164 for
+// the latter.  Same bits and, against that build in one process, times inside its own bracket-to-bracket band:
+// profiles/procrustes_bwd_one_copy_bits.txt, profiles/procrustes_bwd_one_copy_ab.txt.)
+constexpr int PBL_MT = 8;                   // m tiles (16 rows each) of a row tile of the long form
+constexpr int PBL_RT = 16 * PBL_MT;         // rows of a row tile
 
-// The same kernel with the B operand (W) staged through LDS -- see the comment at `bload` below.  One operand buffer each
-// (52 KiB with the row dots: two workgroups per CU), two barriers per K step.  Measured (same box, 1024 x [196, 196] x
-// [196, 768]): 1.04 vs 1.15 ms, the c4 shape 0.91 vs 1.01 -- the 4-byte fragment loads were a tenth of the time, not the
-// bulk of it.  What is left is traffic: per matrix W is read twice (operand + residual; 300 MB of W are in flight
-// across the chip, the second read is not an L2 hit), the [n, n] factor once per 96-column group (8 x 154 KB), the
-// gradient written once -- ~3 GB per launch at 3 - 4 TB/s.  Fewer, wider groups (12 waves, one workgroup per CU) would
-// halve the factor's re-reads; keeping it resident needs 154 KiB of bf16 planes.
-template <int MT, typename TO>      // MT = m tiles (16 rows each) >= ceil(n / 16)
-__global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3))) void procrustes_bwd_side_lds_kernel(
+template <int MT>
+constexpr size_t pb_tiled_lds() {
+  return (size_t)2 * MT * 16 * PB_ROWB + (size_t)2 * 32 * PB_BPITCH + (size_t)MT * 16 * 4 * (PB_WAVES + 1);
+}
+
+template <int MT, typename TO, bool VEC4, bool WHOLE>
+__global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3))) void procrustes_bwd_side_tiled_kernel(
     const float* __restrict__ fac, const float* __restrict__ w, const float* __restrict__ a,
-    const float* __restrict__ gl, int n, int d, TO* __restrict__ out, float* __restrict__ rowdot) {
+    const float* __restrict__ gl, int n, int d, int tiles, TO* __restrict__ out, float* __restrict__ rowdot) {
   extern __shared__ __align__(16) unsigned char smem[];
   constexpr int PLANE = MT * 16 * PB_ROWB;                 // one bf16 plane of one K step
-  constexpr int ITEMS = (MT * 16 * 4 + PB_THREADS - 1) / PB_THREADS;         // staging items (row, k octet) per thread and K step
   unsigned char* abuf = smem;                              // [2 planes][MT * 16 rows][PB_ROWB]   (ONE buffer)
   unsigned char* bbuf = smem + 2 * PLANE;                  // [2 planes][32 k rows][PB_BPITCH]: the W tile of a K step
   float* s_dotw = reinterpret_cast<float*>(smem + 2 * PLANE + 2 * 32 * PB_BPITCH);  // [waves][MT * 16] row dots
-  float* s_c = s_dotw + PB_WAVES * MT * 16;                           // [MT * 16] row scales 2 gl sqrt(a)
-  float* s_park = reinterpret_cast<float*>(abuf);              // [waves][16 rows][16 columns] epilogue tile: the operand
-                                                               // buffers are idle then (80 KiB per workgroup: two per CU)
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  float* s_c = s_dotw + PB_WAVES * MT * 16;                // [MT * 16] row scales 2 gl sqrt(a)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = WHOLE ? (int)blockIdx.x : (int)blockIdx.x / tiles;
+  const int r0 = WHOLE ? 0 : ((int)blockIdx.x - b * tiles) * (MT * 16);   // first row of this tile; r0 < n
   const float* A = fac + (size_t)b * n * n;
   const float* W = w + (size_t)b * n * d;
   TO* O = out + (size_t)b * n * d;
   const int ksteps = (n + 31) >> 5;
   const int strips = d >> 4;
   const float c2 = 2.f * gl[b];
-  for (int i = tid; i < MT * 16; i += PB_THREADS) {
-#pragma unroll
-    for (int wv_ = 0; wv_ < PB_WAVES; ++wv_) s_dotw[wv_ * MT * 16 + i] = 0.f;
-    s_c[i] = i < n ? c2 * __builtin_amdgcn_sqrtf(a[(size_t)b * n + i]) : 0.f;
-  }
-
-  // Staging of one K step of A in two halves: the global loads (branch-free: rows / columns beyond n read a clamped,
-  // valid address and are zeroed by a select) are issued BEFORE the MFMAs of the current step, the split into the two
-  // bf16 planes and the LDS writes follow them -- the L2 round trip hides under the matrix work.
-  // n % 4 == 0 and a 16-byte aligned factor (checked by the C entry): every load is 16 bytes wide.  Offsets are
-  // computed once per item = (row, k octet); a K step only adds a uniform base.  Loads that would leave the matrix
-  // (rows >= n of the padded m tiles, the columns >= n of the last K step) are clamped to its last 16 bytes and the
-  // values zeroed by a mask -- applied in the last K step / for the padded rows only.
-  float4 sa[ITEMS][2];
-  unsigned sa_off[ITEMS];
-  const unsigned a_last = (unsigned)n * (unsigned)n - 4u;
-#pragma unroll
-  for (int it = 0; it < ITEMS; ++it) {
-    const int item = tid + PB_THREADS * it;
-    const int row = item >> 2, oct = item & 3;
-    sa_off[it] = (unsigned)(row < n ? row : n - 1) * (unsigned)n + (unsigned)(oct * 8);
-  }
-  auto stage_load = [&](int ks) {
-    const unsigned kbase = (unsigned)ks * 32u;
-#pragma unroll
-    for (int it = 0; it < ITEMS; ++it) {
-      const unsigned o0 = sa_off[it] + kbase, o1 = o0 + 4u;
-      sa[it][0] = *reinterpret_cast<const float4*>(A + (o0 < a_last ? o0 : a_last));
-      sa[it][1] = *reinterpret_cast<const float4*>(A + (o1 < a_last ? o1 : a_last));
-    }
-  };
-  auto stage_store = [&](int ks, int buf) {
-    unsigned char* dst = abuf;
-    const bool tail = (ks + 1) * 32 > n;                   // uniform
-#pragma unroll
-    for (int it = 0; it < ITEMS; ++it) {
-      const int item = tid + PB_THREADS * it;
-      const int row = item >> 2, oct = item & 3;
-      if (item < MT * 16 * 4) {
-        float4 v0 = sa[it][0], v1 = sa[it][1];
-        const int k0 = ks * 32 + oct * 8;
-        const float m0 = (row < n && (!tail || k0 + 4 <= n)) ? 1.f : 0.f;
-        const float m1 = (row < n && (!tail || k0 + 8 <= n)) ? 1.f : 0.f;
-        uint4 hi, mid;
-        pb_split2(v0.x * m0, v0.y * m0, hi.x, mid.x); pb_split2(v0.z * m0, v0.w * m0, hi.y, mid.y);
-        pb_split2(v1.x * m1, v1.y * m1, hi.z, mid.z); pb_split2(v1.z * m1, v1.w * m1, hi.w, mid.w);
-        const unsigned lo = (unsigned)row * PB_ROWB + (unsigned)oct * 16;
-        *reinterpret_cast<uint4*>(dst + lo) = hi;
-        *reinterpret_cast<uint4*>(dst + PLANE + lo) = mid;
-      }
-    }
-  };
+  pb_rows_init(s_c, s_dotw, MT * 16, tid, PB_THREADS, a + (size_t)b * n, c2, r0, MT * 16, n);
+  PbStageA<MT, VEC4, !WHOLE> sa;
+  PbStageW sb;
+  sa.init(tid, r0, n);
 
   for (int g0 = 0; g0 < strips; g0 += PB_WAVES) {          // column groups of PB_WAVES strips (96 columns), one per wave
     const int s0 = g0 + wave;
-    const bool has = s0 < strips;
-    const int col = (lane & 15);
-    const unsigned cs = has ? (unsigned)(s0 * 16 + col) : (unsigned)col;                // 32-bit offsets: n d < 2^31
-    // The W tile of a K step ([32 k rows][96 columns] fp32, 12 KiB) goes global -> registers (16-byte loads, 384
-    // contiguous bytes per row: two per thread) -> bf16 (hi, mid) planes in LDS, row-major with the k rows PB_BPITCH
-    // bytes apart; a wave's B fragment -- column 16 wave + (lane & 15), rows 8 (lane >> 4) + 0..7 -- comes out of the
-    // transposing read ds_read_b64_tr_b16.  (The version above fetched the fragment with eight 4-byte loads per lane,
-    // 64-byte segments: 2.2 TB/s of such requests was all the 1.08 ms it took.)
     const int c0 = g0 * 16;                                // first column of the group
-    float4 sb[2];
-    auto bload = [&](int ks) {
-#pragma unroll
-      for (int it = 0; it < 2; ++it) {
-        const int item = tid + PB_THREADS * it;            // 768 items = 32 rows x 24 quads
-        const int row = item / 24, q = item - row * 24;
-        const int kr = ks * 32 + row, cc = c0 + 4 * q;
-        const bool ok = kr < n && cc < d;
-        sb[it] = *reinterpret_cast<const float4*>(W + (size_t)(ok ? kr : 0) * d + (ok ? cc : 0));
-        if (!ok) sb[it] = make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    };
-    auto bstore = [&]() {
-#pragma unroll
-      for (int it = 0; it < 2; ++it) {
-        const int item = tid + PB_THREADS * it;
-        const int row = item / 24, q = item - row * 24;
-        uint2 hi, mid;
-        pb_split2(sb[it].x, sb[it].y, hi.x, mid.x); pb_split2(sb[it].z, sb[it].w, hi.y, mid.y);
-        const unsigned lo = (unsigned)row * PB_BPITCH + (unsigned)q * 8;
-        *reinterpret_cast<uint2*>(bbuf + lo) = hi;
-        *reinterpret_cast<uint2*>(bbuf + 32 * PB_BPITCH + lo) = mid;
-      }
-    };
-    __syncthreads();                                       // previous group's fragment reads are done
-    stage_load(0);
-    bload(0);
-    stage_store(0, 0);
-    bstore();
+    __syncthreads();                                       // previous group's fragment / parked-tile reads are done
+    sa.load(A, 0);
+    sb.load(W, tid, 0, c0, n, d);
+    sa.store(abuf, tid, r0, n, 0);
+    sb.store(bbuf, tid);
     __syncthreads();
     f32x4 acc[MT];
 #pragma unroll
@@ -391,111 +481,23 @@ __global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
     for (int ks = 0; ks < ksteps; ++ks) {
       const bool more = ks + 1 < ksteps;
       if (more) {                                          // next step's operands: loads only, stored after the MFMAs
-        bload(ks + 1);
-        stage_load(ks + 1);
+        sb.load(W, tid, ks + 1, c0, n, d);
+        sa.load(A, ks + 1);
       }
       bf16x8 bh, bm;
-      {                                                    // tr_cons of basd_frag.h on the hi and mid planes (byte pitch)
-        const int li = lane & 15, qq = li >> 2, pp = li & 3;
-        const unsigned char* b0 = bbuf + (size_t)((lane >> 4) * 8 + qq) * PB_BPITCH + (size_t)(wave * 16 + 4 * pp) * 2;
-        const v4s h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)b0);
-        const v4s h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(b0 + 4 * PB_BPITCH));
-        const v4s m0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(b0 + 32 * PB_BPITCH));
-        const v4s m1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(b0 + 32 * PB_BPITCH + 4 * PB_BPITCH));
-        bh = (bf16x8){h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-        bm = (bf16x8){m0[0], m0[1], m0[2], m0[3], m1[0], m1[1], m1[2], m1[3]};
-      }
-      // A fragments in two batches of (MT + 1) / 2 tiles: all 16-byte fragment reads of a batch are issued together (one
-      // exposed LDS latency per batch; a fence per tile pair exposed it MT / 2 times per K step: 4.8 k cycles per step
-      // measured with in-kernel stamps against 0.6 k of matrix work), the fence between the batches keeps the
-      // scheduler from hoisting the second batch on top of the first (registers)
-      const unsigned char* ap = abuf + (size_t)(lane & 15) * PB_ROWB + (lane >> 4) * 16;
-      constexpr int HB = (MT + 1) / 2;
-#pragma unroll
-      for (int hb = 0; hb < 2; ++hb) {
-        bf16x8 fh[HB], fm[HB];
-#pragma unroll
-        for (int j = 0; j < HB; ++j) {
-          const int i = hb * HB + j < MT ? hb * HB + j : MT - 1;
-          fh[j] = *reinterpret_cast<const bf16x8*>(ap + (size_t)i * 16 * PB_ROWB);
-          fm[j] = *reinterpret_cast<const bf16x8*>(ap + PLANE + (size_t)i * 16 * PB_ROWB);
-        }
-#pragma unroll
-        for (int j = 0; j < HB; ++j) {
-          const int i = hb * HB + j;
-          if (i < MT) {
-            acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[j], bh, acc[i], 0, 0, 0);
-            acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[j], bm, acc[i], 0, 0, 0);
-            acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fm[j], bh, acc[i], 0, 0, 0);
-          }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
+      pb_read_b_tr(bbuf, PB_BPITCH, 32 * PB_BPITCH, lane & 15, lane >> 4, wave, bh, bm);
+      pb_mfma_step<MT>(abuf + (size_t)(lane & 15) * PB_ROWB + (lane >> 4) * 16, PLANE, 16 * PB_ROWB, bh, bm, acc);
       __syncthreads();                                     // every wave has read the operands of step ks
-      if (more) { stage_store(ks + 1, 0); bstore(); }
+      if (more) { sa.store(abuf, tid, r0, n, ks + 1); sb.store(bbuf, tid); }
       __syncthreads();                                     // step ks + 1 is complete
     }
-    // ---- epilogue.  acc[i][r] = P at row 16 i + 4 (lane >> 4) + r, column 16 s0 + (lane & 15): one value per lane
-    // and row -- consumed in that layout the residual costs a 4-byte load, a 4-byte store and a 16-lane reduction per
-    // element group (measured: 0.8 of 1.2 ms).  Instead the wave parks one 16 x 16 tile at a time in its own 1 KiB of
-    // LDS and reads it back row-wise: 16 bytes per lane, 64 contiguous bytes per row segment for the W load and the
-    // store, a 4-lane reduction per row.  All W loads of the strip are issued before the first tile is processed.
-    float* park = s_park + wave * 256;
-    const int g4 = lane >> 4;
-    const int prow = lane >> 2, pch = lane & 3;            // row-wise walk: 16 rows x 4 chunks of 4 columns
-    const int pcol = s0 * 16 + pch * 4;
-    constexpr int H0 = (MT + 1) / 2;                       // tiles per batch: the W loads of a batch are in flight together
-#pragma unroll
-    for (int hb = 0; hb < 2; ++hb) {
-      constexpr int HN = H0;
-      float4 wq[HN];
-#pragma unroll
-      for (int j = 0; j < HN; ++j) {
-        const int i = hb * H0 + j;
-        const int row = i * 16 + prow;
-        const bool ok = has && row < n && i < MT;
-        wq[j] = *reinterpret_cast<const float4*>(W + (unsigned)(ok ? row : 0) * (unsigned)d + (unsigned)(ok ? pcol : 0));
-      }
-#pragma unroll
-      for (int j = 0; j < HN; ++j) {
-        const int i = hb * H0 + j;
-        if (i < MT) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) park[(g4 * 4 + r) * 16 + col] = acc[i][r];
-          // wave-private tile: the wave's own LDS writes precede its reads (in order), no barrier
-          const float4 pv = *reinterpret_cast<const float4*>(park + prow * 16 + pch * 4);
-          const int row = i * 16 + prow;
-          const bool ok = has && row < n;
-          const unsigned off = (unsigned)(ok ? row : 0) * (unsigned)d + (unsigned)(ok ? pcol : 0);
-          const float4 wv = wq[j];
-          const float cr = s_c[row];
-          const float4 rv = make_float4(wv.x - pv.x, wv.y - pv.y, wv.z - pv.z, wv.w - pv.w);
-          float dot = ok ? fmaf(rv.x, wv.x, fmaf(rv.y, wv.y, fmaf(rv.z, wv.z, rv.w * wv.w))) : 0.f;
-          if (ok) {
-            if constexpr (sizeof(TO) == 4) {
-              *reinterpret_cast<float4*>(O + off) = make_float4(cr * rv.x, cr * rv.y, cr * rv.z, cr * rv.w);
-            } else {
-              uint2 o;
-              o.x = pack_bf16_bits(cr * rv.x, cr * rv.y);
-              o.y = pack_bf16_bits(cr * rv.z, cr * rv.w);
-              *reinterpret_cast<uint2*>(O + off) = o;
-            }
-          }
-          dot += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(dot), 0xB1, 0xF, 0xF, true));     // quad_perm 1,0,3,2
-          dot += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(dot), 0x4E, 0xF, 0xF, true));     // quad_perm 2,3,0,1
-          if (pch == 0) s_dotw[wave * (MT * 16) + row] += c2 * dot;
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    pb_epilogue_strip<MT, TO>(acc, reinterpret_cast<float*>(abuf) + wave * 256, lane, s0 < strips, s0, r0, MT * 16, n, d,
+                              W, O, s_c, [&](int, int lrow, float dot) {
+                                if ((lane & 3) == 0) s_dotw[wave * (MT * 16) + lrow] += c2 * dot;
+                              });
   }
   __syncthreads();
-  for (int i = tid; i < n; i += PB_THREADS) {
-    float t = 0.f;
-#pragma unroll
-    for (int wv_ = 0; wv_ < PB_WAVES; ++wv_) t += s_dotw[wv_ * MT * 16 + i];
-    rowdot[(size_t)b * n + i] = t;
-  }
+  pb_rows_sum(s_dotw, MT * 16, tid, PB_THREADS, rowdot + (size_t)b * n, r0, MT * 16, n);
 }
 
 // g_a = (dot_s + dot_t) / (2 a)
@@ -507,11 +509,11 @@ __global__ __launch_bounds__(256) void procrustes_ga_kernel(const float* __restr
 }
 
 // ---- the resident form: 5 <= ceil(n / 16) <= 16 m tiles ------------------------------------------------------------
-// The staged kernel above re-reads, re-splits and re-stores the [n, n] factor once per 96-column group (8 times at
+// The tiled kernel above (one row tile: "the staged kernel") re-reads, re-splits and re-stores the [n, n] factor once per 96-column group (8 times at
 // d = 768) and puts two __syncthreads() -- each of which also drains the wave's outstanding global loads -- into every
 // K step, so every step exposes one memory round trip.  Here the factor is loaded, masked and split ONCE per workgroup
 // and its (hi, mid) planes stay in LDS for all column groups; what moves in the loop is W alone.
-// * A workgroup owns a ROW TILE of one matrix, MT <= 8 m tiles (the accumulator budget of the row-tiled kernel below),
+// * A workgroup owns a ROW TILE of one matrix, MT <= 8 m tiles (the accumulator budget of the tiled kernel),
 //   and runs over all d columns: its row dots are complete inside the workgroup (no atomics).  Tiles per matrix: the
 //   fewest that fit the 160 KiB of LDS -- one up to 128 rows, two up to 224 (196 rows: 7 + 6 m tiles), three above.
 //   A short tile runs the MFMAs of MT m tiles on rows zeroed in LDS (1 / 14 of the matrix work at 196 rows).
@@ -525,11 +527,10 @@ __global__ __launch_bounds__(256) void procrustes_ga_kernel(const float* __restr
 //   per thread) is loaded PBR_PF = 4 steps ahead into registers -- across group boundaries, so the epilogue of a group
 //   runs with the next group's tiles in flight --, split and stored into the other of two LDS buffers one step ahead.
 //   One barrier per step, and it orders LDS traffic only (lds_barrier): global loads stay in flight across it.
-// * Same arithmetic as the kernels above: per accumulator tile K ascends in steps of 32, three MFMAs per step in the
-//   order hi hi, hi mid, mid hi; the epilogue (fp32 W re-read, residual, scale, fmaf row dot over the 4-column chunk,
-//   quad reduction) is the same code, so `out` has the same bits.  Row dots: strip s is added to slot s % 6 in LDS, strips
-//   ascending, and the six slots are added in order -- the order of the kernels above, whose wave s % 6 owns strip s; so
-//   `rowdot` has the same bits too, and the step computes what it computed.  No atomics (see `pend` in the kernel).
+// * Same arithmetic as the kernels above: pb_mfma_step and pb_epilogue_strip are the code they run, so `out` has the
+//   same bits.  Row dots: strip s is added to slot s % 6 in LDS, strips ascending, and the six slots are added in order
+//   (pb_rows_sum) -- the order of the kernels above, whose wave s % 6 owns strip s; so `rowdot` has the same bits too,
+//   and the step computes what it computed.  No atomics (see `pend` in the kernel).
 // * Bounds: rows >= n and the rows of the other tiles are clamped to row n - 1 on the load and zeroed by a select, the
 //   K tail likewise (every load is clamped to the last 16 bytes of the matrix's own factor); W rows >= n and columns
 //   >= d of a ragged last group read element 0 of the matrix and are zeroed; nothing is stored outside [n, d].
@@ -544,6 +545,11 @@ constexpr int PBR_BPITCH = 304;              // bytes between the k rows of a st
 constexpr int PBR_PF = 4;                    // W tiles in flight (steps between a tile's global load and its LDS store)
 
 __host__ __device__ inline int pbr_apitch(int ksteps) { return ksteps * 64 + ((ksteps & 3) == 3 ? 48 : 16); }
+// LDS of a workgroup with m m tiles: resident factor planes + two W buffers + parked tiles + row scales and row-dot slots
+inline size_t pbr_lds(int m, int ksteps) {
+  return (size_t)2 * m * 16 * pbr_apitch(ksteps) + (size_t)4 * 32 * PBR_BPITCH + (size_t)PBR_WAVES * 1024 +
+         (size_t)m * 64 * (1 + PB_WAVES);
+}
 
 template <int MT, typename TO>      // MT = m tiles of the longest row tile
 __global__ __launch_bounds__(PBR_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void procrustes_bwd_side_resident_kernel(
@@ -616,11 +622,7 @@ __global__ __launch_bounds__(PBR_THREADS) __attribute__((amdgpu_waves_per_eu(2, 
 #pragma unroll
   for (int u = 0; u < PBR_PF; ++u) wnext(wr[u]);           // steps 0 .. PF - 1 are in flight under the factor's staging
 
-  for (int i = tid; i < MT * 16; i += PBR_THREADS) {
-    s_c[i] = (i < trows && r0 + i < n) ? c2 * __builtin_amdgcn_sqrtf(a[(size_t)b * n + r0 + i]) : 0.f;
-#pragma unroll
-    for (int j = 0; j < PB_WAVES; ++j) s_slot[j * MT * 16 + i] = 0.f;
-  }
+  pb_rows_init(s_c, s_slot, MT * 16, tid, PBR_THREADS, a + (size_t)b * n, c2, r0, trows, n);
 
   // ---- the factor slice, once: item = (row of the tile, k octet of 32 slots), two 16-byte loads each, four items in
   // flight per thread.  n % 4 == 0: a 16-byte load is inside the row or beyond it as a whole.
@@ -661,7 +663,7 @@ __global__ __launch_bounds__(PBR_THREADS) __attribute__((amdgpu_waves_per_eu(2, 
 
   f32x4 acc[MT];
   const int col = lane & 15, g4 = lane >> 4;
-  const int prow = lane >> 2, pch = lane & 3;              // epilogue's row-wise walk: 16 rows x 4 chunks of 4 columns
+  const int prow = lane >> 2, pch = lane & 3;              // the epilogue's row-wise walk (row of a tile, 4-column chunk)
   // Row dots in the order of the staged kernel, whose wave s % 6 adds strip s to its own slice, strips ascending, and
   // whose slices are added in wave order: strip s goes to slot s % 6 here as well.  The strips of waves 0 .. 5 of a
   // group fall into six different slots; those of waves 6 and 7 share a slot with waves 0 and 1 and come after them,
@@ -695,93 +697,21 @@ __global__ __launch_bounds__(PBR_THREADS) __attribute__((amdgpu_waves_per_eu(2, 
           wnext(wr[(u + 1) % PBR_PF]);                     // the step PF after it
         }
         bf16x8 bh, bm;
-        {                                                  // tr_cons of basd_frag.h on the hi and mid planes (byte pitch)
-          const int qq = col >> 2, pp = col & 3;
-          const unsigned char* b0 = bbuf + (size_t)buf * 2 * BPLANE + (size_t)(g4 * 8 + qq) * PBR_BPITCH +
-                                    (size_t)(wave * 16 + 4 * pp) * 2;
-          const v4s h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)b0);
-          const v4s h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(b0 + 4 * PBR_BPITCH));
-          const v4s m0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(b0 + BPLANE));
-          const v4s m1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(b0 + BPLANE + 4 * PBR_BPITCH));
-          bh = (bf16x8){h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-          bm = (bf16x8){m0[0], m0[1], m0[2], m0[3], m1[0], m1[1], m1[2], m1[3]};
-        }
-        // A fragments of K step ks out of the resident planes, in two batches (registers), as in the kernels above
-        const unsigned char* ap = abuf + (size_t)col * AP + (size_t)ks * 64 + g4 * 16;
-        constexpr int HB = (MT + 1) / 2;
-#pragma unroll
-        for (int hb = 0; hb < 2; ++hb) {
-          bf16x8 fh[HB], fm[HB];
-#pragma unroll
-          for (int j = 0; j < HB; ++j) {
-            const int i = hb * HB + j < MT ? hb * HB + j : MT - 1;
-            fh[j] = *reinterpret_cast<const bf16x8*>(ap + (size_t)i * 16 * AP);
-            fm[j] = *reinterpret_cast<const bf16x8*>(ap + APLANE + (size_t)i * 16 * AP);
-          }
-#pragma unroll
-          for (int j = 0; j < HB; ++j) {
-            const int i = hb * HB + j;
-            if (i < MT) {
-              acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[j], bh, acc[i], 0, 0, 0);
-              acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[j], bm, acc[i], 0, 0, 0);
-              acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fm[j], bh, acc[i], 0, 0, 0);
-            }
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
+        pb_read_b_tr(bbuf + (size_t)buf * 2 * BPLANE, PBR_BPITCH, BPLANE, col, g4, wave, bh, bm);
+        // A fragments of K step ks out of the resident planes
+        pb_mfma_step<MT>(abuf + (size_t)col * AP + (size_t)ks * 64 + g4 * 16, APLANE, 16 * AP, bh, bm, acc);
         if (++ks == ksteps) {
-          // ---- epilogue of group g, the code of the kernels above: acc[i][r] = P at row r0 + 16 i + 4 (lane >> 4) + r,
-          // column 16 s0 + (lane & 15); the wave parks one tile at a time in its own 1 KiB and reads it back row-wise
+          // ---- epilogue of group g (pb_epilogue_strip); the accumulators are zeroed for the next group on the way
           const int s0 = g * PBR_WAVES + wave;
           const bool has = s0 < strips;
-          const int pcol = s0 * 16 + pch * 4;
           const int slot = s0 % PB_WAVES;
           const bool later = has && wave >= PB_WAVES;      // wave-uniform
           if (later) pend_slot = slot;
-          constexpr int H0 = (MT + 1) / 2;                 // tiles per batch: the W loads of a batch are in flight together
-#pragma unroll
-          for (int hb = 0; hb < 2; ++hb) {
-            float4 wq[H0];
-#pragma unroll
-            for (int j = 0; j < H0; ++j) {
-              const int lrow = (hb * H0 + j) * 16 + prow, row = r0 + lrow;
-              const bool ok = has && lrow < trows && row < n;
-              wq[j] = *reinterpret_cast<const float4*>(W + (unsigned)(ok ? row : 0) * (unsigned)d + (unsigned)(ok ? pcol : 0));
-            }
-#pragma unroll
-            for (int j = 0; j < H0; ++j) {
-              const int i = hb * H0 + j;
-              if (i < MT) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) park[(g4 * 4 + r) * 16 + col] = acc[i][r];
-                // wave-private tile: the wave's own LDS writes precede its reads (in order), no barrier
-                const float4 pv = *reinterpret_cast<const float4*>(park + prow * 16 + pch * 4);
-                const int lrow = i * 16 + prow, row = r0 + lrow;
-                const bool ok = has && lrow < trows && row < n;      // rows of other tiles and rows >= n: never stored
-                const unsigned off = (unsigned)(ok ? row : 0) * (unsigned)d + (unsigned)(ok ? pcol : 0);
-                const float4 wv = wq[j];
-                const float cr = s_c[lrow];
-                const float4 rv = make_float4(wv.x - pv.x, wv.y - pv.y, wv.z - pv.z, wv.w - pv.w);
-                float dot = ok ? fmaf(rv.x, wv.x, fmaf(rv.y, wv.y, fmaf(rv.z, wv.z, rv.w * wv.w))) : 0.f;
-                if (ok) {
-                  if constexpr (sizeof(TO) == 4) {
-                    *reinterpret_cast<float4*>(O + off) = make_float4(cr * rv.x, cr * rv.y, cr * rv.z, cr * rv.w);
-                  } else {
-                    uint2 o;
-                    o.x = pack_bf16_bits(cr * rv.x, cr * rv.y);
-                    o.y = pack_bf16_bits(cr * rv.z, cr * rv.w);
-                    *reinterpret_cast<uint2*>(O + off) = o;
-                  }
-                }
-                dot += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(dot), 0xB1, 0xF, 0xF, true));     // quad_perm 1,0,3,2
-                dot += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(dot), 0x4E, 0xF, 0xF, true));     // quad_perm 2,3,0,1
-                if (later) pend[i] = dot;
-                else if (has && pch == 0) s_slot[slot * MT * 16 + lrow] += c2 * dot;
-                acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-              }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-          }
+          pb_epilogue_strip<MT, TO>(acc, park, lane, has, s0, r0, trows, n, d, W, O, s_c, [&](int i, int lrow, float dot) {
+            if (later) pend[i] = dot;
+            else if (has && pch == 0) s_slot[slot * MT * 16 + lrow] += c2 * dot;
+            acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+          });
           ks = 0;
           ++g;
         }
@@ -792,23 +722,16 @@ __global__ __launch_bounds__(PBR_THREADS) __attribute__((amdgpu_waves_per_eu(2, 
   lds_barrier();
   flush();
   lds_barrier();
-  for (int i = tid; i < trows; i += PBR_THREADS) {
-    if (r0 + i < n) {
-      float s = 0.f;
-#pragma unroll
-      for (int j = 0; j < PB_WAVES; ++j) s += s_slot[j * MT * 16 + i];
-      rowdot[(size_t)b * n + r0 + i] = s;
-    }
-  }
+  pb_rows_sum(s_slot, MT * 16, tid, PBR_THREADS, rowdot + (size_t)b * n, r0, trows, n);
 }
 
 // Compiler's resource report (hipcc --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage; fp32 and bf16 output
-// alike but for MT = 7; LDS is dynamic: 2 x 16 MT x pitch factor planes + 38912 W tiles + 8192 parked tiles + 64 MT row
+// alike; LDS is dynamic, pbr_lds(): 2 x 16 MT x pitch factor planes + 38912 W tiles + 8192 parked tiles + 64 MT row
 // scales + 384 MT row-dot slots):
-//   MT = 5   VGPRs 124        AGPRs 0  scratch 0 bytes/lane  occupancy 2 waves/SIMD
-//   MT = 6   VGPRs 134        AGPRs 0  scratch 0 bytes/lane  occupancy 2 waves/SIMD
-//   MT = 7   VGPRs 140 / 138  AGPRs 0  scratch 0 bytes/lane  occupancy 2 waves/SIMD   (196 rows: 161344 bytes of LDS)
-//   MT = 8   VGPRs 148        AGPRs 0  scratch 0 bytes/lane  occupancy 2 waves/SIMD
+//   MT = 5   VGPRs 122  AGPRs 0  scratch 0 bytes/lane  occupancy 2 waves/SIMD
+//   MT = 6   VGPRs 134  AGPRs 0  scratch 0 bytes/lane  occupancy 2 waves/SIMD
+//   MT = 7   VGPRs 140  AGPRs 0  scratch 0 bytes/lane  occupancy 2 waves/SIMD   (196 rows: 161344 bytes of LDS)
+//   MT = 8   VGPRs 150  AGPRs 0  scratch 0 bytes/lane  occupancy 2 waves/SIMD
 // Measured on one MI355X against the staged kernel of the parent commit, both libraries loaded into one process, the
 // same inputs, alternated medians of 4 brackets of 10 launches (ms; the parent's own brackets differ by 0.005 - 0.026,
 // 0.061 at 128 rows):
@@ -826,6 +749,14 @@ __global__ __launch_bounds__(PBR_THREADS) __attribute__((amdgpu_waves_per_eu(2, 
 // that order changes `rowdot` by 6.6e-8 rel-L2 and with it every later step of a training run.)  `out` and `rowdot` have
 // the bits of the staged kernel at these and six smaller shapes, fp32 and bf16.  Up to four m tiles (c1: 64 tokens)
 // were not timed and stay on the kernels above.
+
+// one launch; a kernel that asks for more than the default 64 KiB of dynamic LDS has its limit raised once
+template <typename... P, typename... Args>
+static void launch_pb(void (*kernel)(P...), dim3 grid, int threads, size_t lds, hipStream_t st, Args... args) {
+  if (lds > 64 * 1024) allow_full_lds((const void*)kernel);
+  hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, st, args...);
+}
+
 template <typename TO>
 static int launch_side_resident(const float* fac, const float* w, const float* a, const float* gl, int batch, int n,
                                 int d, TO* out, float* rowdot, hipStream_t st) {
@@ -834,27 +765,22 @@ static int launch_side_resident(const float* fac, const float* w, const float* a
   size_t lds = 0;
   for (;; ++tiles) {                                       // the fewest row tiles whose resident planes fit
     m = (mt + tiles - 1) / tiles;
-    lds = (size_t)2 * m * 16 * pbr_apitch(ksteps) + (size_t)4 * 32 * PBR_BPITCH + (size_t)PBR_WAVES * 1024 + (size_t)m * 64 * (1 + PB_WAVES);
+    lds = pbr_lds(m, ksteps);
     if (lds <= 160 * 1024) break;
   }
   const dim3 grid((unsigned)((batch + 7) / 8) * 8u * (unsigned)tiles);
-#define BASD_PB_RESIDENT(MT)                                                                                 \
-  do {                                                                                                       \
-    allow_full_lds((const void*)procrustes_bwd_side_resident_kernel<MT, TO>);                                \
-    hipLaunchKernelGGL((procrustes_bwd_side_resident_kernel<MT, TO>), grid, dim3(PBR_THREADS), lds, st, fac, w, a, gl,  \
-                       batch, n, d, tiles, out, rowdot);                                                     \
-  } while (0)
+  auto go = [&](auto kernel) { launch_pb(kernel, grid, PBR_THREADS, lds, st, fac, w, a, gl, batch, n, d, tiles, out, rowdot); };
   switch (m) {
-    case 5: BASD_PB_RESIDENT(5); break;
-    case 6: BASD_PB_RESIDENT(6); break;
-    case 7: BASD_PB_RESIDENT(7); break;
-    case 8: BASD_PB_RESIDENT(8); break;
+    case 5: go(procrustes_bwd_side_resident_kernel<5, TO>); break;
+    case 6: go(procrustes_bwd_side_resident_kernel<6, TO>); break;
+    case 7: go(procrustes_bwd_side_resident_kernel<7, TO>); break;
+    case 8: go(procrustes_bwd_side_resident_kernel<8, TO>); break;
     default: return fail(BASD_ERR_SHAPE, "procrustes_bwd_side: no resident kernel for %d m tiles in %d row tiles", mt, tiles);
   }
-#undef BASD_PB_RESIDENT
   return check_launch("procrustes_bwd (resident residual product)");
 }
 
+// n <= 256, n % 4 == 0, a 16-byte aligned factor: one workgroup per matrix, or per row tile of the resident kernel
 template <typename TO>
 static int launch_side(const float* fac, const float* w, const float* a, const float* gl, int batch, int n, int d,
                        TO* out, float* rowdot, hipStream_t st) {
@@ -862,293 +788,33 @@ static int launch_side(const float* fac, const float* w, const float* a, const f
   // resident factor where it was measured faster: from five m tiles on, a single row tile (mt <= 8) only with at least
   // 112 columns (300 x 80 x 16: 16.1 against 14.1 us -- one strip for eight waves, and the whole factor is staged first)
   if (mt >= 9 || (mt >= 5 && d >= 112)) return launch_side_resident<TO>(fac, w, a, gl, batch, n, d, out, rowdot, st);
-  // fewer than four rows of tiles: W straight from global memory; from four on W goes through LDS, where the parked
-  // epilogue tiles (6 KiB) alias the A buffer
-#define BASD_PB_DIRECT(MT)                                                                                   \
-  do {                                                                                                       \
-    const size_t lds = (size_t)4 * MT * 16 * PB_ROWB + (size_t)MT * 16 * 4 * (PB_WAVES + 1);       /* MT >= 2: the parked tiles fit */                                  \
-    allow_full_lds((const void*)procrustes_bwd_side_kernel<MT, TO>);                                         \
-    hipLaunchKernelGGL((procrustes_bwd_side_kernel<MT, TO>), dim3(batch), dim3(PB_THREADS), lds, st, fac, w, a, gl, n, d, \
-                       out, rowdot);                                                                         \
-  } while (0)
-#define BASD_PB_STAGED(MT)                                                                                   \
-  do {                                                                                                       \
-    const size_t lds2 = (size_t)2 * MT * 16 * PB_ROWB + (size_t)2 * 32 * PB_BPITCH + (size_t)MT * 16 * 4 * (PB_WAVES + 1);  \
-    allow_full_lds((const void*)procrustes_bwd_side_lds_kernel<MT, TO>);                                     \
-    hipLaunchKernelGGL((procrustes_bwd_side_lds_kernel<MT, TO>), dim3(batch), dim3(PB_THREADS), lds2, st, fac, w, a, gl, n, \
-                       d, out, rowdot);                                                                      \
-  } while (0)
-  if (mt <= 2) BASD_PB_DIRECT(2);
-  else if (mt == 3) BASD_PB_DIRECT(4);
-  else if (mt == 4) BASD_PB_STAGED(4);
-  else if (mt <= 8) BASD_PB_STAGED(8);
-  else if (mt <= 13) BASD_PB_STAGED(13);
-  else BASD_PB_STAGED(16);
-#undef BASD_PB_DIRECT
-#undef BASD_PB_STAGED
+  // fewer than four rows of tiles: W straight from global memory; from four on W goes through LDS
+  const dim3 grid((unsigned)batch);
+  if (mt <= 2)
+    launch_pb(procrustes_bwd_side_kernel<2, TO>, grid, PB_THREADS, pb_direct_lds<2>(), st, fac, w, a, gl, n, d, out, rowdot);
+  else if (mt == 3)
+    launch_pb(procrustes_bwd_side_kernel<4, TO>, grid, PB_THREADS, pb_direct_lds<4>(), st, fac, w, a, gl, n, d, out, rowdot);
+  else if (mt == 4)
+    launch_pb(procrustes_bwd_side_tiled_kernel<4, TO, true, true>, grid, PB_THREADS, pb_tiled_lds<4>(), st, fac, w, a, gl, n, d, 1,
+              out, rowdot);
+  else                                                     // mt = 5 .. 8 with d < 112
+    launch_pb(procrustes_bwd_side_tiled_kernel<8, TO, true, true>, grid, PB_THREADS, pb_tiled_lds<8>(), st, fac, w, a, gl, n, d, 1,
+              out, rowdot);
   return check_launch("procrustes_bwd (fused residual product)");
 }
 
-
-// ---- the row-tiled form: 257 <= n <= 1024, and every n % 4 != 0 -----------------------------------------------------
-// The kernels above keep all ceil(n / 16) accumulator tiles of a 16-column strip in one wave and give a workgroup a
-// whole matrix: 144 accumulator registers per lane at 576 rows.  Here a workgroup owns ONE ROW TILE of PBL_RT = 128 rows
-// (8 accumulator tiles per strip, the MT = 8 budget of the staged kernel) of one matrix and runs the K loop over all n
-// rows of W: grid = batch x ceil(n / 128), the row tiles of a matrix adjacent in the grid so that they run together and
-// share W in the caches (at batch-major order 256 matrices x 1.8 MB of W would be re-read from HBM once per row tile).
-// Same arithmetic and the same staging as procrustes_bwd_side_lds_kernel<8>: A (the 128 x 32 slice of the factor) and
-// the W tile ([32 k rows][96 columns]) go through LDS as (hi, mid) bf16 planes, three MFMAs per tile and K step, the
-// residual / scaling / row dots in the epilogue through the parked tile.  A row tile sees all d columns, so its row
-// dots are complete inside the workgroup: each wave adds its column groups in order into its own slice, the slices are
-// added in wave order -- no atomics, bitwise reproducible.  Rows >= n of the last tile and the K tail (n % 32) are
-// zeroed by selects on the way into LDS and never stored.
-// VEC4 = false (n % 4 != 0: the rows of the factor, and every matrix of the batch but the first, are not 16-byte
-// aligned -- 729 tokens of a /14 grid at 384 px) loads the factor with 4-byte loads; W, the gradient and the LDS
-// traffic are the same (d % 16 == 0 keeps their rows aligned).
-// Compiler's resource report (hipcc --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage; LDS is dynamic:
-// 37376 bytes = 2 x 10240 A planes + 2 x 6656 W planes + 7 x 512 row dots / scales; two workgroups per CU):
-//   <float, true>            VGPRs 156  AGPRs 0  scratch 0 bytes/lane  occupancy 3 waves/SIMD
-//   <unsigned short, true>   VGPRs 156  AGPRs 0  scratch 0 bytes/lane  occupancy 3 waves/SIMD
-//   <float, false>           VGPRs 164  AGPRs 0  scratch 0 bytes/lane  occupancy 3 waves/SIMD
-//   <unsigned short, false>  VGPRs 164  AGPRs 0  scratch 0 bytes/lane  occupancy 3 waves/SIMD
-constexpr int PBL_MT = 8;                   // m tiles (16 rows each) of a row tile
-constexpr int PBL_RT = 16 * PBL_MT;         // rows of a row tile
-
-template <typename TO, bool VEC4>
-__global__ __launch_bounds__(PB_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3))) void procrustes_bwd_side_long_kernel(
-    const float* __restrict__ fac, const float* __restrict__ w, const float* __restrict__ a,
-    const float* __restrict__ gl, int n, int d, int tiles, TO* __restrict__ out, float* __restrict__ rowdot) {
-  extern __shared__ __align__(16) unsigned char smem[];
-  constexpr int MT = PBL_MT;
-  constexpr int PLANE = MT * 16 * PB_ROWB;                 // one bf16 plane of one K step
-  constexpr int ITEMS = (MT * 16 * 4 + PB_THREADS - 1) / PB_THREADS;         // staging items (row, k octet) per thread and K step
-  unsigned char* abuf = smem;                              // [2 planes][128 rows][PB_ROWB]
-  unsigned char* bbuf = smem + 2 * PLANE;                  // [2 planes][32 k rows][PB_BPITCH]: the W tile of a K step
-  float* s_dotw = reinterpret_cast<float*>(smem + 2 * PLANE + 2 * 32 * PB_BPITCH);  // [waves][128] row dots
-  float* s_c = s_dotw + PB_WAVES * MT * 16;                // [128] row scales 2 gl sqrt(a)
-  float* s_park = reinterpret_cast<float*>(abuf);          // [waves][16 rows][16 columns] epilogue tile (operands idle)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int b = (int)blockIdx.x / tiles;
-  const int r0 = ((int)blockIdx.x - b * tiles) * PBL_RT;   // first row of this tile; r0 < n
-  const float* A = fac + (size_t)b * n * n;
-  const float* W = w + (size_t)b * n * d;
-  TO* O = out + (size_t)b * n * d;
-  const int ksteps = (n + 31) >> 5;
-  const int strips = d >> 4;
-  const float c2 = 2.f * gl[b];
-  for (int i = tid; i < PBL_RT; i += PB_THREADS) {
-#pragma unroll
-    for (int wv_ = 0; wv_ < PB_WAVES; ++wv_) s_dotw[wv_ * PBL_RT + i] = 0.f;
-    s_c[i] = r0 + i < n ? c2 * __builtin_amdgcn_sqrtf(a[(size_t)b * n + r0 + i]) : 0.f;
-  }
-
-  // Staging of one K step of the A slice: item = (row of the tile, k octet), the global loads issued before the MFMAs
-  // of the current step, the split and the LDS writes after them.  Every address is clamped into the matrix (rows >= n
-  // to row n - 1, the end of the last row to the last 16 / 4 bytes); what was clamped is zeroed by a select.
-  float sa[ITEMS][8];
-  unsigned sa_off[ITEMS];
-  const unsigned a_last = (unsigned)n * (unsigned)n - (VEC4 ? 4u : 1u);
-#pragma unroll
-  for (int it = 0; it < ITEMS; ++it) {
-    const int item = tid + PB_THREADS * it;
-    const int row = r0 + (item >> 2), oct = item & 3;
-    sa_off[it] = (unsigned)(row < n ? row : n - 1) * (unsigned)n + (unsigned)(oct * 8);
-  }
-  auto stage_load = [&](int ks) {
-    const unsigned kbase = (unsigned)ks * 32u;
-#pragma unroll
-    for (int it = 0; it < ITEMS; ++it) {
-      const unsigned o0 = sa_off[it] + kbase;
-      if constexpr (VEC4) {
-        const unsigned o1 = o0 + 4u;
-        const float4 v0 = *reinterpret_cast<const float4*>(A + (o0 < a_last ? o0 : a_last));
-        const float4 v1 = *reinterpret_cast<const float4*>(A + (o1 < a_last ? o1 : a_last));
-        sa[it][0] = v0.x; sa[it][1] = v0.y; sa[it][2] = v0.z; sa[it][3] = v0.w;
-        sa[it][4] = v1.x; sa[it][5] = v1.y; sa[it][6] = v1.z; sa[it][7] = v1.w;
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const unsigned oj = o0 + (unsigned)j;
-          sa[it][j] = A[oj < a_last ? oj : a_last];
-        }
-      }
-    }
-  };
-  auto stage_store = [&](int ks) {
-#pragma unroll
-    for (int it = 0; it < ITEMS; ++it) {
-      const int item = tid + PB_THREADS * it;
-      const int row = item >> 2, oct = item & 3;
-      if (item < MT * 16 * 4) {
-        const int k0 = ks * 32 + oct * 8;
-        const bool rok = r0 + row < n;
-        float x[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) x[j] = (rok && k0 + j < n) ? sa[it][j] : 0.f;
-        uint4 hi, mid;
-        pb_split2(x[0], x[1], hi.x, mid.x); pb_split2(x[2], x[3], hi.y, mid.y);
-        pb_split2(x[4], x[5], hi.z, mid.z); pb_split2(x[6], x[7], hi.w, mid.w);
-        const unsigned lo = (unsigned)row * PB_ROWB + (unsigned)oct * 16;
-        *reinterpret_cast<uint4*>(abuf + lo) = hi;
-        *reinterpret_cast<uint4*>(abuf + PLANE + lo) = mid;
-      }
-    }
-  };
-
-  for (int g0 = 0; g0 < strips; g0 += PB_WAVES) {          // column groups of PB_WAVES strips (96 columns), one per wave
-    const int s0 = g0 + wave;
-    const bool has = s0 < strips;
-    const int col = (lane & 15);
-    // the W tile of a K step: global -> registers (16-byte loads) -> (hi, mid) planes in LDS; the wave's B fragment
-    // comes out of the transposing read, as in procrustes_bwd_side_lds_kernel
-    const int c0 = g0 * 16;                                // first column of the group
-    float4 sb[2];
-    auto bload = [&](int ks) {
-#pragma unroll
-      for (int it = 0; it < 2; ++it) {
-        const int item = tid + PB_THREADS * it;            // 768 items = 32 rows x 24 quads
-        const int row = item / 24, q = item - row * 24;
-        const int kr = ks * 32 + row, cc = c0 + 4 * q;
-        const bool ok = kr < n && cc < d;
-        sb[it] = *reinterpret_cast<const float4*>(W + (size_t)(ok ? kr : 0) * d + (ok ? cc : 0));
-        if (!ok) sb[it] = make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    };
-    auto bstore = [&]() {
-#pragma unroll
-      for (int it = 0; it < 2; ++it) {
-        const int item = tid + PB_THREADS * it;
-        const int row = item / 24, q = item - row * 24;
-        uint2 hi, mid;
-        pb_split2(sb[it].x, sb[it].y, hi.x, mid.x); pb_split2(sb[it].z, sb[it].w, hi.y, mid.y);
-        const unsigned lo = (unsigned)row * PB_BPITCH + (unsigned)q * 8;
-        *reinterpret_cast<uint2*>(bbuf + lo) = hi;
-        *reinterpret_cast<uint2*>(bbuf + 32 * PB_BPITCH + lo) = mid;
-      }
-    };
-    __syncthreads();                                       // previous group's fragment / parked-tile reads are done
-    stage_load(0);
-    bload(0);
-    stage_store(0);
-    bstore();
-    __syncthreads();
-    f32x4 acc[MT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    for (int ks = 0; ks < ksteps; ++ks) {
-      const bool more = ks + 1 < ksteps;
-      if (more) {                                          // next step's operands: loads only, stored after the MFMAs
-        bload(ks + 1);
-        stage_load(ks + 1);
-      }
-      bf16x8 bh, bm;
-      {                                                    // tr_cons of basd_frag.h on the hi and mid planes (byte pitch)
-        const int li = lane & 15, qq = li >> 2, pp = li & 3;
-        const unsigned char* b0 = bbuf + (size_t)((lane >> 4) * 8 + qq) * PB_BPITCH + (size_t)(wave * 16 + 4 * pp) * 2;
-        const v4s h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)b0);
-        const v4s h1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(b0 + 4 * PB_BPITCH));
-        const v4s m0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(b0 + 32 * PB_BPITCH));
-        const v4s m1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(b0 + 32 * PB_BPITCH + 4 * PB_BPITCH));
-        bh = (bf16x8){h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-        bm = (bf16x8){m0[0], m0[1], m0[2], m0[3], m1[0], m1[1], m1[2], m1[3]};
-      }
-      // A fragments in two batches of four tiles (one exposed LDS latency per batch; the fence keeps the second
-      // batch's reads from being hoisted on top of the first: registers)
-      const unsigned char* ap = abuf + (size_t)(lane & 15) * PB_ROWB + (lane >> 4) * 16;
-      constexpr int HB = MT / 2;
-#pragma unroll
-      for (int hb = 0; hb < 2; ++hb) {
-        bf16x8 fh[HB], fm[HB];
-#pragma unroll
-        for (int j = 0; j < HB; ++j) {
-          const int i = hb * HB + j;
-          fh[j] = *reinterpret_cast<const bf16x8*>(ap + (size_t)i * 16 * PB_ROWB);
-          fm[j] = *reinterpret_cast<const bf16x8*>(ap + PLANE + (size_t)i * 16 * PB_ROWB);
-        }
-#pragma unroll
-        for (int j = 0; j < HB; ++j) {
-          const int i = hb * HB + j;
-          acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[j], bh, acc[i], 0, 0, 0);
-          acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh[j], bm, acc[i], 0, 0, 0);
-          acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fm[j], bh, acc[i], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      __syncthreads();                                     // every wave has read the operands of step ks
-      if (more) { stage_store(ks + 1); bstore(); }
-      __syncthreads();                                     // step ks + 1 is complete
-    }
-    // ---- epilogue: acc[i][r] = P at row r0 + 16 i + 4 (lane >> 4) + r, column 16 s0 + (lane & 15).  The wave parks one
-    // 16 x 16 tile at a time in its own 1 KiB of LDS and reads it back row-wise (16 bytes per lane, 64 contiguous bytes
-    // per row segment for the W load and the store, a 4-lane reduction per row), as in the kernels above.
-    float* park = s_park + wave * 256;
-    const int g4 = lane >> 4;
-    const int prow = lane >> 2, pch = lane & 3;            // row-wise walk: 16 rows x 4 chunks of 4 columns
-    const int pcol = s0 * 16 + pch * 4;
-    constexpr int H0 = MT / 2;                             // tiles per batch: the W loads of a batch are in flight together
-#pragma unroll
-    for (int hb = 0; hb < 2; ++hb) {
-      float4 wq[H0];
-#pragma unroll
-      for (int j = 0; j < H0; ++j) {
-        const int row = r0 + (hb * H0 + j) * 16 + prow;
-        const bool ok = has && row < n;
-        wq[j] = *reinterpret_cast<const float4*>(W + (unsigned)(ok ? row : 0) * (unsigned)d + (unsigned)(ok ? pcol : 0));
-      }
-#pragma unroll
-      for (int j = 0; j < H0; ++j) {
-        const int i = hb * H0 + j;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) park[(g4 * 4 + r) * 16 + col] = acc[i][r];
-        // wave-private tile: the wave's own LDS writes precede its reads (in order), no barrier
-        const float4 pv = *reinterpret_cast<const float4*>(park + prow * 16 + pch * 4);
-        const int lrow = i * 16 + prow, row = r0 + lrow;
-        const bool ok = has && row < n;                    // rows >= n are never stored
-        const unsigned off = (unsigned)(ok ? row : 0) * (unsigned)d + (unsigned)(ok ? pcol : 0);
-        const float4 wv = wq[j];
-        const float cr = s_c[lrow];
-        const float4 rv = make_float4(wv.x - pv.x, wv.y - pv.y, wv.z - pv.z, wv.w - pv.w);
-        float dot = ok ? fmaf(rv.x, wv.x, fmaf(rv.y, wv.y, fmaf(rv.z, wv.z, rv.w * wv.w))) : 0.f;
-        if (ok) {
-          if constexpr (sizeof(TO) == 4) {
-            *reinterpret_cast<float4*>(O + off) = make_float4(cr * rv.x, cr * rv.y, cr * rv.z, cr * rv.w);
-          } else {
-            uint2 o;
-            o.x = pack_bf16_bits(cr * rv.x, cr * rv.y);
-            o.y = pack_bf16_bits(cr * rv.z, cr * rv.w);
-            *reinterpret_cast<uint2*>(O + off) = o;
-          }
-        }
-        dot += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(dot), 0xB1, 0xF, 0xF, true));     // quad_perm 1,0,3,2
-        dot += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(dot), 0x4E, 0xF, 0xF, true));     // quad_perm 2,3,0,1
-        if (pch == 0) s_dotw[wave * PBL_RT + lrow] += c2 * dot;
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-  __syncthreads();
-  for (int i = tid; i < PBL_RT; i += PB_THREADS) {
-    if (r0 + i < n) {
-      float t = 0.f;
-#pragma unroll
-      for (int wv_ = 0; wv_ < PB_WAVES; ++wv_) t += s_dotw[wv_ * PBL_RT + i];
-      rowdot[(size_t)b * n + r0 + i] = t;
-    }
-  }
-}
-
+// 257 <= n <= 1024, and every n % 4 != 0: row tiles of PBL_RT rows
 template <typename TO>
 static int launch_side_long(const float* fac, const float* w, const float* a, const float* gl, int batch, int n, int d,
                             TO* out, float* rowdot, hipStream_t st) {
   const int tiles = (n + PBL_RT - 1) / PBL_RT;
-  const size_t lds = (size_t)2 * PBL_RT * PB_ROWB + (size_t)2 * 32 * PB_BPITCH + (size_t)PBL_RT * 4 * (PB_WAVES + 1);
   const dim3 grid((unsigned)batch * (unsigned)tiles);
   if (n % 4 == 0 && (((uintptr_t)fac) & 15) == 0)
-    hipLaunchKernelGGL((procrustes_bwd_side_long_kernel<TO, true>), grid, dim3(PB_THREADS), lds, st, fac, w, a, gl, n, d,
-                       tiles, out, rowdot);
+    launch_pb(procrustes_bwd_side_tiled_kernel<PBL_MT, TO, true, false>, grid, PB_THREADS, pb_tiled_lds<PBL_MT>(), st, fac, w, a, gl,
+              n, d, tiles, out, rowdot);
   else
-    hipLaunchKernelGGL((procrustes_bwd_side_long_kernel<TO, false>), grid, dim3(PB_THREADS), lds, st, fac, w, a, gl, n, d,
-                       tiles, out, rowdot);
+    launch_pb(procrustes_bwd_side_tiled_kernel<PBL_MT, TO, false, false>, grid, PB_THREADS, pb_tiled_lds<PBL_MT>(), st, fac, w, a, gl,
+              n, d, tiles, out, rowdot);
   return check_launch("procrustes_bwd (row-tiled residual product)");
 }
 
