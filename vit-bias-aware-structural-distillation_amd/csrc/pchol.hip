@@ -314,13 +314,13 @@ __global__ __launch_bounds__(1024) void pchol_kernel(const double* __restrict__ 
       s_d[r] -= col * col;
       if (r == pv) { s_alive[r] = 0; piv[k] = pv; }
     }
-    if (part == 1 && r >= n && r < ld) W0[(size_t)k * ld + r] = 0.f;
+    if (part == 1 && n + r < ld) W0[(size_t)k * ld + n + r] = 0.f;    // padding: ld - n <= 123 (ld may exceed 256)
     __syncthreads();
   }
   // ---- zero the columns beyond the numerical rank; complete the permutation
   for (int k = rank; k < n; ++k) {
-    if (part == 0 && r < n) Lw[(size_t)k * n + r] = 0.0;
-    if (part == 0 && r < ld) W0[(size_t)k * ld + r] = 0.f;
+    if (part == 0 && r < n) { Lw[(size_t)k * n + r] = 0.0; W0[(size_t)k * ld + r] = 0.f; }
+    if (part == 1 && n + r < ld) W0[(size_t)k * ld + n + r] = 0.f;
   }
   if (tid == 0) {
     rank_all[blockIdx.x] = rank;
@@ -337,14 +337,16 @@ __global__ __launch_bounds__(1024) void mp_rank_kernel(const float* __restrict__
   __shared__ float s_v[1024];
   __shared__ float s_sorted[1024];
   __shared__ int s_count;
+  __shared__ int s_nan;
   const int tid = threadIdx.x;
   const float* e = evals + (size_t)blockIdx.x * n;
   s_v[tid] = (tid < n) ? e[tid] * scale : -1.f;
   s_sorted[tid] = -1.f;
-  if (tid == 0) s_count = 0;
+  if (tid == 0) { s_count = 0; s_nan = 0; }
   __syncthreads();
   if (tid < n) {
     const float mine = s_v[tid];
+    if (mine != mine) s_nan = 1;   // a NaN has no place in the order below (it would leave -1 fillers in s_sorted)
     int rk = 0;   // descending rank
     for (int c = 0; c < n; ++c) rk += (s_v[c] > mine) || (s_v[c] == mine && c < tid);
     s_sorted[rk] = mine;
@@ -360,10 +362,11 @@ __global__ __launch_bounds__(1024) void mp_rank_kernel(const float* __restrict__
   if (tid < n_eff && s_sorted[tid] > edge) atomicAdd(&s_count, 1);
   __syncthreads();
   if (tid == 0) {
-    ranks[blockIdx.x] = s_count < cap ? s_count : cap;
-    // rank 0 makes the reference divide by sum(sw) = 0 (layer_selector.py:105, NaN weights); a NaN spectrum
-    // compares false everywhere and also counts 0
-    if (status && s_count == 0) atomicOr(status, (sigma2 == sigma2) ? BASD_STATUS_RANK0 : BASD_STATUS_NONFINITE);
+    const int count = s_nan ? 0 : s_count;
+    ranks[blockIdx.x] = count < cap ? count : cap;
+    // rank 0 makes the reference divide by sum(sw) = 0 (layer_selector.py:105, NaN weights); a spectrum with a NaN
+    // counts 0 like the reference's (its median and edge are NaN)
+    if (status && count == 0) atomicOr(status, (!s_nan && sigma2 == sigma2) ? BASD_STATUS_RANK0 : BASD_STATUS_NONFINITE);
   }
 }
 

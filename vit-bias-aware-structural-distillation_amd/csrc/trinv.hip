@@ -1,13 +1,13 @@
 // Batched inverse of the pivoted Cholesky factor, fp64, one matrix per workgroup,
-// packed lower triangle resident in LDS (n(n+1)/2 doubles <= 148 KiB at n = 192).
+// lower block triangle resident in LDS (78 blocks of 16 x 16 doubles = 156 KiB at n = 192).
 // Replaces torch.linalg.solve_triangular in the Procrustes core: rocBLAS' batched
 // dtrsm runs as ~16 small GEMM launches PER MATRIX (16k launches per step in the
 // round-1 profile).
 //
 // Input is the factor as basd_pchol_f64 leaves it (lwork column-major by step, rows
 // in original order, plus piv / rank).  With P the pivot permutation, L_p = P L is
-// lower triangular; the kernel forms X = L_p^-1 in place (LAPACK dtrti2 recurrence,
-// last column first) and writes  out[k, piv[c]] = X[k, c],  i.e. out = L_p^-1 P, so
+// lower triangular; the kernel forms X = L_p^-1 in place (block columns, last one
+// first) and writes  out[k, piv[c]] = X[k, c],  i.e. out = L_p^-1 P, so
 // that  out @ M  ==  L_p^-1 (P M)  for any M whose rows are in ORIGINAL order: no
 // gather of the right-hand sides is needed.  Columns >= rank of L_p are replaced by
 // unit columns (their rows of out are zeroed: pseudo-inverse semantics).
@@ -16,73 +16,15 @@
 
 namespace basd {
 
-__device__ __forceinline__ int tri(int i, int k) { return i * (i + 1) / 2 + k; }
-
-__global__ __launch_bounds__(768) void trinv_kernel(const double* __restrict__ lw_all,
-                                                    const int32_t* __restrict__ piv_all,
-                                                    const int32_t* __restrict__ rank_all, int n,
-                                                    double* __restrict__ out_all, const int32_t* __restrict__ skip) {
-  if (skip != nullptr && skip[blockIdx.x] != 0) return;       // masked problem: output left untouched
-  extern __shared__ __align__(16) double X[];          // packed lower triangle
-  int* s_piv = reinterpret_cast<int*>(X + (size_t)n * (n + 1) / 2);
-  const int tid = threadIdx.x, nt = blockDim.x;
-  const double* Lw = lw_all + (size_t)blockIdx.x * n * n;
-  const int32_t* piv = piv_all + (size_t)blockIdx.x * n;
-  const int rank = rank_all[blockIdx.x];
-  double* out = out_all + (size_t)blockIdx.x * n * n;
-
-  for (int i = tid; i < n; i += nt) s_piv[i] = piv[i];
-  __syncthreads();
-  // gather L_p[i, k] = Lw[k * n + piv[i]]  (k <= i); dead columns -> identity
-  for (int e = tid; e < n * n; e += nt) {
-    const int k = e / n, i = e - k * n;     // consecutive threads: consecutive i (reads of row k scattered by piv)
-    if (k <= i) {
-      double v;
-      if (k < rank) v = Lw[(size_t)k * n + s_piv[i]];
-      else v = (i == k) ? 1.0 : 0.0;
-      X[tri(i, k)] = v;
-    }
-  }
-  __syncthreads();
-  const int row_l = tid >> 2, part = tid & 3;            // 4 lanes per row
-  for (int j = n - 1; j >= 0; --j) {
-    const double ajj = 1.0 / X[tri(j, j)];
-    // v_i = sum_{k=j+1..i} X[i,k] * L[k,j]   for i = j+1 .. n-1   (rows strided over the workgroup)
-    double v[2] = {0.0, 0.0};
-    int cnt = 0;
-    for (int i = j + 1 + row_l; i < n; i += (nt >> 2), ++cnt) {
-      double acc = 0.0;
-      const double* xi = X + tri(i, 0);
-      for (int k = j + 1 + part; k <= i; k += 4) acc = fma(xi[k], X[tri(k, j)], acc);
-      acc += __shfl_xor(acc, 1, 64);
-      acc += __shfl_xor(acc, 2, 64);
-      v[cnt] = acc;
-    }
-    __syncthreads();                                      // column j is still the ORIGINAL L[:, j] until here
-    cnt = 0;
-    for (int i = j + 1 + row_l; i < n; i += (nt >> 2), ++cnt)
-      if (part == 0) X[tri(i, j)] = -ajj * v[cnt];
-    if (tid == 0) X[tri(j, j)] = ajj;
-    __syncthreads();
-  }
-  // out[k, piv[c]] = X[k, c] (c <= k), zero elsewhere; rows k >= rank zeroed
-  for (int e = tid; e < n * n; e += nt) {
-    const int k = e / n, c = e - k * n;
-    const double v = (c <= k && k < rank) ? X[tri(k, c)] : 0.0;
-    out[(size_t)k * n + s_piv[c]] = v;
-  }
-}
-
 // ---------------------------------------------------------------------------------------------
-// Blocked version on the fp64 matrix cores (default).  The kernel above walks the 192 columns one
-// by one (two barriers and an LDS-latency-bound dot product per column: 0.4 ms per matrix).  Here
+// Blocked on the fp64 matrix cores.  A column-by-column recurrence costs two barriers and an
+// LDS-latency-bound dot product per column (0.4 ms per matrix at 192 columns).  Here
 // L_p is held as 16 x 16 blocks and inverted block column by block column:
 //   1. X_jj = L_jj^-1 for the 12 diagonal blocks at once (one thread per column, registers),
 //   2. W_kj = L_kj X_jj for every sub-diagonal block (independent 16^3 products, one wave each),
 //   3. for j = nb-2 .. 0:   X_ij = - sum_{k=j+1..i} X_ik W_kj   (i > j; one wave per row block,
 //      v_mfma_f64_16x16x4_f64 chains), which only reads finished block columns > j of X and
 //      column j of W: 11 levels with two barriers each instead of 192 steps.
-// Same input / output contract as trinv_kernel.
 
 __device__ __forceinline__ int blk_off(int bi, int bj) { return (bi * (bi + 1) / 2 + bj) * 256; }
 
@@ -204,8 +146,8 @@ __global__ __launch_bounds__(768) void trinv_blocked_kernel(const double* __rest
 // Border rows of L_p^-1 P for n_lead < ld <= n_lead + 16 (the 196-token matrices of the wide students: 192 + 4):
 // with L_p = [[L11, 0], [L21, L22]],  rows i >= n_lead of the inverse are  (e_i^T - L_p[i, :i] X[:i, :]) / L_p[i, i],
 // computed column by column of the OUTPUT layout (out[k, piv[c]] = X[k, c]: the leading rows written by
-// trinv_blocked_kernel are read back row-contiguously, one thread per output column).  The unblocked kernel above
-// needs 0.84 ms per 512 matrices of 196 x 196; blocked leading part + this border: see DESIGN.md section 5.
+// trinv_blocked_kernel are read back row-contiguously, one thread per output column).  An unblocked column-by-column
+// kernel needed 0.84 ms per 512 matrices of 196 x 196; blocked leading part + this border: see DESIGN.md section 5.
 __global__ __launch_bounds__(256) void trinv_border_kernel(const double* __restrict__ lw_all,
                                                            const int32_t* __restrict__ piv_all,
                                                            const int32_t* __restrict__ rank_all, int n_lead, int ld,
@@ -265,28 +207,23 @@ extern "C" int basd_trinv_f64_masked(const double* lwork, const int32_t* piv, co
                                      double* out, const int32_t* skip, void* stream) {
   using namespace basd;
   if (batch <= 0) return BASD_OK;
-  const size_t lds = (size_t)n * (n + 1) / 2 * 8 + (size_t)n * 4 + 64;
-  if (n < 1 || (lds > 160 * 1024 && n > 208))
+  // n <= 192: 12 x 12 blocks, 162 048 B of LDS; 193 .. 208: the same leading block + border rows.  Nothing else fits.
+  if (n < 1 || n > 208)
     return fail(BASD_ERR_SHAPE, "trinv_f64: n=%d does not fit the LDS-resident forms (n <= 208)", n);
   const int nb = (n + 15) / 16;
   const size_t lds_blk = (size_t)nb * (nb + 1) / 2 * 256 * 8 + (size_t)16 * nb * (8 + 4);
-  if (nb <= 12 && lds_blk <= 160 * 1024) {
+  if (nb <= 12) {
     allow_full_lds((const void*)trinv_blocked_kernel);
     hipLaunchKernelGGL(trinv_blocked_kernel, dim3(batch), dim3(768), lds_blk, (hipStream_t)stream, lwork, piv, rank, n,
                        n, out, skip);
     return check_launch("trinv_f64 (blocked)");
   }
-  if (n > 192 && n <= 208) {     // 192 leading rows on the blocked kernel, up to 16 border rows behind it
-    const size_t lds12 = (size_t)12 * 13 / 2 * 256 * 8 + (size_t)16 * 12 * (8 + 4);
-    allow_full_lds((const void*)trinv_blocked_kernel);
-    hipLaunchKernelGGL(trinv_blocked_kernel, dim3(batch), dim3(768), lds12, (hipStream_t)stream, lwork, piv, rank, 192,
-                       n, out, skip);
-    hipLaunchKernelGGL(trinv_border_kernel, dim3(batch), dim3(256), 0, (hipStream_t)stream, lwork, piv, rank, 192, n, out,
-                       skip);
-    return check_launch("trinv_f64 (blocked + border)");
-  }
-  // 4 lanes per row, rows strided by 192 per pass: two passes cover n <= 384 (v[2])
-  allow_full_lds((const void*)trinv_kernel);
-  hipLaunchKernelGGL(trinv_kernel, dim3(batch), dim3(768), lds, (hipStream_t)stream, lwork, piv, rank, n, out, skip);
-  return check_launch("trinv_f64");
+  // 193 .. 208: 192 leading rows on the blocked kernel, up to 16 border rows behind it
+  const size_t lds12 = (size_t)12 * 13 / 2 * 256 * 8 + (size_t)16 * 12 * (8 + 4);
+  allow_full_lds((const void*)trinv_blocked_kernel);
+  hipLaunchKernelGGL(trinv_blocked_kernel, dim3(batch), dim3(768), lds12, (hipStream_t)stream, lwork, piv, rank, 192,
+                     n, out, skip);
+  hipLaunchKernelGGL(trinv_border_kernel, dim3(batch), dim3(256), 0, (hipStream_t)stream, lwork, piv, rank, 192, n, out,
+                     skip);
+  return check_launch("trinv_f64 (blocked + border)");
 }
