@@ -673,6 +673,32 @@ int basd_mixup_cutmix(const void* images, int img_bf16, int B, int C_img, int H,
                       int num_classes, int mode, float lam, int y0, int y1, int x0, int x1, void* out_images,
                       float* out_targets, void* stream);
 
+/* Gradient of the selector term with respect to the E tapped student token tensors (the loop at the end of
+ * _SelectorWeightsFn.backward: sf = s.float(); row = -(sf.mean(0) @ W); addmm(row, sf, W).to(bf16)), all taps in one
+ * call:   out_e[b, n, :] = bf16((s_e[b, n, :] - mean_e) W_e),   mean_e = the column mean of s_e over all B N rows.
+ * tokens: HOST array of E device pointers to bf16 [B, N, D_s] views (sample b at + b * batch_stride elements, rows
+ * dense; the CLS-stripped block outputs are consumed in place), w [E, D_s, D_s] fp32, out: HOST array of E device
+ * pointers to contiguous bf16 [B, N, D_s] tensors.  Column sums in fp64; the centring is applied after the product
+ * (s W - mean W); the product runs on the bf16 matrix cores over a three-way bf16 split of W with fp32 accumulation
+ * (s is exact in bf16).  Two launches on `stream`, no allocation, no synchronisation, legal inside a stream capture.
+ * D_s in {192, 384, 768}, 1 <= E <= 8, batch_stride % 8 == 0, B * batch_stride < 2^31, every pointer 16-byte aligned
+ * (BASD_ERR_SHAPE);
+ * workspace >= basd_selector_token_grad_workspace_bytes(E, D_s) bytes, 16-byte aligned (BASD_ERR_WORKSPACE). */
+int64_t basd_selector_token_grad_workspace_bytes(int E, int D_s);
+int basd_selector_token_grad(const void* const* tokens, int E, int B, int N, int D_s, int64_t batch_stride,
+                             const float* w, void* const* out, void* workspace, int64_t workspace_bytes,
+                             void* stream);
+
+/* Backward of a token tap out[:, offset:, :] of a block output [B, T, D_s] (offset 1 strips the CLS token, 0 = none),
+ * everything autograd did around it in one pass:   out = g_out (+) pad(g_a (+) g_b),   all bf16.
+ * g_out [B, T, D_s] (gradient of the block output; NULL = zero), g_a, g_b [B, T - offset, D_s] contiguous (gradients
+ * of the token view; either may be NULL), out [B, T, D_s].  Rounding as autograd's chain of bf16 adds:
+ * r = bf16(float(g_a) + float(g_b)), out = bf16(float(g_out) + float(r)) on rows offset .. T - 1; rows below offset
+ * are copies of g_out; an absent operand is skipped, not added as zero.  One launch of 16-byte accesses on `stream`.
+ * D_s % 64 == 0, 0 <= offset < T, pointers 16-byte aligned (BASD_ERR_SHAPE). */
+int basd_tap_grad_scatter(const void* g_out, const void* g_a, const void* g_b, int B, int T, int D_s, int offset,
+                          void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,7 +35,8 @@ EXPORTS = (
     "basd_attention_bwd_long_workspace_bytes", "basd_attention_bwd_long_bf16", "basd_attention_fwd_f32x3_long",
     "basd_dwconv7_ln_bf16", "basd_grn_workspace_bytes", "basd_grn_bf16", "basd_patchify_bf16",
     "basd_resample_u8", "basd_ta_normalize_u8", "basd_cls_tally", "basd_resample_u8_packed",
-    "basd_mixup_cutmix",
+    "basd_mixup_cutmix", "basd_selector_token_grad_workspace_bytes", "basd_selector_token_grad",
+    "basd_tap_grad_scatter",
 )
 
 
@@ -108,6 +109,9 @@ _SIGNATURES = {
     "basd_ta_normalize_u8": (_P, _P, _P, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P),
     "basd_cls_tally": (_P, _I, _I64, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P),
     "basd_mixup_cutmix": (_P, _I, _I, _I, _I, _I, _P, _I, _I, _F, _I, _I, _I, _I, _P, _P, _P),
+    "basd_selector_token_grad_workspace_bytes": (_I, _I),
+    "basd_selector_token_grad": (_P, _I, _I, _I, _I, _I64, _P, _P, _P, _I64, _P),
+    "basd_tap_grad_scatter": (_P, _P, _P, _I, _I, _I, _I, _P, _P),
 }
 
 
@@ -1419,3 +1423,62 @@ def mixup_cutmix(images: torch.Tensor, labels: torch.Tensor, num_classes: int, m
                                    int(num_classes), int(mode), ctypes.c_float(lam), y0, y1, x0, x1, _ptr(out),
                                    _ptr(out_targets), _stream()), "basd_mixup_cutmix")
     return out, out_targets
+
+
+# --------------------------------------------------------------------------- #
+# gradient of the tapped student tokens (csrc/tap_grad.hip)
+def selector_token_grad_supported(d_s: int) -> bool:
+    """student widths basd_selector_token_grad takes (column panels of 192); every other width keeps the torch chain"""
+    return d_s in (192, 384, 768)
+
+
+def selector_token_grad(student, w_tok: torch.Tensor, out=None):
+    """student: E same-shape bf16 [B, N, D_s] token tensors (CLS-stripped views are read in place), w_tok [E, D_s, D_s]
+    fp32 -> list of E contiguous bf16 [B, N, D_s] gradients (s_i - column mean) w_tok[i]: ONE C call, two launches.
+    ``out``: E contiguous bf16 [B, N, D_s] tensors to write into instead of a fresh allocation."""
+    _need_cuda(*student, w_tok)
+    e = len(student)
+    b, n, d = student[0].shape
+    assert selector_token_grad_supported(d) and w_tok.shape == (e, d, d), (d, tuple(w_tok.shape))
+    assert all(t.dtype == torch.bfloat16 for t in student)
+    layers, _, bstride = _layer_views(list(student))
+    w = w_tok.detach().contiguous().float()
+    if out is None:
+        buf = torch.empty(e, b, n, d, dtype=torch.bfloat16, device=w.device)
+        outs = [buf[i] for i in range(e)]
+    else:
+        outs = list(out)
+        assert len(outs) == e and all(o.shape == (b, n, d) and o.dtype == torch.bfloat16 and o.is_contiguous()
+                                      for o in outs)
+    ws = torch.empty(int(lib().basd_selector_token_grad_workspace_bytes(e, d)), dtype=torch.uint8, device=w.device)
+    _check(lib().basd_selector_token_grad(_ptr_table(layers), e, b, n, d, ctypes.c_int64(bstride), _ptr(w),
+                                          _ptr_table(outs), _ptr(ws), ctypes.c_int64(ws.numel()), _stream()),
+           "basd_selector_token_grad")
+    return outs
+
+
+def tap_grad_scatter_supported(d_s: int) -> bool:
+    return d_s > 0 and d_s % 64 == 0
+
+
+def tap_grad_scatter(g_out, g_a, g_b, shape, offset: int, device=None) -> torch.Tensor:
+    """Backward of the token tap out[:, offset:, :] of a [B, T, D_s] bf16 block output in one launch:
+    g_out (+) pad(g_a (+) g_b) with autograd's bf16 roundings; any of the three may be None (basd_tap_grad_scatter)."""
+    b, t, d = shape
+    given = [g for g in (g_out, g_a, g_b) if g is not None]
+    _need_cuda(*given)
+    assert tap_grad_scatter_supported(d) and 0 <= offset < t
+    if g_out is not None:
+        assert g_out.dtype == torch.bfloat16 and tuple(g_out.shape) == (b, t, d)
+        g_out = g_out.contiguous()
+    tok = []
+    for g in (g_a, g_b):
+        if g is not None:
+            assert g.dtype == torch.bfloat16 and tuple(g.shape) == (b, t - offset, d)
+            g = g.contiguous()
+        tok.append(g)
+    device = given[0].device if given else device
+    out = torch.empty(b, t, d, dtype=torch.bfloat16, device=device)
+    _check(lib().basd_tap_grad_scatter(_ptr(g_out), _ptr(tok[0]), _ptr(tok[1]), b, t, d, int(offset), _ptr(out),
+                                       _stream()), "basd_tap_grad_scatter")
+    return out

@@ -508,6 +508,12 @@ class _SelectorWeightsFn(torch.autograd.Function):
             # four small fp64 products in six launches on a workspace
             g_lt, w_tok = ops.angle_weights_bwd(g_w, g_pre_out, wts, d2, log_temp, t_seed, v_s, lam_s, proj_s)
             g_lt = g_lt.to(log_temp.dtype)
+            fused = getattr(ops, "selector_token_grad_supported", None)
+            if (fused is not None and fused(student[0].shape[-1]) and student[0].dim() == 3
+                    and all(s.dtype == torch.bfloat16 and s.shape == student[0].shape for s in student)):
+                # all E taps in one C call (basd_selector_token_grad): the tokens are read once as bf16, in place
+                grads = ops.selector_token_grad(student, w_tok)
+                return (g_lt, None, None, None, None, None, None, None, *grads)
             grads = []
             for i in range(E):
                 s = student[i]

@@ -30,6 +30,43 @@ from .mixup import mixup_cutmix
 from .optim import AdamWScheduleFree, FlatParams
 
 
+class _TokenTapFn(torch.autograd.Function):
+    """Token tap of a block output: (the output passed through, out[:, offset:, :]).  Its backward is the whole
+    gradient of the block output in one launch (basd_tap_grad_scatter) instead of autograd's zero fill, strided copy
+    and add around the slice; the roundings are autograd's."""
+
+    @staticmethod
+    def forward(ctx, out, offset):
+        ctx.offset, ctx.shape, ctx.device = offset, tuple(out.shape), out.device
+        ctx.set_materialize_grads(False)
+        return out.view_as(out), out[:, offset:, :]
+
+    @staticmethod
+    def backward(ctx, g_out, g_tok):
+        if g_out is None and g_tok is None:
+            return None, None
+        ops = get_ops()
+        if all(g is None or (g.dtype == torch.bfloat16 and ops.handles(g)) for g in (g_out, g_tok)):
+            return ops.tap_grad_scatter(g_out, g_tok, None, ctx.shape, ctx.offset, ctx.device), None
+        if g_tok is None:
+            return g_out, None
+        pad = torch.nn.functional.pad(g_tok, (0, 0, ctx.offset, 0))
+        return (pad if g_out is None else g_out + pad), None
+
+
+def _fused_tap_ok(model: nn.Module, block: nn.Module, out) -> bool:
+    """the tap takes _TokenTapFn: bf16 device activations of a fused training block with grad enabled (activation
+    checkpointing re-runs the block and its hooks: the plain slice stays there, as on the CPU and for other dtypes)"""
+    if not (isinstance(out, torch.Tensor) and out.dim() == 3 and out.dtype == torch.bfloat16 and out.requires_grad
+            and torch.is_grad_enabled()):
+        return False
+    if getattr(model, "grad_checkpointing", False) or not getattr(block, "fuse_training", False):
+        return False
+    ops = get_ops()
+    supported = getattr(ops, "tap_grad_scatter_supported", None)
+    return supported is not None and ops.handles(out) and supported(out.shape[-1]) and out.shape[1] > 1
+
+
 def _extract_student(model: nn.Module, x: torch.Tensor, layer_indices, *, layer_paths, has_cls_token: bool):
     """Student forward with token taps at ``layer_indices`` (CLS stripped), reference :16-37."""
     hooks, captured = [], {}
@@ -38,6 +75,16 @@ def _extract_student(model: nn.Module, x: torch.Tensor, layer_indices, *, layer_
 
         def make_hook(i):
             def hook(mod, inp, out):
+                if _fused_tap_ok(model, mod, out):
+                    new, tok = _TokenTapFn.apply(out, 1 if has_cls_token else 0)
+                    # a node of its own for the tokens: the two-stage backward differentiates with respect to the tapped
+                    # tensor, and an input captured at the tap's own node would pull the blocks between the tap and the
+                    # cut (they reach that node through ``new``) into stage 1
+                    captured[i] = tok.view_as(tok)
+                    pre = getattr(out, "_basd_prenorm", None)
+                    if pre is not None:
+                        new._basd_prenorm = pre      # the next block's norm1 finds its fused result on the new tensor
+                    return new
                 captured[i] = out[:, 1:, :] if has_cls_token else out
             return hook
         hooks.append(block.register_forward_hook(make_hook(idx)))
