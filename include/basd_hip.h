@@ -78,8 +78,12 @@
  *                          and criterion(outputs, labels) of one evaluation batch, accumulated on the device
  *   basd_mixup_cutmix      src/training/trainer.py:89-92,138: RandomChoice([MixUp, CutMix]) of one batch and its soft
  *                          targets, written into the captured step's input buffers in one launch
+ *   basd_resample_tokens, basd_resample_tokens_adjoint
+ *                          src/losses/combined.py:9-14 (_align_token_count) and its autograd
+ *   basd_procrustes_importance_bwd
+ *                          autograd of relational.py:29-33 w.r.t. the importance, back through the token resample
  *
- * 66 entries in all (basd_version and basd_last_error included).
+ * 72 entries in all (basd_version and basd_last_error included).
  */
 #ifndef BASD_HIP_H
 #define BASD_HIP_H
@@ -481,6 +485,37 @@ int64_t basd_procrustes_bwd_workspace_bytes(int batch, int n);
 int basd_procrustes_bwd(const float* s_w, const float* t_w, const float* a, const float* gl, const float* fac_s,
                         const float* a_t, int batch, int n, int d_s, int d_t, void* g_s, int g_s_dtype, float* g_t,
                         float* g_a, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* 1-D linear resampling along the token axis, the rule of F.interpolate(mode="linear", align_corners=False) that
+ * basd_procrustes_prep applies to the teacher tokens and the importance (reference src/losses/combined.py:9-14).  Output
+ * index i of an n_in -> n_out resample has the taps, in fp32 with every operation rounded on its own (no FMA):
+ *     pos = max(0, (i + 0.5) * (n_in / n_out) - 0.5),  lo = min((int)pos, n_in - 1),  hi = min(lo + 1, n_in - 1),
+ *     fr = pos - lo;    lo = hi = i, fr = 0 when n_in == n_out.
+ * x [batch, n_in, d] -> out [batch, n_out, d]:  out[b, i, :] = (1 - fr_i) x[b, lo_i, :] + fr_i x[b, hi_i, :].
+ * dtype: BASD_DTYPE_F32 | BASD_DTYPE_BF16, of x and out alike; fp32 arithmetic.  1 <= n_in, n_out <= 1024, d >= 4,
+ * d % 4 == 0, batch >= 1; BASD_ERR_SHAPE (nothing launched) outside the range or for a NULL pointer.  16-byte accesses
+ * when x and out are 16-byte aligned (bf16: and d % 8 == 0), narrower ones down to one element otherwise.  One launch,
+ * no workspace, no host synchronisation. */
+int basd_resample_tokens(const void* x, int dtype, int batch, int n_in, int n_out, int d, void* out, void* stream);
+
+/* The adjoint (transpose) of basd_resample_tokens with the same taps: the gradient of an n_in -> n_out resample.
+ * g [batch, n_out, d] -> out [batch, n_in, d]:
+ *     out[b, j, :] = sum_{i: lo_i = j} (1 - fr_i) g[b, i, :] + sum_{i: hi_i = j, fr_i != 0} fr_i g[b, i, :].
+ * Gather form: every output row is summed by one thread per vector in ascending i, without atomics, so the result is
+ * bitwise reproducible; a row that no i reaches is written as zeros.  Ranges, dtypes, alignment and errors as above. */
+int basd_resample_tokens_adjoint(const void* g, int dtype, int batch, int n_in, int n_out, int d, void* out,
+                                 void* stream);
+
+/* The way from basd_procrustes_bwd's g_a back to the importance the caller gave basd_procrustes_prep
+ * (src/losses/relational.py:29-33: a = v / sum(v), v = R imp with R the n_t -> n_s resample above, the identity when
+ * n_t == n_s).  g_a, a [batch, n_s] (a: the prep output), imp [batch, n_t] -> g_imp [batch, n_t], all fp32:
+ *     g_v[i] = (g_a[i] - sum_k a[k] g_a[k]) / sum(R imp),    g_imp = R^T g_v,
+ * per sample in fp64 from the fp32 inputs and taps, sums in a fixed order, one rounding at the store.
+ * 1 <= n_s, n_t <= 1024, batch >= 1; BASD_ERR_SHAPE (nothing launched) outside the range or for a NULL pointer.
+ * A C-only caller finishes the Procrustes backward for any token counts with
+ * basd_resample_tokens_adjoint(g_t, BASD_DTYPE_F32, batch, n_t, n_s, d_t, ...) (not needed when n_t == n_s) and this. */
+int basd_procrustes_importance_bwd(const float* g_a, const float* a, const float* imp, int batch, int n_s, int n_t,
+                                   float* g_imp, void* stream);
 
 /* Cross-entropy with label smoothing on soft targets [B, C] (MixUp / CutMix) or class indices [B] (exactly one of the
  * two non-NULL), its gradient, and the UW-SO combination with the Procrustes term (src/losses/combined.py:57,78-85;

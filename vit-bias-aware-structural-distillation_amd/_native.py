@@ -36,7 +36,7 @@ EXPORTS = (
     "basd_dwconv7_ln_bf16", "basd_grn_workspace_bytes", "basd_grn_bf16", "basd_patchify_bf16",
     "basd_resample_u8", "basd_ta_normalize_u8", "basd_cls_tally", "basd_resample_u8_packed",
     "basd_mixup_cutmix", "basd_selector_token_grad_workspace_bytes", "basd_selector_token_grad",
-    "basd_tap_grad_scatter",
+    "basd_tap_grad_scatter", "basd_resample_tokens", "basd_resample_tokens_adjoint", "basd_procrustes_importance_bwd",
 )
 
 
@@ -112,6 +112,9 @@ _SIGNATURES = {
     "basd_selector_token_grad_workspace_bytes": (_I, _I),
     "basd_selector_token_grad": (_P, _I, _I, _I, _I, _I64, _P, _P, _P, _I64, _P),
     "basd_tap_grad_scatter": (_P, _P, _P, _I, _I, _I, _I, _P, _P),
+    "basd_resample_tokens": (_P, _I, _I, _I, _I, _I, _P, _P),
+    "basd_resample_tokens_adjoint": (_P, _I, _I, _I, _I, _I, _P, _P),
+    "basd_procrustes_importance_bwd": (_P, _P, _P, _I, _I, _I, _P, _P),
 }
 
 
@@ -1481,4 +1484,56 @@ def tap_grad_scatter(g_out, g_a, g_b, shape, offset: int, device=None) -> torch.
     out = torch.empty(b, t, d, dtype=torch.bfloat16, device=device)
     _check(lib().basd_tap_grad_scatter(_ptr(g_out), _ptr(tok[0]), _ptr(tok[1]), b, t, d, int(offset), _ptr(out),
                                        _stream()), "basd_tap_grad_scatter")
+    return out
+
+
+# --------------------------------------------------------------------------- #
+# token resampling, its adjoint and the importance backward (csrc/resample.hip)
+RESAMPLE_MAX_N = 1024
+
+
+def resample_supported(n_in: int, n_out: int, d: int, dtype) -> bool:
+    """token counts, widths and dtypes basd_resample_tokens / _adjoint take; everything else keeps the torch chain"""
+    return (1 <= n_in <= RESAMPLE_MAX_N and 1 <= n_out <= RESAMPLE_MAX_N and d >= 4 and d % 4 == 0
+            and dtype in (torch.float32, torch.bfloat16))
+
+
+def _resample_call(entry: str, x: torch.Tensor, n_to: int, n_in: int, n_out: int, out) -> torch.Tensor:
+    _need_cuda(x, out)
+    assert x.dim() == 3, tuple(x.shape)
+    x = x.contiguous()
+    b, _, d = x.shape
+    if out is None:
+        out = torch.empty(b, n_to, d, dtype=x.dtype, device=x.device)
+    assert out.shape == (b, n_to, d) and out.dtype == x.dtype and out.is_contiguous()
+    _check(getattr(lib(), entry)(_ptr(x), _dtype_code(x), b, n_in, n_out, d, _ptr(out), _stream()), entry)
+    return out
+
+
+def resample_tokens(x: torch.Tensor, n_out: int, out=None) -> torch.Tensor:
+    """x [B, n_in, D] fp32 / bf16 -> [B, n_out, D] of the same dtype: F.interpolate(mode="linear",
+    align_corners=False) along the token axis in one launch (basd_resample_tokens); written into ``out`` when given."""
+    return _resample_call("basd_resample_tokens", x, n_out, x.shape[1], n_out, out)
+
+
+def resample_tokens_adjoint(g: torch.Tensor, n_in: int, out=None) -> torch.Tensor:
+    """g [B, n_out, D] fp32 / bf16 -> [B, n_in, D]: the transpose of ``resample_tokens`` (n_in -> n_out) applied to g,
+    i.e. its gradient; gather form, bitwise reproducible (basd_resample_tokens_adjoint)."""
+    return _resample_call("basd_resample_tokens_adjoint", g, n_in, n_in, g.shape[1], out)
+
+
+def procrustes_importance_bwd(g_a: torch.Tensor, a: torch.Tensor, imp: torch.Tensor, out=None) -> torch.Tensor:
+    """g_a, a [batch, n_s] (``procrustes_bwd`` / ``procrustes_prep`` outputs), imp [batch, n_t] (what the prep was given),
+    all fp32 -> g_imp [batch, n_t]: the gradient through a = R imp / sum(R imp) (basd_procrustes_importance_bwd)."""
+    _need_cuda(g_a, a, imp, out)
+    for t_ in (g_a, a, imp):
+        assert t_.dtype == torch.float32 and t_.is_contiguous() and t_.dim() == 2
+    batch, n_s = a.shape
+    n_t = imp.shape[1]
+    assert g_a.shape == a.shape and imp.shape[0] == batch
+    if out is None:
+        out = torch.empty(batch, n_t, dtype=torch.float32, device=a.device)
+    assert out.shape == (batch, n_t) and out.dtype == torch.float32 and out.is_contiguous()
+    _check(lib().basd_procrustes_importance_bwd(_ptr(g_a), _ptr(a), _ptr(imp), batch, n_s, n_t, _ptr(out), _stream()),
+           "basd_procrustes_importance_bwd")
     return out

@@ -16,14 +16,35 @@ from . import functional as BF
 from .layer_selector import GrassmannianLayerSelector
 
 
+class _AlignTokenCountFn(torch.autograd.Function):
+    """The resample and its adjoint as one launch each (basd_resample_tokens / basd_resample_tokens_adjoint)."""
+
+    @staticmethod
+    def forward(ctx, tokens, target_n):
+        ctx.n_in = tokens.shape[1]
+        return BF.get_ops().resample_tokens(tokens, target_n)
+
+    @staticmethod
+    def backward(ctx, g):
+        return BF.get_ops().resample_tokens_adjoint(g, ctx.n_in), None
+
+
 def _align_token_count(tokens: torch.Tensor, target_n: int) -> torch.Tensor:
     """Linear resample along the token axis (reference combined.py:9-14).
 
     The fused Procrustes prep does this on the fly; the function is kept for callers
-    of the reference surface.
+    of the reference surface.  fp32 / bf16 [B, N, D] tensors the kernel provider handles go through its resample
+    entries; CPU tensors, other dtypes and shapes keep the dense matmul.
     """
     if tokens.shape[1] == target_n:
         return tokens
+    ops = BF.get_ops() if tokens.is_cuda else None
+    resample_ok = getattr(ops, "resample_supported", None)
+    if (resample_ok is not None and tokens.dim() == 3 and ops.handles(tokens)
+            and resample_ok(tokens.shape[1], target_n, tokens.shape[2], tokens.dtype)):
+        return _AlignTokenCountFn.apply(tokens, target_n)
+    if tokens.is_cuda:
+        BF.note_library_gemm("_align_token_count: dense resample matmul")
     r = BF.resample_matrix(tokens.shape[1], target_n, tokens.device, tokens.dtype)
     return torch.matmul(r, tokens)
 

@@ -642,15 +642,26 @@ class _ProcrustesFn(torch.autograd.Function):
             g_t, dot_t = ops.procrustes_bwd_rows(p_t, t_w, a, gl, out_dtype=torch.float32)
             g_a = (dot_s + dot_t) / (2.0 * a)
         imp = imp_all.float().reshape(-1, n_t)
-        if n_t != n_s:
+        # the way back from (resampled teacher tokens, normalised importance) to what the caller passed in.  Equal counts:
+        # g_t is already the answer and the normalisation backward is three pointwise launches, kept exactly as they
+        # were (the step of the N_t == N_s configurations computes what it computed before, bit for bit).  Different
+        # counts: the adjoint of the prep kernel's 2-tap resample and the normalisation backward as two C entries
+        # (basd_resample_tokens_adjoint, basd_procrustes_importance_bwd; csrc/resample.hip) -- a dense [n_s, n_t] matrix
+        # and three library GEMMs before, which stay as the fallback of providers without the entries.
+        resample_ok = getattr(ops, "resample_supported", None)
+        if n_t == n_s:
+            tot = imp.sum(-1, keepdim=True)
+            g_imp = (g_a - (a * g_a).sum(-1, keepdim=True)) / tot
+        elif resample_ok is not None and ops.handles(g_t) and resample_ok(n_t, n_s, g_t.shape[2], g_t.dtype):
+            g_imp = ops.procrustes_importance_bwd(g_a.contiguous(), a, imp.contiguous())
+            g_t = ops.resample_tokens_adjoint(g_t, n_t)
+        else:
+            note_library_gemm("Procrustes backward: fp32 matmul (resample adjoint of g_t and of the importance)")
             r = resample_matrix(n_t, n_s, s_w.device)                  # [n_s, n_t]
             tot = (imp @ r.t()).sum(-1, keepdim=True)
             g_raw = (g_a - (a * g_a).sum(-1, keepdim=True)) / tot
             g_imp = g_raw @ r
             g_t = torch.matmul(r.t(), g_t)
-        else:
-            tot = imp.sum(-1, keepdim=True)
-            g_imp = (g_a - (a * g_a).sum(-1, keepdim=True)) / tot
         b = g_s.shape[0] // E
         return (g_t.view(E, b, n_t, -1), g_imp.view(E, b, n_t), *g_s.view(E, b, n_s, -1).unbind(0))
 
