@@ -68,6 +68,8 @@
  *                          basd_attention_fwd_f32x3 refuses the shape
  *   basd_dwconv7_ln_bf16, basd_grn_bf16, basd_patchify_bf16
  *                          the frozen ConvNeXt-V2 teacher trunk (src/models/teacher.py through timm)
+ *   basd_conv3x3_bf16, basd_conv7x7s2_relu_bf16, basd_maxpool3x3s2_bf16, basd_add_relu_bf16
+ *                          the frozen ResNet teacher trunk (src/models/teacher.py through timm)
  *   basd_resample_u8, basd_ta_normalize_u8
  *                          the torchvision v2 transforms of both training views (src/data/datasets.py:80-94 clean /
  *                          evaluation view, :137-149 augmented view), which the reference runs in its loader workers
@@ -613,6 +615,38 @@ int basd_grn_bf16(void* x, const float* weight, const float* bias, int B, int HW
  * H % p == 0, W % p == 0, K_pad % 8 == 0, K_pad >= C p p; out 16-byte aligned.  Exact (a copy). */
 int basd_patchify_bf16(const void* x, int B, int C, int H, int W, int64_t sb, int64_t sc, int64_t sh, int64_t sw,
                        int p, int K_pad, void* out, void* stream);
+
+/* ---- frozen ResNet teacher trunk (models/cnn.py, ResNet-v1.5 bottlenecks with BatchNorm folded into weight and bias).
+ * Activations use the channels-last rows of the ConvNeXt section above: [B, H, W, ld] bf16, columns C .. ld zero on
+ * output and never read on input (a 64-channel map lives in rows of 128, the narrowest N of basd_gemm_bf16); 16-byte
+ * aligned buffers.  The 1 x 1 convolutions are basd_gemm_bf16 on these rows, the strided one behind
+ * basd_patchify_bf16 at p = 1 on the [:, :, ::2, ::2] view. */
+
+/* 3 x 3 convolution, zero padding 1, stride 1 or 2, C -> C channels, as an implicit GEMM on the bf16 matrix cores
+ * (fp32 accumulation, one rounding at the store; the im2col matrix is never stored):
+ *   y[b, oh, ow, n] = epi(sum_{dy, dx, c} in(x[b, oh s + dy - 1, ow s + dx - 1, c]) w9[n][(dy 3 + dx) C + c] + bias[n])
+ * x [B, H, W, ld_in], w9 [C, 9 C] bf16 tap-major, bias [C] bf16, y [B, Ho, Wo, ld_out] with Ho = (H - 1) / s + 1.
+ * relu_in != 0: in = max(0, .) on every input element as it is staged (the 1 x 1 convolution in front stays a plain
+ * GEMM + bias); relu_out != 0: epi = max(0, .) before the bf16 rounding.  C % 64 == 0, 64 <= C <= 512; any H, W >= 1;
+ * ld % 8 == 0, C <= ld_in, C <= ld_out <= 2 C; B Ho Wo <= 0x7fffff00 output pixels (the kernel decodes pixel indices
+ * in int); y must not alias x. */
+int basd_conv3x3_bf16(const void* x, const void* w9, const void* bias, int B, int H, int W, int C, int stride,
+                      int ld_in, int ld_out, int relu_in, int relu_out, void* y, void* stream);
+
+/* The stem: 7 x 7 convolution, padding 3, stride 2, 3 -> 64 channels, + bias, ReLU.  x [B, 3, H, W] bf16 addressed
+ * through ELEMENT strides (sb, sc, sh, sw) as in basd_patchify_bf16 (NCHW and channels-last are the same call),
+ * w [64, K_pad] bf16 with column (dy 7 + dx) 3 + c and zero columns behind 147 (K_pad % 8 == 0, K_pad >= 160),
+ * bias [64] bf16 -> y [B, H1, W1, ld_out], H1 = (H - 1) / 2 + 1, 64 <= ld_out <= 128, ld_out % 8 == 0. */
+int basd_conv7x7s2_relu_bf16(const void* x, const void* w, const void* bias, int B, int H, int W, int64_t sb,
+                             int64_t sc, int64_t sh, int64_t sw, int K_pad, int ld_out, void* y, void* stream);
+
+/* 3 x 3 max pool, stride 2, padding 1 (the padding never wins): x [B, H, W, ld_in] -> y [B, Ho, Wo, ld_out],
+ * Ho = (H - 1) / 2 + 1.  Exact.  C % 8 == 0, ld % 8 == 0, C <= ld; y must not alias x. */
+int basd_maxpool3x3s2_bf16(const void* x, int B, int H, int W, int C, int ld_in, int ld_out, void* y, void* stream);
+
+/* The end of a bottleneck block, in place:  y <- bf16(max(0, float(y) + float(r)))  on rows x C with row strides
+ * ld_y, ld_r (elements; the columns behind C are not touched).  C % 8 == 0, ld % 8 == 0, C <= ld. */
+int basd_add_relu_bf16(void* y, const void* r, int64_t rows, int C, int ld_y, int ld_r, void* stream);
 
 /* ---- both training views from one uint8 batch (data/device_views.py).  The CPU functions of data/transforms.py are the
  * definition, stage by stage. */

@@ -37,6 +37,7 @@ EXPORTS = (
     "basd_resample_u8", "basd_ta_normalize_u8", "basd_cls_tally", "basd_resample_u8_packed",
     "basd_mixup_cutmix", "basd_selector_token_grad_workspace_bytes", "basd_selector_token_grad",
     "basd_tap_grad_scatter", "basd_resample_tokens", "basd_resample_tokens_adjoint", "basd_procrustes_importance_bwd",
+    "basd_conv3x3_bf16", "basd_conv7x7s2_relu_bf16", "basd_maxpool3x3s2_bf16", "basd_add_relu_bf16",
 )
 
 
@@ -115,6 +116,10 @@ _SIGNATURES = {
     "basd_resample_tokens": (_P, _I, _I, _I, _I, _I, _P, _P),
     "basd_resample_tokens_adjoint": (_P, _I, _I, _I, _I, _I, _P, _P),
     "basd_procrustes_importance_bwd": (_P, _P, _P, _I, _I, _I, _P, _P),
+    "basd_conv3x3_bf16": (_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P),
+    "basd_conv7x7s2_relu_bf16": (_P, _P, _P, _I, _I, _I, _I64, _I64, _I64, _I64, _I, _I, _P, _P),
+    "basd_maxpool3x3s2_bf16": (_P, _I, _I, _I, _I, _I, _I, _P, _P),
+    "basd_add_relu_bf16": (_P, _P, _I64, _I, _I, _I, _P),
 }
 
 
@@ -1306,6 +1311,94 @@ def patchify(x: torch.Tensor, p: int, k_pad: int) -> torch.Tensor:
     _check(lib().basd_patchify_bf16(_ptr(x), b, c, h, w, ctypes.c_int64(sb), ctypes.c_int64(sc), ctypes.c_int64(sh),
                                     ctypes.c_int64(sw), p, k_pad, _ptr(out), _stream()), "basd_patchify_bf16")
     return out
+
+
+# --------------------------------------------------------------------------- ResNet teacher trunk (csrc/resnet.hip)
+STEM_K_PAD = 160          # 7 x 7 x 3 = 147 columns of the stem's weight image, padded to whole k-blocks of 32
+
+
+def conv3x3_supported(c: int, ld_in: int, ld_out: int, stride: int = 1) -> bool:
+    return (c % 64 == 0 and 64 <= c <= 512 and stride in (1, 2) and ld_in % 8 == 0 and ld_out % 8 == 0 and c <= ld_in
+            and c <= ld_out <= 2 * c)
+
+
+def conv3x3(x: torch.Tensor, w9: torch.Tensor, bias: torch.Tensor, stride: int = 1, relu_in: bool = False,
+            relu_out: bool = False, ld_out: int | None = None) -> torch.Tensor:
+    """x [B, H, W, ld_in] bf16 channels-last rows, w9 [C, 9 C] bf16 tap-major (column (dy 3 + dx) C + c), bias [C] bf16
+    -> epi(conv3x3(in(x), padding 1, stride) + bias) [B, Ho, Wo, ld_out] bf16, columns C .. ld_out zero; in / epi =
+    ReLU if ``relu_in`` / ``relu_out``."""
+    _need_cuda(x, w9, bias)
+    assert x.dtype == w9.dtype == bias.dtype == torch.bfloat16 and x.dim() == 4 and x.is_contiguous()
+    b, h, w, ld_in = x.shape
+    c = w9.shape[0]
+    ld_out = ld_in if ld_out is None else ld_out
+    if not (w9.shape == (c, 9 * c) and bias.shape == (c,) and conv3x3_supported(c, ld_in, ld_out, stride)):
+        raise BasdNativeError(f"conv3x3: C={c} ld_in={ld_in} ld_out={ld_out} stride={stride} w9={tuple(w9.shape)} is "
+                              "not tiled (C % 64 == 0, 64 <= C <= 512, C <= ld_out <= 2 C, stride 1 or 2)")
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    y = torch.empty(b, ho, wo, ld_out, dtype=torch.bfloat16, device=x.device)
+    _check(lib().basd_conv3x3_bf16(_ptr(x), _ptr(w9.contiguous()), _ptr(bias.contiguous()), b, h, w, c, stride, ld_in,
+                                   ld_out, int(relu_in), int(relu_out), _ptr(y), _stream()), "basd_conv3x3_bf16")
+    return y
+
+
+def conv7x7s2_relu_supported(ld_out: int) -> bool:
+    return ld_out % 8 == 0 and 64 <= ld_out <= 128
+
+
+def conv7x7s2_relu(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, ld_out: int = 128) -> torch.Tensor:
+    """x [B, 3, H, W] bf16 in any strides, w [64, K_pad] bf16 with column (dy 7 + dx) 3 + c (zero behind 147), bias [64]
+    bf16 -> relu(conv7x7(x, padding 3, stride 2) + bias) [B, H1, W1, ld_out] bf16, columns 64 .. ld_out zero."""
+    _need_cuda(x, w, bias)
+    assert x.dtype == w.dtype == bias.dtype == torch.bfloat16 and x.dim() == 4
+    b, c, h, wd = x.shape
+    if not (c == 3 and w.dim() == 2 and w.shape[0] == 64 and w.shape[1] >= STEM_K_PAD and w.shape[1] % 8 == 0
+            and bias.shape == (64,) and conv7x7s2_relu_supported(ld_out)):
+        raise BasdNativeError(f"conv7x7s2_relu: x={tuple(x.shape)} w={tuple(w.shape)} ld_out={ld_out} is not tiled "
+                              f"(3 input channels, w [64, K_pad >= {STEM_K_PAD}], 64 <= ld_out <= 128)")
+    y = torch.empty(b, (h - 1) // 2 + 1, (wd - 1) // 2 + 1, ld_out, dtype=torch.bfloat16, device=x.device)
+    sb, sc, sh, sw = x.stride()
+    _check(lib().basd_conv7x7s2_relu_bf16(_ptr(x), _ptr(w.contiguous()), _ptr(bias.contiguous()), b, h, wd,
+                                          ctypes.c_int64(sb), ctypes.c_int64(sc), ctypes.c_int64(sh), ctypes.c_int64(sw),
+                                          w.shape[1], ld_out, _ptr(y), _stream()), "basd_conv7x7s2_relu_bf16")
+    return y
+
+
+def maxpool3x3s2_supported(c: int, ld_in: int, ld_out: int) -> bool:
+    return c % 8 == 0 and c >= 8 and ld_in % 8 == 0 and ld_out % 8 == 0 and c <= ld_in and c <= ld_out
+
+
+def maxpool3x3s2(x: torch.Tensor, c: int, ld_out: int | None = None) -> torch.Tensor:
+    """x [B, H, W, ld_in] bf16 channels-last rows with c channels -> max_pool2d(3, stride 2, padding 1)
+    [B, Ho, Wo, ld_out] bf16, columns c .. ld_out zero.  Exact."""
+    _need_cuda(x)
+    assert x.dtype == torch.bfloat16 and x.dim() == 4 and x.is_contiguous()
+    b, h, w, ld_in = x.shape
+    ld_out = ld_in if ld_out is None else ld_out
+    if not maxpool3x3s2_supported(c, ld_in, ld_out):
+        raise BasdNativeError(f"maxpool3x3s2: C={c} ld_in={ld_in} ld_out={ld_out} (multiples of 8, C <= ld)")
+    y = torch.empty(b, (h - 1) // 2 + 1, (w - 1) // 2 + 1, ld_out, dtype=torch.bfloat16, device=x.device)
+    _check(lib().basd_maxpool3x3s2_bf16(_ptr(x), b, h, w, c, ld_in, ld_out, _ptr(y), _stream()),
+           "basd_maxpool3x3s2_bf16")
+    return y
+
+
+def add_relu_supported(c: int, ld_y: int, ld_r: int) -> bool:
+    return c % 8 == 0 and c >= 8 and ld_y % 8 == 0 and ld_r % 8 == 0 and c <= ld_y and c <= ld_r
+
+
+def add_relu_(y: torch.Tensor, r: torch.Tensor, c: int | None = None) -> torch.Tensor:
+    """y <- bf16(max(0, y + r)) IN PLACE on the first c columns of the rows y [rows, ld_y], r [rows, ld_r] (bf16,
+    contiguous; c defaults to the whole row).  Returns y."""
+    _need_cuda(y, r)
+    assert y.dtype == r.dtype == torch.bfloat16 and y.dim() == 2 and r.dim() == 2 and y.is_contiguous() and r.is_contiguous()
+    assert y.shape[0] == r.shape[0]
+    c = y.shape[1] if c is None else c
+    if not add_relu_supported(c, y.shape[1], r.shape[1]):
+        raise BasdNativeError(f"add_relu_: C={c} ld_y={y.shape[1]} ld_r={r.shape[1]} (multiples of 8, C <= ld)")
+    _check(lib().basd_add_relu_bf16(_ptr(y), _ptr(r), ctypes.c_int64(y.shape[0]), c, y.shape[1], r.shape[1], _stream()),
+           "basd_add_relu_bf16")
+    return y
 
 
 # --------------------------------------------------------------------------- device-side dual views (csrc/dual_view.hip)

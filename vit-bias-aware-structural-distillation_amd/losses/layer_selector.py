@@ -37,7 +37,19 @@ def marchenko_pastur_rank(features: torch.Tensor) -> int:
     ops = get_ops()
     m, d = features.shape
     if d > 1024:
-        raise BF.BasdShapeError(f"marchenko_pastur_rank: D={d} > 1024 (the device rank count sorts up to 1024 values)")
+        # CNN teachers (ResNet: D = 2048).  With fewer rows than columns the reference takes the M x M Gram X X^T
+        # (layer_selector.py:14-15): it has the same non-zero spectrum, and M <= 1024 fits the eigen-solver and the
+        # device rank count.  Rows are zero-padded to a multiple of 32 (the Gram kernels' regular shapes): that only adds
+        # zero eigenvalues, and the count uses the M largest.
+        if m > 1024:
+            raise BF.BasdShapeError(f"marchenko_pastur_rank: M={m} and D={d} both > 1024 (the eigen-solver and the device "
+                                    "rank count take up to 1024 values: calibrate on at most 1024 tokens)")
+        m_pad = -(-m // 32) * 32
+        xt = torch.zeros(d, m_pad, device=features.device, dtype=torch.float32)
+        xt[:, :m] = features.t()
+        gram, _ = ops.token_gram(xt, torch.eye(m_pad, device=features.device, dtype=torch.float32))
+        sigma, _, _ = BF.psd_eig(gram.unsqueeze(0))
+        return int(ops.mp_rank(sigma ** 2, m, d, d)[0].item())
     # X^T X in fp64: the fused one-pass kernel up to 256 columns, projection-free split-K fp64 MFMA GEMM beyond
     # (ViT-B .. ViT-H teachers: D_t = 768 .. 1280 -> 1024 is covered; the eigen-solve is the blocked one for D > 192)
     eye = torch.eye(d, device=features.device, dtype=torch.float32)

@@ -6,16 +6,26 @@ family of ``models/convnext.py`` (what the reference's cross-arch overlay names,
 The reference takes CNN teachers from timm (``src/models/teacher.py:118``) and only ever calls ``forward_features``
 on them (``teacher.py:184-191``).  timm / torchvision are not available offline, so the trunks are defined in this
 package with the torchvision / timm parameter names (``conv1``, ``bn1``, ``layer1..4.N.conv1`` ...) so that a local
-state dict of either package loads.  The frozen ResNet trunk is a black box for the BASD step (SURVEY section 8,
-"c3"): it runs through PyTorch-ROCm / MIOpen in channels-last bf16, no hand-written kernel is involved.  The
-ConvNeXt-V2 trunk runs on the package's own kernels (``csrc/convnext.hip`` + ``basd_gemm_bf16``).
+state dict of either package loads.
+
+Two forwards of the same ResNet parameters, as for the ConvNeXt-V2 trunk:
+
+* plain PyTorch (``nn.Conv2d``, ``nn.BatchNorm2d``, ``nn.MaxPool2d``): the CPU path, the path of every dtype but bf16
+  and of a model with gradients; on the device it runs in library kernels (MIOpen);
+* the fused inference path of a frozen bf16 model on the device (``prepare_fused`` once after the weights are
+  loaded): BatchNorm is folded into weight and bias, activations are channels-last rows ``[B H W, ld]`` (64 channels
+  in rows of 128), the 1 x 1 convolutions are ``basd_gemm_bf16`` (the strided one behind a ``basd_patchify_bf16``
+  row gather), the 3 x 3 convolutions, the stem, the pool and the residual add + ReLU are ``csrc/resnet.hip``.  It
+  enqueues no convolution, batch-norm, pooling or GEMM of a library.  A bf16 no-grad device forward that cannot
+  take it is reported through ``library_fallback``.
 """
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 
-from .convnext import CONVNEXT_PRESETS
+from ..losses._ops import get_ops, library_fallback
+from .convnext import CONVNEXT_PRESETS, _row_width
 
 
 class Bottleneck(nn.Module):
@@ -46,6 +56,7 @@ class ResNet(nn.Module):
     def __init__(self, depths=(3, 4, 6, 3), num_classes: int = 0, in_chans: int = 3):
         super().__init__()
         self.inplanes = 64
+        self._fused = None
         self.conv1 = nn.Conv2d(in_chans, 64, 7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
         self.relu = nn.ReLU(inplace=True)
@@ -68,9 +79,126 @@ class ResNet(nn.Module):
         blocks += [Bottleneck(self.inplanes, planes) for _ in range(depth - 1)]
         return nn.Sequential(*blocks)
 
-    def forward_features(self, x):
+    # ------------------------------------------------------------------------------------------------- plain PyTorch
+    def _forward_plain(self, x):
         x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
         return self.layer4(self.layer3(self.layer2(self.layer1(x))))        # [B, 2048, H/32, W/32]
+
+    # ------------------------------------------------------------------------------------------------- fused path
+    def _stages(self):
+        return [getattr(self, f"layer{i}") for i in range(1, 5)]
+
+    def fused_refusal(self) -> str | None:
+        """Why the kernels do not take this architecture (None: they do)."""
+        ops = get_ops()
+        if not hasattr(ops, "conv3x3"):
+            return "the kernel provider has no ResNet trunk entries"
+        if self.conv1.weight.shape[1] != 3:
+            return f"the stem kernel takes 3 input channels (got {self.conv1.weight.shape[1]})"
+        ld = _row_width(64)
+        if not (ops.conv7x7s2_relu_supported(ld) and ops.maxpool3x3s2_supported(64, ld, ld)):
+            return f"stem rows of {ld} are not tiled by the stem / pool kernels"
+        c_in = 64
+        for stage in self._stages():
+            for blk in stage:
+                if not isinstance(blk, Bottleneck):
+                    return f"{type(blk).__name__} blocks (bottleneck blocks only)"
+                p, c_out, s = blk.conv2.weight.shape[0], blk.conv3.weight.shape[0], blk.conv2.stride[0]
+                ld_in, ld_p, ld_o = _row_width(c_in), _row_width(p), _row_width(c_out)
+                if not (ops.gemm_supported(ld_p, ld_in) and ops.conv3x3_supported(p, ld_p, ld_p, s)
+                        and ops.gemm_supported(ld_o, ld_p) and ops.gemm_supported(ld_o, ld_in)
+                        and ld_o == c_out and ops.add_relu_supported(c_out, ld_o, ld_o)):
+                    return f"bottleneck {c_in} -> {p} -> {c_out} (stride {s}) is not tiled by the GEMM / trunk kernels"
+                c_in = c_out
+        return None
+
+    @torch.no_grad()
+    def prepare_fused(self) -> bool:
+        """Build the weight images of the fused path once (frozen teacher: no refresh).  BatchNorm is folded in fp32
+        from the stored parameters, s = gamma / sqrt(var + eps): w' = bf16(w s), b' = bf16(beta - mean s).  The 3 x 3
+        images are tap-major [C, 9 C], the 1 x 1 images [N_ld, K_ld] with zero rows (and zero bias) for padded output
+        channels and zero columns for padded input channels, the stem image [64, K_pad] in the kernel's patch order."""
+        self._fused = None
+        if self.fused_refusal() is not None or any(p.requires_grad for p in self.parameters()):
+            return False
+        ops = get_ops()
+        bf = torch.bfloat16
+
+        def fold(conv, bn):
+            s = bn.weight.float() / torch.sqrt(bn.running_var.float() + bn.eps)
+            return conv.weight.float() * s.view(-1, 1, 1, 1), bn.bias.float() - bn.running_mean.float() * s
+
+        def image(w2d, bias, n_ld, k_ld):
+            n, k = w2d.shape
+            w = torch.zeros(n_ld, k_ld, dtype=bf, device=w2d.device)
+            w[:n, :k] = w2d.to(bf)
+            b = torch.zeros(n_ld, dtype=bf, device=w2d.device)
+            b[:n] = bias.to(bf)
+            return w, b
+
+        def pointwise(conv, bn, ld_in):
+            w, b = fold(conv, bn)
+            return image(w.flatten(1), b, _row_width(w.shape[0]), ld_in)
+
+        w, b = fold(self.conv1, self.bn1)
+        fused = {"ld0": _row_width(64), "blocks": [],
+                 "stem": image(w.permute(0, 2, 3, 1).reshape(64, 147), b, 64, ops.STEM_K_PAD)}
+        c_in = 64
+        for stage in self._stages():
+            for blk in stage:
+                p = blk.conv2.weight.shape[0]
+                ld_in = _row_width(c_in)
+                w, b = fold(blk.conv2, blk.bn2)
+                rec = {"c1": pointwise(blk.conv1, blk.bn1, ld_in), "planes": p, "stride": blk.conv2.stride[0],
+                       "c2": image(w.permute(0, 2, 3, 1).reshape(p, 9 * p), b, p, 9 * p),
+                       "c3": pointwise(blk.conv3, blk.bn3, _row_width(p)), "down": None}
+                if blk.downsample is not None:
+                    rec["down"] = pointwise(blk.downsample[0], blk.downsample[1], ld_in)
+                fused["blocks"].append(rec)
+                c_in = blk.conv3.weight.shape[0]
+        fused["c_last"] = c_in
+        self._fused = fused
+        return True
+
+    def _forward_fused(self, x):
+        """x [B, 3, H, W] bf16 (any strides) -> [B, 2048, H/32, W/32] bf16, a channels-last view of the last rows"""
+        ops, fz = get_ops(), self._fused
+        ld = fz["ld0"]
+        t = ops.maxpool3x3s2(ops.conv7x7s2_relu(x, *fz["stem"], ld_out=ld), 64, ld)
+        b, h, w, _ = t.shape
+        rows = t.view(b * h * w, ld)
+        for rec in fz["blocks"]:
+            ld_in, s = rows.shape[1], rec["stride"]
+            y = ops.gemm_bf16(rows, *rec["c1"])                                          # conv1 + bn1; its ReLU ...
+            y = ops.conv3x3(y.view(b, h, w, y.shape[1]), *rec["c2"], stride=s, relu_in=True, relu_out=True)   # ... here
+            ho, wo = y.shape[1], y.shape[2]
+            y = ops.gemm_bf16(y.view(b * ho * wo, y.shape[3]), *rec["c3"])
+            idt = rows
+            if rec["down"] is not None:
+                if s != 1:                                                               # rows of the [::s, ::s] pixels
+                    grid = rows.view(b, h, w, ld_in).permute(0, 3, 1, 2)[:, :, ::s, ::s]
+                    idt = ops.patchify(grid, 1, ld_in)
+                idt = ops.gemm_bf16(idt, *rec["down"])
+            rows = ops.add_relu_(y, idt)
+            h, w = ho, wo
+        return rows.view(b, h, w, rows.shape[1])[..., :fz["c_last"]].permute(0, 3, 1, 2)
+
+    def _takes_fused(self, x) -> bool:
+        return (self._fused is not None and not torch.is_grad_enabled() and x.dtype == torch.bfloat16 and x.dim() == 4
+                and x.shape[1] == 3 and self.conv1.weight.dtype == torch.bfloat16)
+
+    def forward_features(self, x):
+        if x.dtype == torch.bfloat16 and not torch.is_grad_enabled() and get_ops().handles(x):
+            if self._takes_fused(x):
+                return self._forward_fused(x)
+            library_fallback("resnet trunk", self.fused_refusal() or
+                             f"shape={tuple(x.shape)} weights={self.conv1.weight.dtype} prepared={self._fused is not None}")
+        return self._forward_plain(x)
+
+    def _apply(self, fn, *args, **kwargs):
+        # .to() / .cuda() / .float() move or recast the parameters: the weight images no longer belong to them
+        self._fused = None
+        return super()._apply(fn, *args, **kwargs)
 
     def forward(self, x):
         return self.fc(self.forward_features(x).mean(dim=(2, 3)))
