@@ -143,7 +143,8 @@ int basd_token_gram(const void* x, int x_dtype, int64_t rows, int d_in,
 /* bf16-input fast path of basd_token_gram: x [rows, d_in] bf16, proj_split [3, d_out, d_in] bf16 =
  * the three-term bf16 split of the fp32 projection (P = Ph + Pm + Pl, each term the bf16
  * rounding of the remainder).  Same outputs / zeroing contract.  d_out in {32, 64, 128, 192},
- * d_in % 32 == 0. */
+ * d_in % 32 == 0.  x is read in 16-byte fragments: x must be 16-byte aligned and batch_stride a multiple of 8
+ * elements (BASD_ERR_SHAPE otherwise). */
 int basd_token_gram_bf16x3(const void* x, int64_t rows, int d_in, int rows_per_batch, int64_t batch_stride,
                            const void* proj_split, int d_out, double* gram, double* colsum, void* stream);
 

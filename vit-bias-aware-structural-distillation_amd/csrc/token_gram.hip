@@ -625,6 +625,10 @@ extern "C" int basd_token_gram_bf16x3(const void* x, int64_t rows, int d_in, int
   if (rows <= 0) return BASD_OK;
   if (rows_per_batch < 1) return fail(BASD_ERR_SHAPE, "token_gram_bf16x3: rows_per_batch < 1");
   if (d_in % KC2 || d_in < KC2) return fail(BASD_ERR_SHAPE, "token_gram_bf16x3: d_in %% 32 != 0 (%d)", d_in);
+  // the kernels read x in 16-byte fragments: with d_in % 32 == 0 every token starts on one if x and the batch stride do
+  if ((((uintptr_t)x) & 15) || batch_stride % 8)
+    return fail(BASD_ERR_SHAPE, "token_gram_bf16x3: need a 16-byte aligned x and batch_stride %% 8 == 0 (got %lld)",
+                (long long)batch_stride);
   hipStream_t st = (hipStream_t)stream;
   switch (d_out) {
     case 32: launch_tg_bf16x3<2>(x, rows, d_in, rows_per_batch, batch_stride, proj_split, gram, colsum, st); break;
