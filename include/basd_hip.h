@@ -309,8 +309,14 @@ int basd_mix_grad_dots(const void* const* x_layers, int x_dtype, int L, int E,
 /* Batched GEMM with fp64 accumulation on the fp64 matrix cores: C[b] = op(A[b]) op(B[b]).
  * Row-major, explicit leading dimensions and batch strides (in elements); A/B dtype F32 or F64,
  * C dtype F32 or F64; trans_x != 0 means the stored matrix is the transpose of op(X).
- * symmetric != 0 (M == N, result known symmetric, e.g. X X^T): only the lower 64x64 tiles are
- * computed and mirrored on store.
+ * symmetric != 0 (M == N, result known symmetric, e.g. X X^T): only the lower triangle is the product; the upper one is
+ * a copy of it.  Tiles of 64x64 above the diagonal are not computed but mirrored from their transposes on store; the
+ * pipelined kernel (aligned shapes) also mirrors the 16x16 sub-tiles above the diagonal inside a diagonal tile, and every
+ * kernel computes the sub-tiles (or tiles) ON the diagonal in full, both triangles.  So c == c^T bit for bit holds for
+ * true X X^T operands only (the same numbers on both sides: (i, j) and (j, i) are then the same sum in the same order);
+ * for a product that is symmetric only in exact arithmetic (X^T (G X)) the elements above the diagonal inside a diagonal
+ * sub-tile are the rounded (i, j) sums, the others copies of (j, i).  Callers of that form read the lower triangle only
+ * (basd_pchol_f64 does).
  * Replaces the torch.bmm / matmul calls of the Procrustes core that must not round to fp32
  * (reference src/losses/relational.py:47 forms the cross-covariance in fp32). */
 int basd_bgemm_f64(const void* a, int a_dtype, int64_t a_stride, int lda, int trans_a,
