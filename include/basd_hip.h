@@ -20,6 +20,10 @@
  *                          torch.linalg.svdvals   layer_selector.py:99
  *                          matrix_norm(ord="nuc") src/losses/relational.py:48
  *   basd_mp_rank           layer_selector.py:17-20 (.median/.sum, on device, no .item())
+ *   basd_sym_tridiag_f64, basd_sym_tridiag_f64_workspace_bytes, basd_tridiag_mp_rank
+ *                          layer_selector.py:8-20 for 1024 < min(M, D) <= 2048 (ViT-H .. 2048-channel teachers at
+ *                          start-up): torch.linalg.eigvalsh + .median / .sum replaced by eigenvalue COUNTS of the
+ *                          fp64 Gram (Householder tridiagonal form + Sturm bisection), no spectrum, no fp32
  *   basd_angle_weights     layer_selector.py:100-108 (acos / spectral weighting / softmax over teacher layers)
  *   basd_angle_weights_bwd autograd of layer_selector.py:86-108 (student frame, angles, softmax, temperatures)
  *   basd_selector_frames   layer_selector.py:69-74, 133-138 (teacher: MP rank, PCA frame cut at the rank) and
@@ -85,7 +89,7 @@
  *   basd_procrustes_importance_bwd
  *                          autograd of relational.py:29-33 w.r.t. the importance, back through the token resample
  *
- * 72 entries in all (basd_version and basd_last_error included).
+ * 75 entries in all (basd_version and basd_last_error included).
  */
 #ifndef BASD_HIP_H
 #define BASD_HIP_H
@@ -219,6 +223,27 @@ int basd_jacobi_svd(float* w, int batch, int m_rows, int n_cols, int ld, int nor
  * status (optional device int32 word): BASD_STATUS_RANK0 when a count is 0, BASD_STATUS_NONFINITE for a NaN spectrum. */
 int basd_mp_rank(const float* evals, int batch, int n, int64_t rows, int d, int cap,
                  int32_t* ranks, int32_t* status, void* stream);
+
+/* Householder reduction of a symmetric fp64 matrix to tridiagonal form with the same eigenvalues (unblocked, one
+ * reflector per column: LAPACK dsytd2 without the reflectors kept).  a [n, n] row-major, BOTH triangles valid; it is
+ * scratch and is overwritten.  diag [n], off [n - 1] receive the tridiagonal matrix.  work: at least
+ * basd_sym_tridiag_f64_workspace_bytes(n) bytes of device memory.  2 <= n <= 2048, anything else is BASD_ERR_SHAPE and
+ * no pointer is touched.  2 (n - 2) + 1 launches on `stream` (two per column, one for the last 2 x 2 block), no host
+ * sync, no grid-wide wait, no floating-point atomics: every reduction has a fixed order, so two runs on the same input
+ * agree bit for bit.  A column that is already zero below the sub-diagonal takes tau = 0 (no update); NaN / Inf in `a`
+ * propagate into diag / off. */
+int64_t basd_sym_tridiag_f64_workspace_bytes(int n);
+int basd_sym_tridiag_f64(double* a, int n, double* diag, double* off, void* work, void* stream);
+
+/* Marchenko-Pastur rank (reference layer_selector.py:8-20) from the tridiagonal form of the smaller-side Gram
+ * (X^T X or X X^T, NOT divided by rows) of an [rows, d] matrix, by Sturm counts: the lower median eigenvalue
+ * (ascending index (n - 1) / 2, what torch.median returns) by 256-section inside the Gershgorin bracket down to
+ * 2^-48 of its width, lambda_+ = med / rows * (1 + sqrt(d / rows))^2, rank[0] = min(cap, #eigenvalues of Gram / rows
+ * at or above lambda_+).  One workgroup, fp64 throughout.  2 <= n <= 2048 and n <= min(rows, d), else BASD_ERR_SHAPE.
+ * status (optional device int32 word): BASD_STATUS_RANK0 when the count is 0 on a finite spectrum; any NaN / Inf in
+ * diag / off gives rank 0 and BASD_STATUS_NONFINITE. */
+int basd_tridiag_mp_rank(const double* diag, const double* off, int n, int64_t rows, int d, int cap,
+                         int32_t* rank, int32_t* status, void* stream);
 
 /* Data-dependent failure raised from host-orchestrated checks (the blocked eigensolver's orthogonality test): ORs
  * `bit` (a BASD_STATUS_* value) into the device health word if any of the n fp64 values is NOT <= tol -- a NaN raises it

@@ -38,6 +38,7 @@ EXPORTS = (
     "basd_mixup_cutmix", "basd_selector_token_grad_workspace_bytes", "basd_selector_token_grad",
     "basd_tap_grad_scatter", "basd_resample_tokens", "basd_resample_tokens_adjoint", "basd_procrustes_importance_bwd",
     "basd_conv3x3_bf16", "basd_conv7x7s2_relu_bf16", "basd_maxpool3x3s2_bf16", "basd_add_relu_bf16",
+    "basd_sym_tridiag_f64_workspace_bytes", "basd_sym_tridiag_f64", "basd_tridiag_mp_rank",
 )
 
 
@@ -120,6 +121,9 @@ _SIGNATURES = {
     "basd_conv7x7s2_relu_bf16": (_P, _P, _P, _I, _I, _I, _I64, _I64, _I64, _I64, _I, _I, _P, _P),
     "basd_maxpool3x3s2_bf16": (_P, _I, _I, _I, _I, _I, _I, _P, _P),
     "basd_add_relu_bf16": (_P, _P, _I64, _I, _I, _I, _P),
+    "basd_sym_tridiag_f64_workspace_bytes": (_I,),
+    "basd_sym_tridiag_f64": (_P, _I, _P, _P, _P, _P),
+    "basd_tridiag_mp_rank": (_P, _P, _I, _I64, _I, _I, _P, _P, _P),
 }
 
 
@@ -468,6 +472,35 @@ def mp_rank(evals: torch.Tensor, rows: int, d: int, cap: int) -> torch.Tensor:
     _check(lib().basd_mp_rank(_ptr(evals), batch, n, ctypes.c_int64(rows), d, cap, _ptr(ranks),
                               _ptr(status_word(evals.device)), _stream()), "basd_mp_rank")
     return ranks
+
+
+TRIDIAG_MAX_N = 2048         # largest order basd_sym_tridiag_f64 / basd_tridiag_mp_rank take (diag + off^2 in LDS)
+
+
+def sym_tridiag(a64: torch.Tensor):
+    """a64 [n, n] fp64, symmetric with both triangles valid, 2 <= n <= 2048 -> (diag [n], off [n - 1]) fp64 of a
+    tridiagonal matrix with the same eigenvalues (unblocked Householder, 2 (n - 2) + 1 launches on the current stream,
+    no host sync).  ``a64`` is SCRATCH: it is overwritten by the reduction."""
+    _need_cuda(a64)
+    assert a64.dtype == torch.float64 and a64.dim() == 2 and a64.shape[0] == a64.shape[1] and a64.is_contiguous()
+    n = a64.shape[0]
+    diag = torch.empty(n, dtype=torch.float64, device=a64.device)
+    off = torch.empty(max(n - 1, 0), dtype=torch.float64, device=a64.device)
+    work = torch.empty(lib().basd_sym_tridiag_f64_workspace_bytes(n) // 8, dtype=torch.float64, device=a64.device)
+    _check(lib().basd_sym_tridiag_f64(_ptr(a64), n, _ptr(diag), _ptr(off), _ptr(work), _stream()), "basd_sym_tridiag_f64")
+    return diag, off
+
+
+def tridiag_mp_rank(diag: torch.Tensor, off: torch.Tensor, rows: int, d: int, cap: int) -> torch.Tensor:
+    """(diag [n], off [n - 1]) fp64 of a tridiagonal matrix with the spectrum of the smaller-side Gram of an [rows, d]
+    matrix (n <= min(rows, d)) -> int32 [1] Marchenko-Pastur rank on the device, by Sturm counts (no spectrum)."""
+    _need_cuda(diag, off)
+    assert diag.dtype == torch.float64 and off.dtype == torch.float64 and off.numel() == diag.numel() - 1
+    diag, off = diag.contiguous(), off.contiguous()
+    rank = torch.empty(1, dtype=torch.int32, device=diag.device)
+    _check(lib().basd_tridiag_mp_rank(_ptr(diag), _ptr(off), diag.numel(), ctypes.c_int64(rows), d, cap, _ptr(rank),
+                                      _ptr(status_word(diag.device)), _stream()), "basd_tridiag_mp_rank")
+    return rank
 
 
 def flag_if_exceeds(values: torch.Tensor, tol: float, bit: int) -> None:

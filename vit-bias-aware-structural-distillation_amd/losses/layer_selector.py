@@ -33,6 +33,9 @@ def marchenko_pastur_rank(features: torch.Tensor) -> int:
 
     Returns a Python int like the reference (this entry is the start-up path,
     src/models/teacher.py:161-177; the train step keeps ranks on the device).
+
+    Takes min(M, D) <= 1024 (the eigen-solver and the device rank count).  Beyond that, up to 2048, see
+    ``marchenko_pastur_rank_wide``; ``mp_rank_route`` tells which of the two a shape takes.
     """
     ops = get_ops()
     m, d = features.shape
@@ -56,6 +59,56 @@ def marchenko_pastur_rank(features: torch.Tensor) -> int:
     gram, _ = ops.token_gram(features.contiguous(), eye)
     sigma, _, _ = BF.psd_eig(gram.unsqueeze(0))
     return int(ops.mp_rank(sigma ** 2, m, d, d)[0].item())
+
+
+MP_SPECTRUM_MAX = 1024       # marchenko_pastur_rank: full spectrum (eigen-solver + one-workgroup sort)
+MP_COUNTED_MAX = 2048        # marchenko_pastur_rank_wide: eigenvalue counts of the tridiagonal form (csrc/tridiag.hip)
+
+
+def mp_rank_route(m: int, d: int) -> str:
+    """Which implementation the MP rank of an [m, d] matrix takes at start-up: "spectrum" (``marchenko_pastur_rank``:
+    every shape it has ever taken, unchanged) up to 1024 on the smaller side, "counted"
+    (``marchenko_pastur_rank_wide``) up to 2048; beyond that ``BasdShapeError``.  Pure host logic."""
+    n = min(int(m), int(d))
+    if n > MP_COUNTED_MAX:
+        raise BF.BasdShapeError(f"Marchenko-Pastur rank: M={m} and D={d} both > {MP_COUNTED_MAX} (the tridiagonal "
+                                f"reduction and the Sturm count take up to {MP_COUNTED_MAX} values on the smaller side)")
+    return "counted" if n > MP_SPECTRUM_MAX else "spectrum"
+
+
+def _gram_slabs(k: int) -> int:
+    """Split-K slabs of the wide route's Gram over its k summed rows: about 2048 rows per slab, at most 8 (each slab
+    is an [n, n] fp64 partial sum: 8 x 32 MiB at n = 2048)."""
+    return max(1, min(8, k // 2048))
+
+
+@torch.no_grad()
+def marchenko_pastur_rank_wide(features: torch.Tensor) -> int:
+    """MP rank of an [M, D] matrix with 2 <= min(M, D) <= 2048 (reference layer_selector.py:8-20), in fp64 throughout
+    and without a spectrum: the Gram on the smaller side (X^T X if M >= D, else X X^T: the reference's rule) is
+    accumulated in fp64 by the split-K batched GEMM (symmetric tiles, no identity projection, no library GEMM), reduced
+    to tridiagonal form by Householder reflectors, and the lower median eigenvalue and the number of eigenvalues above
+    the noise edge are found by Sturm counts on the device.  Returns a Python int (one synchronisation)."""
+    ops = get_ops()
+    m, d = features.shape
+    n = min(m, d)
+    if n < 2 or n > MP_COUNTED_MAX:
+        raise BF.BasdShapeError(f"marchenko_pastur_rank_wide: min(M, D) = {n} for M={m}, D={d} is outside 2 .. "
+                                f"{MP_COUNTED_MAX} (the tridiagonal reduction and the Sturm count keep {MP_COUNTED_MAX} "
+                                "values per workgroup)")
+    x = features.float()
+    if m < d:
+        x = x.t()                                   # [k, n]: the Gram is x^T x, summed over the k rows
+    k = x.shape[0]
+    slabs = _gram_slabs(k)
+    k_pad = -(-k // (4 * slabs)) * (4 * slabs)      # zero rows add nothing to x^T x
+    xs = torch.zeros(k_pad, n, device=features.device, dtype=torch.float32)
+    xs[:k] = x
+    xs = xs.view(slabs, k_pad // slabs, n)
+    gram = ops.bgemm_f64(xs, xs, trans_a=True, symmetric=True)          # [slabs, n, n] fp64
+    gram = gram.sum(dim=0) if slabs > 1 else gram[0]
+    diag, off = ops.sym_tridiag(gram.contiguous())                      # gram is scratch from here on
+    return int(ops.tridiag_mp_rank(diag, off, m, d, n)[0].item())
 
 
 class GrassmannianLayerSelector(nn.Module):

@@ -23,7 +23,7 @@ from typing import NamedTuple
 import torch
 import torch.nn as nn
 
-from ..losses.layer_selector import marchenko_pastur_rank
+from ..losses.layer_selector import marchenko_pastur_rank, marchenko_pastur_rank_wide, mp_rank_route
 from .vit import VIT_PRESETS, create_vit
 
 
@@ -201,10 +201,14 @@ def estimate_intrinsic_dim(teacher: TeacherModel, images: torch.Tensor) -> int:
     """Marchenko-Pastur rank of the teacher's LAST-stage tokens over a calibration batch (reference
     teacher.py:161-177; feeds ``_derive_from_teacher``, src/train.py:57-66).  The last stage's tokens are exactly what
     ``extract_intermediates`` returns for its highest layer index, so the tap machinery is reused instead of a second
-    hook; the rank is computed on the GPU (token Gram in fp64 -> blocked or LDS-resident eigensolver -> device count)."""
+    hook; the rank is computed on the GPU (token Gram in fp64 -> blocked or LDS-resident eigensolver -> device count; with
+    more than 1024 on the smaller side, ViT-H and wider: fp64 Gram -> tridiagonal form -> Sturm counts, up to 2048)."""
     tokens, _ = extract_intermediates(teacher, images)
     last = tokens[max(tokens)]
-    return marchenko_pastur_rank(last.reshape(-1, last.shape[-1]).float())
+    x = last.reshape(-1, last.shape[-1]).float()
+    if mp_rank_route(x.shape[0], x.shape[1]) == "counted":
+        return marchenko_pastur_rank_wide(x)
+    return marchenko_pastur_rank(x)
 
 
 @torch.no_grad()
