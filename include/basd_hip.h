@@ -74,6 +74,9 @@
  *                          the frozen ConvNeXt-V2 teacher trunk (src/models/teacher.py through timm)
  *   basd_conv3x3_bf16, basd_conv7x7s2_relu_bf16, basd_maxpool3x3s2_bf16, basd_add_relu_bf16
  *                          the frozen ResNet teacher trunk (src/models/teacher.py through timm)
+ *   basd_window_attention_fwd_bf16, basd_patch_merge_ln_bf16
+ *                          the frozen Swin teacher trunk (src/models/teacher.py through timm: the `layers` container and
+ *                          the nhwc feature map its probe understands)
  *   basd_resample_u8, basd_ta_normalize_u8
  *                          the torchvision v2 transforms of both training views (src/data/datasets.py:80-94 clean /
  *                          evaluation view, :137-149 augmented view), which the reference runs in its loader workers
@@ -89,7 +92,7 @@
  *   basd_procrustes_importance_bwd
  *                          autograd of relational.py:29-33 w.r.t. the importance, back through the token resample
  *
- * 75 entries in all (basd_version and basd_last_error included).
+ * 81 entries in all (basd_version and basd_last_error included).
  */
 #ifndef BASD_HIP_H
 #define BASD_HIP_H
@@ -679,6 +682,37 @@ int basd_maxpool3x3s2_bf16(const void* x, int B, int H, int W, int C, int ld_in,
 /* The end of a bottleneck block, in place:  y <- bf16(max(0, float(y) + float(r)))  on rows x C with row strides
  * ld_y, ld_r (elements; the columns behind C are not touched).  C % 8 == 0, ld % 8 == 0, C <= ld. */
 int basd_add_relu_bf16(void* y, const void* r, int64_t rows, int C, int ld_y, int ld_r, void* stream);
+
+/* ---- frozen Swin teacher trunk (models/swin.py).  Token grids use the channels-last rows of the ConvNeXt section above:
+ * [B, H, W, ld] bf16, columns C .. ld zero on output and never read on input; 16-byte aligned buffers.  The linear layers
+ * are basd_gemm_bf16 on these rows, the LayerNorms basd_layernorm_fwd_bf16 / basd_add_layernorm_fwd_bf16 (ld == C) or
+ * basd_dwconv7_ln_bf16 at H = W = 1 (ld > C). */
+
+/* (Shifted-)window attention of one Swin block, from the packed qkv rows into the rows the output projection reads:
+ *   out[token] = softmax_keys(scale q . k + bias[head][slot_q][slot_k] + mask) v   per window and head, head dim 32.
+ * qkv [B, H, W, ld_qkv] bf16 with q | k | v in the first 3 C columns, each laid out [heads, 32] (the columns behind 3 C
+ * are never read); out [B, H, W, ld_out] bf16, head h in columns 32 h .. 32 h + 31, columns C .. ld_out written as zero.
+ * The cyclic roll by -shift, the partition into ws x ws windows and their inverses are index arithmetic: slot
+ * iy ws + ix of window (wy, wx) is token ((wy ws + iy + shift) mod H, (wx ws + ix + shift) mod W), on the loads and on the
+ * store; no rolled or partitioned copy exists.  mask (shift > 0 only): every slot carries the label 3 ly + lx of its
+ * ROLLED coordinate (wy ws + iy, wx ws + ix), with l = 0 on [0, n - ws), 1 on [n - ws, n - shift), 2 on [n - shift, n)
+ * per axis of length n; a pair of slots with different labels gets -100.0 added (not -inf).
+ * bias: the IMAGE fp32 [heads, 64, 64], entry [h][i][j] = relative-position bias of query slot i and key slot j for
+ * i, j < ws^2 (table[index[i][j]][h]); the rest of a 64 x 64 plane must be allocated and is ignored.
+ * Arithmetic: bf16 products with fp32 accumulation, fp32 logits and softmax (maximum subtracted), probabilities rounded
+ * to bf16 for the second product, fp32 accumulation, one rounding at the store.  Slots behind ws^2 of the 64-slot tile
+ * enter no softmax and are not stored.
+ * 1 <= ws <= 8, 0 <= shift < ws, H % ws == 0, W % ws == 0, C == 32 heads, ld % 8 == 0, 3 C <= ld_qkv, C <= ld_out; out
+ * must not alias qkv.  Anything else is BASD_ERR_SHAPE without a launch. */
+int basd_window_attention_fwd_bf16(const void* qkv, const float* bias, int B, int H, int W, int heads, int C, int ws,
+                                   int shift, int ld_qkv, int ld_out, float scale, void* out, void* stream);
+
+/* Patch merging + LayerNorm: x [B, H, W, ld_in] bf16 with C channels -> y [B, H/2, W/2, 4 C] bf16 (contiguous),
+ *   y[b, r, c, :] = LayerNorm_{4 C}(concat(x[b, 2r, 2c], x[b, 2r+1, 2c], x[b, 2r, 2c+1], x[b, 2r+1, 2c+1])),
+ * gamma / beta fp32 [4 C], two-pass fp32 statistics in a fixed summation order (the same input gives the same bits).
+ * C % 8 == 0, 8 <= 4 C <= 4096, H and W even, ld_in % 8 == 0, C <= ld_in; y must not alias x. */
+int basd_patch_merge_ln_bf16(const void* x, const float* gamma, const float* beta, int B, int H, int W, int C, int ld_in,
+                             float eps, void* y, void* stream);
 
 /* ---- both training views from one uint8 batch (data/device_views.py).  The CPU functions of data/transforms.py are the
  * definition, stage by stage. */

@@ -39,6 +39,7 @@ EXPORTS = (
     "basd_tap_grad_scatter", "basd_resample_tokens", "basd_resample_tokens_adjoint", "basd_procrustes_importance_bwd",
     "basd_conv3x3_bf16", "basd_conv7x7s2_relu_bf16", "basd_maxpool3x3s2_bf16", "basd_add_relu_bf16",
     "basd_sym_tridiag_f64_workspace_bytes", "basd_sym_tridiag_f64", "basd_tridiag_mp_rank",
+    "basd_window_attention_fwd_bf16", "basd_patch_merge_ln_bf16",
 )
 
 
@@ -124,6 +125,8 @@ _SIGNATURES = {
     "basd_sym_tridiag_f64_workspace_bytes": (_I,),
     "basd_sym_tridiag_f64": (_P, _I, _P, _P, _P, _P),
     "basd_tridiag_mp_rank": (_P, _P, _I, _I64, _I, _I, _P, _P, _P),
+    "basd_window_attention_fwd_bf16": (_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P),
+    "basd_patch_merge_ln_bf16": (_P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P),
 }
 
 
@@ -1431,6 +1434,69 @@ def add_relu_(y: torch.Tensor, r: torch.Tensor, c: int | None = None) -> torch.T
         raise BasdNativeError(f"add_relu_: C={c} ld_y={y.shape[1]} ld_r={r.shape[1]} (multiples of 8, C <= ld)")
     _check(lib().basd_add_relu_bf16(_ptr(y), _ptr(r), ctypes.c_int64(y.shape[0]), c, y.shape[1], r.shape[1], _stream()),
            "basd_add_relu_bf16")
+    return y
+
+
+# --------------------------------------------------------------------------- Swin teacher trunk (csrc/swin.hip)
+WINDOW_SLOTS = 64          # slots of a window tile: ws <= 8; also the row / column count of a bias image
+
+
+def window_attention_supported(h: int, w: int, ws: int, shift: int, heads: int, c: int, ld_qkv: int, ld_out: int) -> bool:
+    return (1 <= ws <= 8 and 0 <= shift < ws and h >= ws and w >= ws and h % ws == 0 and w % ws == 0 and heads >= 1
+            and c == 32 * heads and ld_qkv % 8 == 0 and ld_out % 8 == 0 and ld_qkv >= 3 * c and ld_out >= c)
+
+
+def window_bias_image(bias: torch.Tensor) -> torch.Tensor:
+    """bias [heads, ws^2, ws^2] (query slot, key slot) -> the image the kernel reads: fp32 [heads, 64, 64], zero behind
+    ws^2 in both axes.  Built once per block of a frozen teacher."""
+    heads, n, _ = bias.shape
+    assert bias.shape == (heads, n, n) and n <= WINDOW_SLOTS
+    img = torch.zeros(heads, WINDOW_SLOTS, WINDOW_SLOTS, dtype=torch.float32, device=bias.device)
+    img[:, :n, :n] = bias.float()
+    return img
+
+
+def window_attention(qkv: torch.Tensor, bias_img: torch.Tensor, ws: int, shift: int, heads: int, scale: float,
+                     ld_out: int | None = None) -> torch.Tensor:
+    """qkv [B, H, W, ld_qkv] bf16 rows (q | k | v in the first 3 C columns, each [heads, 32]), bias_img from
+    ``window_bias_image`` -> (shifted-)window attention [B, H, W, ld_out] bf16, columns C .. ld_out zero.  Token
+    (y, x) sits in slot ((y - shift) mod H, (x - shift) mod W) of the window partition; the mask of a shifted block is
+    computed from the slot coordinates."""
+    _need_cuda(qkv, bias_img)
+    assert qkv.dtype == torch.bfloat16 and qkv.dim() == 4 and qkv.is_contiguous()
+    assert bias_img.dtype == torch.float32 and bias_img.is_contiguous()
+    b, h, w, ld_qkv = qkv.shape
+    c = 32 * heads
+    ld_out = c if ld_out is None else ld_out
+    if not (window_attention_supported(h, w, ws, shift, heads, c, ld_qkv, ld_out)
+            and bias_img.shape == (heads, WINDOW_SLOTS, WINDOW_SLOTS)):
+        raise BasdNativeError(f"window_attention: grid {h}x{w} ws={ws} shift={shift} heads={heads} ld_qkv={ld_qkv} "
+                              f"ld_out={ld_out} bias={tuple(bias_img.shape)} is not tiled (ws <= 8, head dim 32, grid a "
+                              "multiple of ws, bias image [heads, 64, 64])")
+    out = torch.empty(b, h, w, ld_out, dtype=torch.bfloat16, device=qkv.device)
+    _check(lib().basd_window_attention_fwd_bf16(_ptr(qkv), _ptr(bias_img), b, h, w, heads, c, ws, shift, ld_qkv, ld_out,
+                                                ctypes.c_float(scale), _ptr(out), _stream()),
+           "basd_window_attention_fwd_bf16")
+    return out
+
+
+def patch_merge_ln_supported(c: int, ld_in: int, h: int = 2, w: int = 2) -> bool:
+    return c % 8 == 0 and 8 <= 4 * c <= 4096 and ld_in % 8 == 0 and c <= ld_in and h >= 2 and w >= 2 and h % 2 == 0 and w % 2 == 0
+
+
+def patch_merge_ln(x: torch.Tensor, c: int, gamma: torch.Tensor, beta: torch.Tensor, eps: float) -> torch.Tensor:
+    """x [B, H, W, ld_in] bf16 rows with c channels, gamma / beta fp32 [4 c] -> LayerNorm over the 4 c channels of
+    concat(x[2r, 2c], x[2r+1, 2c], x[2r, 2c+1], x[2r+1, 2c+1]) [B, H/2, W/2, 4 c] bf16."""
+    _need_cuda(x, gamma, beta)
+    assert x.dtype == torch.bfloat16 and x.dim() == 4 and x.is_contiguous()
+    assert gamma.dtype == beta.dtype == torch.float32 and gamma.shape == beta.shape == (4 * c,)
+    b, h, w, ld_in = x.shape
+    if not patch_merge_ln_supported(c, ld_in, h, w):
+        raise BasdNativeError(f"patch_merge_ln: grid {h}x{w} C={c} ld_in={ld_in} is not tiled (even grid, C % 8 == 0, "
+                              "4 C <= 4096)")
+    y = torch.empty(b, h // 2, w // 2, 4 * c, dtype=torch.bfloat16, device=x.device)
+    _check(lib().basd_patch_merge_ln_bf16(_ptr(x), _ptr(gamma.contiguous()), _ptr(beta.contiguous()), b, h, w, c, ld_in,
+                                          ctypes.c_float(eps), _ptr(y), _stream()), "basd_patch_merge_ln_bf16")
     return y
 
 

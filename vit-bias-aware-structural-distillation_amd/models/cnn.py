@@ -1,7 +1,9 @@
 """Convolutional teachers for the cross-architecture configuration: the ResNets defined here (BASELINE configs[2]:
 ResNet-50 teacher, single "layer" of 7 x 7 = 49 tokens x 2048 channels, uniform importance) and the ConvNeXt-V2
 family of ``models/convnext.py`` (what the reference's cross-arch overlay names,
-``configs/experiment/basd_imagenet_cross_arch.yaml:6``), both listed in ``CNN_PRESETS``.
+``configs/experiment/basd_imagenet_cross_arch.yaml:6``), both listed in ``CNN_PRESETS`` -- the table of every teacher
+that hands over ONE feature map instead of per-block tokens, which is why the Swin family of ``models/swin.py`` (a
+hierarchical ViT with an NHWC map of 7 x 7 x 768 / 1024) is listed there too.
 
 The reference takes CNN teachers from timm (``src/models/teacher.py:118``) and only ever calls ``forward_features``
 on them (``teacher.py:184-191``).  timm / torchvision are not available offline, so the trunks are defined in this
@@ -26,6 +28,7 @@ import torch.nn as nn
 
 from ..losses._ops import get_ops, library_fallback
 from .convnext import CONVNEXT_PRESETS, _row_width
+from .swin import SWIN_PRESETS
 
 
 class Bottleneck(nn.Module):
@@ -208,6 +211,7 @@ CNN_PRESETS = {
     "resnet50": lambda: ResNet((3, 4, 6, 3)),
     "resnet101": lambda: ResNet((3, 4, 23, 3)),
     **CONVNEXT_PRESETS,
+    **SWIN_PRESETS,
 }
 
 

@@ -70,7 +70,8 @@ def probe_model(model: nn.Module, img_size: int) -> dict:
     modules collects heads / MLP width, one forward of a zero image through a hook on the LAST stage tells the
     feature format (token / nchw / nhwc) and the token count.  Runs on the model's own device.  It needs the forward
     to go through the stage modules: probe BEFORE a trunk that bypasses them is prepared (``ConvNeXtV2.prepare_fused``
-    replaces the stages' forward on bf16 device tensors, so their hooks no longer fire), as ``load_teacher`` does."""
+    and ``SwinTransformer.prepare_fused`` replace the stages' forward on bf16 device tensors, so their hooks no longer
+    fire), as ``load_teacher`` does."""
     layer_paths = _stage_paths(model)
     width = getattr(model, "embed_dim", None) or getattr(model, "num_features", None)
     heads, attn_name, hidden = [], None, None
@@ -148,8 +149,9 @@ def _probe_scope(model: nn.Module):
 def load_teacher(model_name: str, img_size: int, *, weights: str | None = None, device="cuda",
                  seed: int = 42, patch_size: int | None = None, dtype=torch.bfloat16) -> TeacherModel:
     """Build (not download: reference teacher.py:113-148 fetches from the network) the named teacher -- a ViT preset of
-    ``models/vit.py`` or a CNN preset of ``models/cnn.py`` -- frozen, in eval mode, weights pre-cast to bf16; ``weights``
-    = a local state dict (timm / torchvision parameter names)."""
+    ``models/vit.py`` or a feature-map preset of ``models/cnn.py`` (ResNet, ConvNeXt-V2 and the Swin family of
+    ``models/swin.py``) -- frozen, in eval mode, weights pre-cast to bf16; ``weights`` = a local state dict (timm /
+    torchvision parameter names)."""
     from .cnn import CNN_PRESETS, create_cnn
     if model_name not in VIT_PRESETS and model_name not in CNN_PRESETS and model_name.split(".", 1)[0] in CNN_PRESETS:
         model_name = model_name.split(".", 1)[0]      # timm's pretrained tag ("convnextv2_tiny.fcmae"): weights are local
