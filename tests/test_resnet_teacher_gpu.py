@@ -5,9 +5,9 @@ import os
 
 import pytest
 import torch
-from torch.utils._python_dispatch import TorchDispatchMode
 
 from tests import _resnet_ref as R
+from tests._teacher_cases import bf16_frozen, fused_and_library, images as _images
 
 pytestmark = pytest.mark.gpu
 
@@ -15,45 +15,8 @@ CFG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                    "vit-bias-aware-structural-distillation_amd", "configs", "config.yaml")
 
 
-def _images(batch, size, seed):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(batch, 3, size, size, generator=g)
-    yy, xx = torch.meshgrid(torch.linspace(-1, 1, size), torch.linspace(-1, 1, size), indexing="ij")
-    return x + 2.0 * torch.sin(3.0 * xx) * torch.cos(2.0 * yy)
-
-
-class _OpNames(TorchDispatchMode):
-    def __init__(self):
-        super().__init__()
-        self.names = set()
-
-    def __torch_dispatch__(self, func, types, args=(), kwargs=None):
-        self.names.add(func._schema.name)
-        return func(*args, **(kwargs or {}))
-
-
-def _fused_and_library(model, x):
-    import basd_amd.losses._ops as O
-    xd = x.cuda().to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
-    O.FALLBACKS.clear()
-    O.set_strict(True)
-    ops = _OpNames()
-    try:
-        with torch.no_grad(), O.record_library_gemms() as seen, ops:
-            fused = model.forward_features(xd)
-    finally:
-        O.set_strict(False)
-    assert not O.FALLBACKS and not seen, (dict(O.FALLBACKS), seen)
-    library = sorted(n for n in ops.names if any(k in n for k in ("conv", "batch_norm", "max_pool")))
-    assert not library, library
-    with torch.no_grad():
-        lib = model._forward_plain(xd)
-    torch.cuda.synchronize()
-    return fused, lib
-
-
 def _check_trunk(model, depths, x, label):
-    fused, lib = _fused_and_library(model, x)
+    fused, lib = fused_and_library(model, x, forbidden_ops=("conv", "batch_norm", "max_pool"))
     assert fused.shape == lib.shape and fused.shape[1] == 2048 and fused.dtype == torch.bfloat16
     want = R.tokens(R.forward_features({k: v.cpu() for k, v in model.state_dict().items()}, x.to(torch.bfloat16), depths))
     e_f = R.rel_l2_per_sample(R.tokens(fused.float().cpu()), want)
@@ -69,10 +32,7 @@ def test_small_trunk_against_fp64(depths, size):
     72 px the maps are 18, 9, 5, 3 (odd sizes in front of the stride-2 convolution and gather)"""
     from basd_amd.models.cnn import ResNet
     torch.manual_seed(0)
-    model = R.randomise_bn(ResNet(depths), seed=7).cuda().eval()
-    for p in model.parameters():
-        p.requires_grad = False
-    model = model.to(torch.bfloat16).to(memory_format=torch.channels_last)
+    model = bf16_frozen(R.randomise_bn(ResNet(depths), seed=7).cuda(), memory_format=torch.channels_last)
     assert model.prepare_fused()
     _check_trunk(model, depths, _images(2, size, seed=1), f"small trunk {depths} {size} px")
 

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from tests import _swin_ref as R
+from tests._teacher_cases import bf16_frozen, fused_and_library, images as _images
 
 pytestmark = pytest.mark.gpu
 
@@ -15,32 +16,8 @@ CFG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 SWIN_T = "swin_tiny_patch4_window7_224"
 
 
-def _images(batch, size, seed):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(batch, 3, size, size, generator=g)
-    yy, xx = torch.meshgrid(torch.linspace(-1, 1, size), torch.linspace(-1, 1, size), indexing="ij")
-    return x + 2.0 * torch.sin(3.0 * xx) * torch.cos(2.0 * yy)
-
-
-def _fused_and_library(model, x):
-    import basd_amd.losses._ops as O
-    xd = x.cuda().to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
-    O.FALLBACKS.clear()
-    O.set_strict(True)
-    try:
-        with torch.no_grad(), O.record_library_gemms() as seen:
-            fused = model.forward_features(xd)
-    finally:
-        O.set_strict(False)
-    assert not O.FALLBACKS and not seen, (dict(O.FALLBACKS), seen)
-    with torch.no_grad():
-        lib = model._forward_plain(xd)
-    torch.cuda.synchronize()
-    return fused, lib
-
-
 def _check_trunk(model, depths, heads, ws, x, label):
-    fused, lib = _fused_and_library(model, x)
+    fused, lib = fused_and_library(model, x)
     assert fused.shape == lib.shape and fused.shape[3] == model.embed_dim and fused.shape[1] == x.shape[2] // 32
     want = R.tokens(R.forward_features(model.state_dict(), x.to(torch.bfloat16), depths, heads, ws))
     e_f = R.rel_l2_per_sample(R.tokens(fused.float().cpu()), want)
@@ -59,13 +36,7 @@ def test_small_trunk_at_128px_against_fp64(dims, heads):
     from basd_amd.models.swin import SwinTransformer
     depths = (2, 2, 2, 2)
     torch.manual_seed(0)
-    model = R.randomise_affine(SwinTransformer(depths, dims, heads, window_size=4), seed=7).cuda().eval()
-    for p in model.parameters():
-        p.requires_grad = False
-    model = model.to(torch.bfloat16)
-    for m in model.modules():
-        if isinstance(m, torch.nn.LayerNorm):
-            m.float()
+    model = bf16_frozen(R.randomise_affine(SwinTransformer(depths, dims, heads, window_size=4), seed=7).cuda())
     assert model.fused_refusal() is None and model.prepare_fused()
     _check_trunk(model, depths, heads, 4, _images(2, 128, seed=1), f"small trunk {dims[0]}..{dims[-1]} 128 px")
 

@@ -10,7 +10,8 @@ on them (``teacher.py:184-191``).  timm / torchvision are not available offline,
 package with the torchvision / timm parameter names (``conv1``, ``bn1``, ``layer1..4.N.conv1`` ...) so that a local
 state dict of either package loads.
 
-Two forwards of the same ResNet parameters, as for the ConvNeXt-V2 trunk:
+Two forwards of the same ResNet parameters, under the protocol and with the image helpers of
+``models/fused_trunk.py``:
 
 * plain PyTorch (``nn.Conv2d``, ``nn.BatchNorm2d``, ``nn.MaxPool2d``): the CPU path, the path of every dtype but bf16
   and of a model with gradients; on the device it runs in library kernels (MIOpen);
@@ -26,8 +27,9 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from ..losses._ops import get_ops, library_fallback
-from .convnext import CONVNEXT_PRESETS, _row_width
+from ..losses._ops import get_ops
+from .convnext import CONVNEXT_PRESETS
+from .fused_trunk import FusedTrunk, padded_image, patch_image, row_width
 from .swin import SWIN_PRESETS
 
 
@@ -53,13 +55,13 @@ class Bottleneck(nn.Module):
         return self.relu(y + idt)
 
 
-class ResNet(nn.Module):
+class ResNet(FusedTrunk, nn.Module):
     """ResNet-v1.5 trunk (stride on the 3x3 convolution), stages ``layer1..layer4`` as in torchvision / timm."""
+    _fallback_name = "resnet trunk"
 
     def __init__(self, depths=(3, 4, 6, 3), num_classes: int = 0, in_chans: int = 3):
         super().__init__()
         self.inplanes = 64
-        self._fused = None
         self.conv1 = nn.Conv2d(in_chans, 64, 7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
         self.relu = nn.ReLU(inplace=True)
@@ -98,7 +100,7 @@ class ResNet(nn.Module):
             return "the kernel provider has no ResNet trunk entries"
         if self.conv1.weight.shape[1] != 3:
             return f"the stem kernel takes 3 input channels (got {self.conv1.weight.shape[1]})"
-        ld = _row_width(64)
+        ld = row_width(64)
         if not (ops.conv7x7s2_relu_supported(ld) and ops.maxpool3x3s2_supported(64, ld, ld)):
             return f"stem rows of {ld} are not tiled by the stem / pool kernels"
         c_in = 64
@@ -107,7 +109,7 @@ class ResNet(nn.Module):
                 if not isinstance(blk, Bottleneck):
                     return f"{type(blk).__name__} blocks (bottleneck blocks only)"
                 p, c_out, s = blk.conv2.weight.shape[0], blk.conv3.weight.shape[0], blk.conv2.stride[0]
-                ld_in, ld_p, ld_o = _row_width(c_in), _row_width(p), _row_width(c_out)
+                ld_in, ld_p, ld_o = row_width(c_in), row_width(p), row_width(c_out)
                 if not (ops.gemm_supported(ld_p, ld_in) and ops.conv3x3_supported(p, ld_p, ld_p, s)
                         and ops.gemm_supported(ld_o, ld_p) and ops.gemm_supported(ld_o, ld_in)
                         and ld_o == c_out and ops.add_relu_supported(c_out, ld_o, ld_o)):
@@ -115,53 +117,35 @@ class ResNet(nn.Module):
                 c_in = c_out
         return None
 
-    @torch.no_grad()
-    def prepare_fused(self) -> bool:
-        """Build the weight images of the fused path once (frozen teacher: no refresh).  BatchNorm is folded in fp32
-        from the stored parameters, s = gamma / sqrt(var + eps): w' = bf16(w s), b' = bf16(beta - mean s).  The 3 x 3
-        images are tap-major [C, 9 C], the 1 x 1 images [N_ld, K_ld] with zero rows (and zero bias) for padded output
-        channels and zero columns for padded input channels, the stem image [64, K_pad] in the kernel's patch order."""
-        self._fused = None
-        if self.fused_refusal() is not None or any(p.requires_grad for p in self.parameters()):
-            return False
+    def _build_fused(self):
+        """The weight images of ``prepare_fused``.  BatchNorm is folded in fp32 from the stored parameters, s = gamma /
+        sqrt(var + eps): w' = bf16(w s), b' = bf16(beta - mean s), one rounding.  The 3 x 3 images are tap-major
+        [C, 9 C], the 1 x 1 images zero-padded [N_ld, K_ld], the stem image [64, K_pad] in the kernel's patch order."""
         ops = get_ops()
-        bf = torch.bfloat16
 
-        def fold(conv, bn):
+        def folded(conv, bn, n_ld, k_ld):
             s = bn.weight.float() / torch.sqrt(bn.running_var.float() + bn.eps)
-            return conv.weight.float() * s.view(-1, 1, 1, 1), bn.bias.float() - bn.running_mean.float() * s
-
-        def image(w2d, bias, n_ld, k_ld):
-            n, k = w2d.shape
-            w = torch.zeros(n_ld, k_ld, dtype=bf, device=w2d.device)
-            w[:n, :k] = w2d.to(bf)
-            b = torch.zeros(n_ld, dtype=bf, device=w2d.device)
-            b[:n] = bias.to(bf)
-            return w, b
+            w = patch_image(conv.weight.float() * s.view(-1, 1, 1, 1))
+            return padded_image(w, bn.bias.float() - bn.running_mean.float() * s, n_ld, k_ld)
 
         def pointwise(conv, bn, ld_in):
-            w, b = fold(conv, bn)
-            return image(w.flatten(1), b, _row_width(w.shape[0]), ld_in)
+            return folded(conv, bn, row_width(conv.weight.shape[0]), ld_in)
 
-        w, b = fold(self.conv1, self.bn1)
-        fused = {"ld0": _row_width(64), "blocks": [],
-                 "stem": image(w.permute(0, 2, 3, 1).reshape(64, 147), b, 64, ops.STEM_K_PAD)}
+        fused = {"ld0": row_width(64), "blocks": [], "stem": folded(self.conv1, self.bn1, 64, ops.STEM_K_PAD)}
         c_in = 64
         for stage in self._stages():
             for blk in stage:
                 p = blk.conv2.weight.shape[0]
-                ld_in = _row_width(c_in)
-                w, b = fold(blk.conv2, blk.bn2)
+                ld_in = row_width(c_in)
                 rec = {"c1": pointwise(blk.conv1, blk.bn1, ld_in), "planes": p, "stride": blk.conv2.stride[0],
-                       "c2": image(w.permute(0, 2, 3, 1).reshape(p, 9 * p), b, p, 9 * p),
-                       "c3": pointwise(blk.conv3, blk.bn3, _row_width(p)), "down": None}
+                       "c2": folded(blk.conv2, blk.bn2, p, 9 * p),
+                       "c3": pointwise(blk.conv3, blk.bn3, row_width(p)), "down": None}
                 if blk.downsample is not None:
                     rec["down"] = pointwise(blk.downsample[0], blk.downsample[1], ld_in)
                 fused["blocks"].append(rec)
                 c_in = blk.conv3.weight.shape[0]
         fused["c_last"] = c_in
-        self._fused = fused
-        return True
+        return fused
 
     def _forward_fused(self, x):
         """x [B, 3, H, W] bf16 (any strides) -> [B, 2048, H/32, W/32] bf16, a channels-last view of the last rows"""
@@ -190,18 +174,12 @@ class ResNet(nn.Module):
         return (self._fused is not None and not torch.is_grad_enabled() and x.dtype == torch.bfloat16 and x.dim() == 4
                 and x.shape[1] == 3 and self.conv1.weight.dtype == torch.bfloat16)
 
-    def forward_features(self, x):
-        if x.dtype == torch.bfloat16 and not torch.is_grad_enabled() and get_ops().handles(x):
-            if self._takes_fused(x):
-                return self._forward_fused(x)
-            library_fallback("resnet trunk", self.fused_refusal() or
-                             f"shape={tuple(x.shape)} weights={self.conv1.weight.dtype} prepared={self._fused is not None}")
-        return self._forward_plain(x)
+    def _reports(self, x) -> bool:
+        # only a bf16 no-grad forward is reported: every other dtype and a model with gradients take the plain path
+        return x.dtype == torch.bfloat16 and not torch.is_grad_enabled() and get_ops().handles(x)
 
-    def _apply(self, fn, *args, **kwargs):
-        # .to() / .cuda() / .float() move or recast the parameters: the weight images no longer belong to them
-        self._fused = None
-        return super()._apply(fn, *args, **kwargs)
+    def _fallback_detail(self, x) -> str:
+        return f"shape={tuple(x.shape)} weights={self.conv1.weight.dtype} prepared={self._fused is not None}"
 
     def forward(self, x):
         return self.fc(self.forward_features(x).mean(dim=(2, 3)))

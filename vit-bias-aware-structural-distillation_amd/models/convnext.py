@@ -11,7 +11,7 @@ names (stated assumption; the architecture itself is pinned b
   ``mlp.fc1`` (C -> 4C), exact GELU, ``mlp.grn.weight / .bias`` [4C], ``mlp.fc2`` (4C -> C), residual add
 * ``forward_features`` = stem + the four stages -> ``[B, C_last, H/32, W/32]``
 
-Two forwards of the same parameters:
+Two forwards of the same parameters, under the protocol and with the image helpers of ``models/fused_trunk.py``:
 
 * plain PyTorch (``nn.Conv2d``, ``F.layer_norm``, ``nn.Linear``): the CPU path, and on the device the path of any
   shape / dtype the kernels refuse -- reported through ``library_fallback`` like every other layer;
@@ -26,7 +26,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..losses._ops import get_ops, library_fallback
+from ..losses._ops import get_ops
+from .fused_trunk import FusedTrunk, centre_tap_identity, norm_params, padded_image, patch_image, row_width
 
 
 class LayerNorm2d(nn.LayerNorm):
@@ -97,13 +98,9 @@ class ConvNeXtStage(nn.Module):
         return self.blocks(self.downsample(x))
 
 
-def _row_width(c: int) -> int:
-    """Row stride of a C-channel activation: C itself when the GEMM takes it as N and as K, else the next multiple of 128."""
-    ops = get_ops()
-    return c if ops.gemm_supported(c, c) else (c + 127) // 128 * 128
+class ConvNeXtV2(FusedTrunk, nn.Module):
+    _fallback_name = "convnext trunk"
 
-
-class ConvNeXtV2(nn.Module):
     def __init__(self, depths=(3, 3, 9, 3), dims=(96, 192, 384, 768), num_classes: int = 0, in_chans: int = 3):
         super().__init__()
         self.depths, self.dims = tuple(depths), tuple(dims)
@@ -112,7 +109,6 @@ class ConvNeXtV2(nn.Module):
                                       for i in range(len(dims))])
         self.num_features = self.embed_dim = dims[-1]
         self.head = nn.Linear(dims[-1], num_classes) if num_classes > 0 else nn.Identity()
-        self._fused = None
         for m in self.modules():
             if isinstance(m, (nn.Conv2d, nn.Linear)):
                 nn.init.trunc_normal_(m.weight, std=0.02)
@@ -130,78 +126,43 @@ class ConvNeXtV2(nn.Module):
         """Why the kernels do not take this architecture (None: they do)."""
         ops = get_ops()
         for c in self.dims:
-            ld = _row_width(c)
+            ld = row_width(c)
             if not (ops.dwconv7_ln_supported(c, ld, ld) and ops.grn_supported(4 * c) and ops.gemm_supported(4 * c, ld)
                     and ops.gemm_supported(ld, 4 * c) and ops.layernorm_supported(c)):
                 return f"width {c} (rows of {ld}, hidden {4 * c}) is not tiled by the GEMM / trunk kernels"
         return None
 
-    @torch.no_grad()
-    def prepare_fused(self) -> bool:
-        """Build the weight images of the fused path once (frozen teacher: no refresh): tap-major depthwise weights,
-        zero-padded GEMM images in the patch order of ``basd_patchify_bf16``, fp32 norm / GRN parameters."""
-        self._fused = None
-        if self.fused_refusal() is not None or any(p.requires_grad for p in self.parameters()):
-            return False
+    def _build_fused(self):
+        """The weight images of ``prepare_fused``: tap-major depthwise weights, zero-padded GEMM images in the patch
+        order of ``basd_patchify_bf16`` (K rounded up to a multiple of 64), fp32 norm / GRN parameters."""
         bf, f32 = torch.bfloat16, torch.float32
-        lds = [_row_width(c) for c in self.dims]
+        lds = [row_width(c) for c in self.dims]
 
         def conv_image(conv, c_in_ld, n_ld):
-            # [C_out, C_in, p, p] -> [n_ld, k_pad] with column (i p + j) c_in_ld + c: zero columns for the padded input
-            # channels, zero rows (and zero bias) for the padded output channels
-            c_out, c_in, p, _ = conv.weight.shape
-            k = p * p * c_in_ld
-            k_pad = (k + 63) // 64 * 64
-            img = torch.zeros(n_ld, p * p, c_in_ld, dtype=bf, device=conv.weight.device)
-            img[:c_out, :, :c_in] = conv.weight.permute(0, 2, 3, 1).reshape(c_out, p * p, c_in).to(bf)
-            w = torch.zeros(n_ld, k_pad, dtype=bf, device=conv.weight.device)
-            w[:, :k] = img.reshape(n_ld, k)
-            b = torch.zeros(n_ld, dtype=bf, device=conv.weight.device)
-            b[:c_out] = conv.bias.to(bf)
-            return w, b, k_pad
-
-        def ln_as_conv(c, dev):
-            # LayerNorm over C columns of rows of stride ld > C through basd_dwconv7_ln_bf16 at H = W = 1: the one-hot
-            # centre tap and a zero bias make the convolution an exact copy
-            w49 = torch.zeros(49, c, dtype=bf, device=dev)
-            w49[24] = 1.0
-            return w49, torch.zeros(c, dtype=f32, device=dev)
+            w2d = patch_image(conv.weight, c_in_ld)
+            k_pad = (w2d.shape[1] + 63) // 64 * 64
+            return padded_image(w2d, conv.bias, n_ld, k_pad) + (k_pad,)
 
         dev = self.stem[0].weight.device
         fused = {"lds": lds, "stages": []}
-        in_ch = self.stem[0].weight.shape[1]
-        fused["stem"] = conv_image(self.stem[0], in_ch, lds[0])
-        fused["stem_norm"] = (self.stem[1].weight.to(f32), self.stem[1].bias.to(f32), self.stem[1].eps)
-        fused["ident"] = {c: ln_as_conv(c, dev) for c, ld in zip(self.dims, lds) if ld != c}
+        fused["stem"] = conv_image(self.stem[0], self.stem[0].weight.shape[1], lds[0])
+        fused["stem_norm"] = norm_params(self.stem[1])
+        fused["ident"] = {c: centre_tap_identity(c, dev) for c, ld in zip(self.dims, lds) if ld != c}
         for i, stage in enumerate(self.stages):
             c, ld = self.dims[i], lds[i]
             rec = {"down": None, "blocks": []}
             if i > 0:
-                norm, conv = stage.downsample[0], stage.downsample[1]
-                rec["down"] = (norm.weight.to(f32), norm.bias.to(f32), norm.eps) + conv_image(conv, lds[i - 1], ld)
+                rec["down"] = norm_params(stage.downsample[0]) + conv_image(stage.downsample[1], lds[i - 1], ld)
             for blk in stage.blocks:
-                w1 = torch.zeros(4 * c, ld, dtype=bf, device=dev)
-                w1[:, :c] = blk.mlp.fc1.weight.to(bf)
-                w2 = torch.zeros(ld, 4 * c, dtype=bf, device=dev)
-                w2[:c] = blk.mlp.fc2.weight.to(bf)
-                b2 = torch.zeros(ld, dtype=bf, device=dev)
-                b2[:c] = blk.mlp.fc2.bias.to(bf)
+                gamma, beta, eps = norm_params(blk.norm)
+                w1, b1 = padded_image(blk.mlp.fc1.weight, blk.mlp.fc1.bias, 4 * c, ld)
+                w2, b2 = padded_image(blk.mlp.fc2.weight, blk.mlp.fc2.bias, ld, 4 * c)
                 rec["blocks"].append({
                     "w49": blk.conv_dw.weight.reshape(c, 49).t().contiguous().to(bf), "dw_bias": blk.conv_dw.bias.to(f32),
-                    "gamma": blk.norm.weight.to(f32), "beta": blk.norm.bias.to(f32), "eps": blk.norm.eps,
-                    "w1": w1, "b1": blk.mlp.fc1.bias.to(bf).contiguous(), "grn_w": blk.mlp.grn.weight.to(f32),
+                    "gamma": gamma, "beta": beta, "eps": eps, "w1": w1, "b1": b1, "grn_w": blk.mlp.grn.weight.to(f32),
                     "grn_b": blk.mlp.grn.bias.to(f32), "grn_eps": blk.mlp.grn.eps, "w2": w2, "b2": b2})
             fused["stages"].append(rec)
-        self._fused = fused
-        return True
-
-    def _norm_rows(self, ops, x, c, gamma, beta, eps):
-        """LayerNorm over the first c columns of x [rows, ld] -> [rows, ld] (pad columns zero)"""
-        rows, ld = x.shape
-        if ld == c:
-            return ops.layernorm_fwd(x, gamma, beta, eps)[0]
-        w49, zero = self._fused["ident"][c]
-        return ops.dwconv7_ln(x.view(rows, 1, 1, ld), w49, zero, gamma, beta, eps).view(rows, ld)
+        return fused
 
     def _forward_fused(self, x):
         """x [B, 3, H, W] bf16 (any strides) -> [B, C_last, H/32, W/32] bf16, a channels-last view of the last rows"""
@@ -231,22 +192,8 @@ class ConvNeXtV2(nn.Module):
         return (self._fused is not None and not torch.is_grad_enabled() and x.dtype == torch.bfloat16 and x.dim() == 4
                 and x.shape[2] % 32 == 0 and x.shape[3] % 32 == 0 and self.stem[0].weight.dtype == torch.bfloat16)
 
-    def forward_features(self, x):
-        if get_ops().handles(x):
-            if self._takes_fused(x):
-                return self._forward_fused(x)
-            library_fallback("convnext trunk", self.fused_refusal() or
-                             f"dtype={x.dtype} size={tuple(x.shape[2:])} grad={torch.is_grad_enabled()} "
-                             f"prepared={self._fused is not None}")
-        return self._forward_plain(x)
-
     def forward(self, x):
         return self.head(self.forward_features(x).mean(dim=(2, 3)))
-
-    def _apply(self, fn, *args, **kwargs):
-        # .to() / .cuda() / .float() move or recast the parameters: the weight images no longer belong to them
-        self._fused = None
-        return super()._apply(fn, *args, **kwargs)
 
 
 CONVNEXT_PRESETS = {

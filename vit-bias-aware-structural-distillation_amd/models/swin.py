@@ -19,7 +19,7 @@ parameter names of timm >= 0.9 (stated assumption; the archit
   is remapped to ``layers.{i+1}.downsample``.
 * final ``norm`` LayerNorm(C_last) inside ``forward_features`` -> ``[B, H/32, W/32, C_last]`` (NHWC); LayerNorm eps 1e-5
 
-Two forwards of the same parameters, as in ``models/convnext.py``:
+Two forwards of the same parameters, under the protocol and with the image helpers of ``models/fused_trunk.py``:
 
 * plain PyTorch: the CPU path, and on the device the path of whatever the kernels refuse -- reported through
   ``library_fallback``.  Its windows are a gather by the token index of every (window, slot); the mask is built from the
@@ -36,8 +36,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..losses._ops import get_ops, library_fallback
-from .convnext import _row_width
+from ..losses._ops import get_ops
+from .fused_trunk import FusedTrunk, centre_tap_identity, norm_params, padded_image, patch_image, row_width
 
 HEAD_DIM = 32
 MASK_VALUE = -100.0
@@ -179,7 +179,9 @@ class _PatchEmbed(nn.Module):
         return _ln(self.norm, self.proj(x).permute(0, 2, 3, 1))                 # NHWC
 
 
-class SwinTransformer(nn.Module):
+class SwinTransformer(FusedTrunk, nn.Module):
+    _fallback_name = "swin trunk"
+
     def __init__(self, depths=(2, 2, 6, 2), dims=(96, 192, 384, 768), heads=(3, 6, 12, 24), window_size: int = 7,
                  num_classes: int = 0, in_chans: int = 3):
         super().__init__()
@@ -190,7 +192,6 @@ class SwinTransformer(nn.Module):
         self.norm = nn.LayerNorm(dims[-1], eps=1e-5)
         self.num_features = self.embed_dim = dims[-1]
         self.head = nn.Linear(dims[-1], num_classes) if num_classes > 0 else nn.Identity()
-        self._fused = None
         for m in self.modules():
             if isinstance(m, nn.Linear):
                 nn.init.trunc_normal_(m.weight, std=0.02)
@@ -232,7 +233,7 @@ class SwinTransformer(nn.Module):
             return f"the patch embedding takes 3 input channels (got {self.patch_embed.proj.weight.shape[1]})"
         ws = self.window_size
         for i, (c, nh) in enumerate(zip(self.dims, self.heads)):
-            ld = _row_width(c)
+            ld = row_width(c)
             nq = self._qkv_width(c, ld)
             if c != HEAD_DIM * nh:
                 return f"stage {i}: width {c} with {nh} heads is not head dim {HEAD_DIM}"
@@ -243,76 +244,43 @@ class SwinTransformer(nn.Module):
                 return f"stage {i}: width {c} (rows of {ld}, hidden {4 * c}) is not tiled by the GEMM / LayerNorm kernels"
             if i > 0:
                 c_in = self.dims[i - 1]
-                if not (c == 2 * c_in and ops.patch_merge_ln_supported(c_in, _row_width(c_in))
+                if not (c == 2 * c_in and ops.patch_merge_ln_supported(c_in, row_width(c_in))
                         and ops.gemm_supported(ld, 4 * c_in)):
                     return f"stage {i}: merging {c_in} -> {c} is not tiled by the patch-merge kernel / the GEMM"
-        if not ops.gemm_supported(_row_width(self.dims[0]), 64):
-            return f"the patch embedding to rows of {_row_width(self.dims[0])} is not tiled by the GEMM"
+        if not ops.gemm_supported(row_width(self.dims[0]), 64):
+            return f"the patch embedding to rows of {row_width(self.dims[0])} is not tiled by the GEMM"
         return None
 
-    @torch.no_grad()
-    def prepare_fused(self) -> bool:
-        """Build the weight images of the fused path once (frozen teacher: no refresh): zero-padded GEMM images (zero
-        rows and zero bias for padded output channels, zero columns for padded input channels), the patch embedding in
-        the patch order of ``basd_patchify_bf16``, fp32 norm parameters, and per block the relative-position bias
-        expanded from the table into the fp32 [heads, 64, 64] image of ``basd_window_attention_fwd_bf16``."""
-        self._fused = None
-        if self.fused_refusal() is not None or any(p.requires_grad for p in self.parameters()):
-            return False
+    def _build_fused(self):
+        """The weight images of ``prepare_fused``: zero-padded GEMM images, the patch embedding in the patch order of
+        ``basd_patchify_bf16`` (48 columns in rows of 64), fp32 norm parameters, and per block the relative-position
+        bias expanded from the table into the fp32 [heads, 64, 64] image of ``basd_window_attention_fwd_bf16``."""
         ops = get_ops()
-        bf, f32 = torch.bfloat16, torch.float32
-        dev = self.patch_embed.proj.weight.device
-        lds = [_row_width(c) for c in self.dims]
-
-        def image(weight, bias, n_ld, k_ld):
-            n, k = weight.shape
-            w = torch.zeros(n_ld, k_ld, dtype=bf, device=dev)
-            w[:n, :k] = weight.to(bf)
-            b = None
-            if bias is not None:
-                b = torch.zeros(n_ld, dtype=bf, device=dev)
-                b[:n] = bias.to(bf)
-            return w, b
-
-        def norm(m):
-            return m.weight.to(f32).contiguous(), m.bias.to(f32).contiguous(), m.eps
-
-        def ln_as_conv(c):
-            # LayerNorm over C columns of rows of stride ld > C through basd_dwconv7_ln_bf16 at H = W = 1: the one-hot
-            # centre tap and a zero bias make the convolution an exact copy (ConvNeXtV2._norm_rows)
-            w49 = torch.zeros(49, c, dtype=bf, device=dev)
-            w49[24] = 1.0
-            return w49, torch.zeros(c, dtype=f32, device=dev)
-
         proj = self.patch_embed.proj
-        fused = {"lds": lds, "stages": [], "ident": {c: ln_as_conv(c) for c, ld in zip(self.dims, lds) if ld != c},
-                 "embed": image(proj.weight.permute(0, 2, 3, 1).reshape(self.dims[0], 48), proj.bias, lds[0], 64),
-                 "embed_norm": norm(self.patch_embed.norm), "norm": norm(self.norm)}
+        lds = [row_width(c) for c in self.dims]
+
+        def linear(m, n_ld, k_ld):
+            return padded_image(m.weight, m.bias, n_ld, k_ld)
+
+        fused = {"lds": lds, "stages": [],
+                 "ident": {c: centre_tap_identity(c, proj.weight.device) for c, ld in zip(self.dims, lds) if ld != c},
+                 "embed": padded_image(patch_image(proj.weight), proj.bias, lds[0], 64),
+                 "embed_norm": norm_params(self.patch_embed.norm), "norm": norm_params(self.norm)}
         for i, stage in enumerate(self.layers):
             c, ld = self.dims[i], lds[i]
             rec = {"merge": None, "blocks": []}
             if i > 0:
                 down = stage.downsample
-                rec["merge"] = norm(down.norm) + (image(down.reduction.weight, None, ld, 4 * self.dims[i - 1])[0],)
+                rec["merge"] = norm_params(down.norm) + linear(down.reduction, ld, 4 * self.dims[i - 1])[:1]
             nq = self._qkv_width(c, ld)
             for blk in stage.blocks:
                 rec["blocks"].append({
-                    "norm1": norm(blk.norm1), "qkv": image(blk.attn.qkv.weight, blk.attn.qkv.bias, nq, ld),
+                    "norm1": norm_params(blk.norm1), "qkv": linear(blk.attn.qkv, nq, ld),
                     "bias": ops.window_bias_image(blk.attn.bias()), "scale": blk.attn.scale, "shift": blk.shift,
-                    "proj": image(blk.attn.proj.weight, blk.attn.proj.bias, ld, ld), "norm2": norm(blk.norm2),
-                    "fc1": image(blk.mlp.fc1.weight, blk.mlp.fc1.bias, 4 * c, ld),
-                    "fc2": image(blk.mlp.fc2.weight, blk.mlp.fc2.bias, ld, 4 * c)})
+                    "proj": linear(blk.attn.proj, ld, ld), "norm2": norm_params(blk.norm2),
+                    "fc1": linear(blk.mlp.fc1, 4 * c, ld), "fc2": linear(blk.mlp.fc2, ld, 4 * c)})
             fused["stages"].append(rec)
-        self._fused = fused
-        return True
-
-    def _norm_rows(self, ops, x, c, gamma, beta, eps):
-        """LayerNorm over the first c columns of x [rows, ld] -> [rows, ld] (pad columns zero)"""
-        rows, ld = x.shape
-        if ld == c:
-            return ops.layernorm_fwd(x, gamma, beta, eps)[0]
-        w49, zero = self._fused["ident"][c]
-        return ops.dwconv7_ln(x.view(rows, 1, 1, ld), w49, zero, gamma, beta, eps).view(rows, ld)
+        return fused
 
     def _forward_fused(self, x):
         """x [B, 3, H, W] bf16 (any strides) -> [B, H/32, W/32, C_last] bf16, a view of the last rows"""
@@ -362,22 +330,8 @@ class SwinTransformer(nn.Module):
                 and x.shape[1] == 3 and self.patch_embed.proj.weight.dtype == torch.bfloat16
                 and self._grid_ok(x.shape[2], x.shape[3]))
 
-    def forward_features(self, x):
-        if get_ops().handles(x):
-            if self._takes_fused(x):
-                return self._forward_fused(x)
-            library_fallback("swin trunk", self.fused_refusal() or
-                             f"dtype={x.dtype} size={tuple(x.shape[2:])} grad={torch.is_grad_enabled()} "
-                             f"prepared={self._fused is not None}")
-        return self._forward_plain(x)
-
     def forward(self, x):
         return self.head(self.forward_features(x).mean(dim=(1, 2)))
-
-    def _apply(self, fn, *args, **kwargs):
-        # .to() / .cuda() / .float() move or recast the parameters: the weight images no longer belong to them
-        self._fused = None
-        return super()._apply(fn, *args, **kwargs)
 
 
 SWIN_PRESETS = {
