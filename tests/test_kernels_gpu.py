@@ -35,6 +35,9 @@ def _colmajor(a: torch.Tensor, ld: int) -> torch.Tensor:
                                        # two matrices per CU (batch > 256)
                                        (192, 130, 3), (150, 150, 2), (176, 191, 2), (64, 180, 2), (120, 133, 300),
                                        (384, 192, 3), (300, 170, 2),
+                                       # the other instantiations of the block kernel: quad-block with 32-lane slots
+                                       # (257 .. 384 rows), with three and with two row chunks
+                                       (300, 64, 2), (176, 100, 2), (120, 64, 2),
                                        # fewer than 8 columns at batch >= 512: the double-buffered odd-even kernel, one
                                        # matrix per workgroup
                                        (40, 7, 513),

@@ -4,9 +4,10 @@
 // (src/losses/layer_selector.py:16,36,92,99; src/losses/relational.py:48).
 //
 // Layout: column c at W + c*ld, rows 0..m-1 significant, rows m..ld-1 zero.
-// Three kernels, chosen by shape alone in basd_jacobi_svd at the end of this file (DESIGN.md has the route table):
-// hex-block and quad-block ordering with scaled rotations for up to 196 columns, odd-even ordering of single
-// columns for everything else that is accepted.
+// Two kernels, chosen by shape alone in basd_jacobi_svd at the end of this file (DESIGN.md has the route table): the
+// block kernel with scaled rotations in its hex-block or quad-block ordering for up to 196 columns, odd-even ordering
+// of single columns for everything else that is accepted.
+#include <type_traits>
 #include "basd_common.h"
 
 namespace basd {
@@ -368,8 +369,8 @@ __attribute__((amdgpu_waves_per_eu((NMAT == 2 || MAXCH > 7) ? 3 : 4, (NMAT == 2 
 }
 
 // ---------------------------------------------------------------------------------------------
-// Quad-block ordering with scaled rotations (the default for 8 .. 196 columns where the hex-block kernel below does
-// not apply).  What its retired predecessor (block odd-even: 8-lane slots owning two blocks of TWO columns, DESIGN.md
+// Block orderings with scaled rotations: jacobi_block_kernel, further down, with BlockOrder<4> or BlockOrder<6>.
+// Quad-block ordering (the default for 8 .. 196 columns where the hex-block ordering below does not apply).  What its retired predecessor (block odd-even: 8-lane slots owning two blocks of TWO columns, DESIGN.md
 // section 5) still paid per rotation and wave: the rotation parameters (five
 // transcendentals, ~25 VALU instructions) are computed by all 8 lanes of a slot, i.e. 8 distinct
 // parameter sets per wave instruction stream; the plane rotation is four FMAs per row pair; and the
@@ -516,309 +517,77 @@ template <int SCTRL, int YMASK> __device__ __forceinline__ float meta_scatter(fl
   }
 }
 
-// LANES = lanes per slot: 16 (rows 4 sub + 64 ch) or 32 (rows 4 sub + 128 ch: columns of up to 384 rows at the same 96
-// column VGPRs, 768 threads -- the block pairs of the D_s = 384 eigensolver).  MAXCH = 4 at 16 lanes (193 .. 256 rows:
-// the 196 x 196 token-side Procrustes cores of the wide students) holds 128 column VGPRs: two waves per SIMD.
-template <int MAXCH, int LANES>
-__global__ __launch_bounds__(LANES == 32 ? 768 : (MAXCH > 3 ? 448 : 384))
-__attribute__((amdgpu_waves_per_eu((LANES == 16 && MAXCH > 3) ? 2 : 3, (LANES == 16 && MAXCH > 3) ? 2 : 3))) void jacobi_b4_kernel(
-    float* __restrict__ wg, int batch, int m, int n, int ld, int norm_rows, float tol, int max_sweeps, int sort,
-    float* __restrict__ sigma, int32_t* __restrict__ sweeps_out, int32_t* __restrict__ status,
-    const int32_t* __restrict__ active, int active_mode) {
-  // active_mode 0: no `active`; 1: active[mat] = number of leading non-zero columns (the tournament runs over those,
-  // the other columns are zero and stay zero); 2: the same and only the leading active[mat] ROWS are non-zero;
-  // 3: `active` is a mask (< 0: skip the matrix, otherwise solve it completely)
-  extern __shared__ __align__(16) float lds[];
-  const int mat = blockIdx.x;
-  int n_act = n;
-  if (active_mode != 0) {
-    const int av = active[mat];
-    if (av < 0) {                                  // masked problem (any mode): nothing is read or written
-      if (sweeps_out && threadIdx.x == 0) sweeps_out[mat] = 0;
-      return;
-    }
-    if (active_mode != 3) n_act = av < 2 ? 2 : (av > n ? n : av);
-  }
-  constexpr int CHR = 4 * LANES;                   // rows of one chunk (4 per lane)
-  constexpr int LDC = CHR * MAXCH;                 // one column in the mailbox
-  constexpr int LDB = 4 * LDC;                     // one block
-  const int tid = threadIdx.x;
-  const int k = tid / LANES, sub = tid % LANES, roff = sub * 4, q = sub & 3;
-  const bool bit0 = (sub & 1) != 0, bit1 = (sub & 2) != 0;
-  const int nb_all = (n + 3) >> 2;
-  const int S_all = (nb_all + 1) >> 1;             // slots the launch provides (threads / 16, rounded up to waves)
-  const int nb = (n_act + 3) >> 2;                 // blocks that hold active columns
-  const int nbe = nb + (nb & 1);                   // line length in blocks (a zero phantom block pads odd nb)
-  const int S = nbe >> 1;                          // slots that take part
-  float* mbox = lds;                               // [S_all + 1][LDB]
-  float* s_sig = mbox + (size_t)(S_all + 1) * LDB; // [8 S_all] by position
-  int* s_rank = reinterpret_cast<int*>(s_sig + 200);      // [8 S_all]
-  float* s_nrm = reinterpret_cast<float*>(s_rank + 200);  // [S_all + 1][4] squared norms travelling with the mailbox
-  float* s_scl = s_nrm + 104;                      // [S_all + 1][4] scales
-  int* s_flag = reinterpret_cast<int*>(s_scl + 104);      // [2] any rotation, [2] any LARGE rotation, [2] max norm
-
-  float* src = wg + (size_t)mat * n * ld;
-  int mr = (m + 3) & ~3;
-  if (active_mode == 2) { const int ma = (n_act + 3) & ~3; mr = ma < mr ? ma : mr; }
-  const bool live = k < S;
-  const bool last = k == S - 1;
-  float* const mybox = mbox + (size_t)k * LDB + roff;          // box k, this lane's rows
-  float* const mymeta = s_nrm + 4 * k + q;                      // box k, this lane's column: norm, +104 scale
-  v4f C[8][MAXCH];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const int idc = 8 * k + c;
-#pragma unroll
-    for (int ch = 0; ch < MAXCH; ++ch) {
-      const int r = roff + CHR * ch;
-      C[c][ch] = (live && idc < n_act && r < mr) ? *reinterpret_cast<const v4f*>(src + (size_t)idc * ld + r)
-                                                 : (v4f){0.f, 0.f, 0.f, 0.f};
-    }
-  }
-  // distributed bookkeeping: lane q of every quad owns column q of block P (C[q]) and of block Q (C[4 + q]).
-  // Column ids are NOT carried: blocks move as wholes on a data-independent schedule -- a sweep of the odd-even
-  // transposition line reverses the block order, so after s sweeps position p holds block (s odd ? nbe - 1 - p : p).
-  float nP = 0.f, nQ = 0.f, dP = 1.f, dQ = 1.f;
-  if (tid < 8) s_flag[tid] = 0;
-  __syncthreads();
-
-  const float inv_tol = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(1.0f / tol)));
-  bool rotated = false, bigrot = false;
-
-  auto round = [&](auto map, bool ok) {
-    using M = decltype(map);
-    float p[4];
-    dot4_cols<MAXCH>(C[M::X(0)], C[M::Y(0)], C[M::X(1)], C[M::Y(1)], C[M::X(2)], C[M::Y(2)], C[M::X(3)], C[M::Y(3)], p);
-    const float gt = reduce_scatter4<LANES>(p[0], p[1], p[2], p[3], bit0, bit1);
-    const float al = meta_gather<M::gx, M::xq_mask>(nP, nQ, q), be = meta_gather<M::gy, M::yq_mask>(nP, nQ, q);
-    const float dx = meta_gather<M::gx, M::xq_mask>(dP, dQ, q), dy = meta_gather<M::gy, M::yq_mask>(dP, dQ, q);
-    const float g = gt * dx * dy;                  // dot product of the true columns
-    const float gsc = g * inv_tol;
-    const float ab_ = al * be;
-    const bool rot = ok & (gsc * gsc > fmaxf(ab_, BASD_JACOBI_TINY));
-    {
-      // no branch around the rotation: a round in which all 16 rotations of the wave are below the threshold only
-      // occurs on padded / rank-deficient columns (the solve stops after the first sweep of small rotations), and a
-      // merge point after the in-place shears costs 48 register moves per round (the allocator does not coalesce the
-      // halves of the column registers across it); converged pairs run the shears with a = b = 0, an exact no-op
-      rotated |= rot;
-      const float gq = g * (1.0f / BASD_JACOBI_QUAD);
-      const bool big_cos = gq * gq > ab_;
-      const float z = (be - al) * __builtin_amdgcn_rcpf(2.f * g);
-      float t = copysignf(1.f, z) * __builtin_amdgcn_rcpf(fabsf(z) + __builtin_amdgcn_sqrtf(fmaf(z, z, 1.f)));
-      t = rot ? t : 0.f;
-      bigrot |= rot & (big_cos | (fabsf(t) > BASD_JACOBI_QUAD_TAN));
-      const float w = fmaf(t, t, 1.f);
-      float c = __builtin_amdgcn_rsqf(w);
-      c = c * fmaf(-0.5f * w, c * c, 1.5f);
-      const float sn = c * t;
-      const float u = sn * __builtin_amdgcn_rcpf(1.0f + c);
-      const float h = sn * u, hp = t * u;          // 1 - c and 1 / c - 1, no cancellation
-      const float aln = fmaf(-t, g, al), ben = fmaf(t, g, be);
-      const float a = t * (dy * __builtin_amdgcn_rcpf(dx));
-      const float b = (sn * c) * (dx * __builtin_amdgcn_rcpf(dy));
-      const float dxn = fmaf(-dx, h, dx), dyn = fmaf(dy, hp, dy);
-      nP = meta_scatter<M::sp, M::py_mask>(aln, ben, q);
-      nQ = meta_scatter<M::sq, M::qy_mask>(aln, ben, q);
-      dP = meta_scatter<M::sp, M::py_mask>(dxn, dyn, q);
-      dQ = meta_scatter<M::sq, M::qy_mask>(dxn, dyn, q);
-      v2f_rot ab[4];
-      ab[0] = (v2f_rot){dppf<qperm(0, 0, 0, 0)>(a), dppf<qperm(0, 0, 0, 0)>(b)};
-      ab[1] = (v2f_rot){dppf<qperm(1, 1, 1, 1)>(a), dppf<qperm(1, 1, 1, 1)>(b)};
-      ab[2] = (v2f_rot){dppf<qperm(2, 2, 2, 2)>(a), dppf<qperm(2, 2, 2, 2)>(b)};
-      ab[3] = (v2f_rot){dppf<qperm(3, 3, 3, 3)>(a), dppf<qperm(3, 3, 3, 3)>(b)};
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int ch = 0; ch < MAXCH; ++ch) shear_in_place(C[M::X(i)][ch], C[M::Y(i)][ch], ab[i]);
-      }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  };
-
-  // fold the scales into the columns (x <- d x~, d <- 1); `kill` zeroes a column instead
-  auto fold = [&](bool killP, bool killQ) {
-    const float fP = killP ? 0.f : dP, fQ = killQ ? 0.f : dQ;
-    float f[8];
-    f[0] = dppf<qperm(0, 0, 0, 0)>(fP); f[1] = dppf<qperm(1, 1, 1, 1)>(fP);
-    f[2] = dppf<qperm(2, 2, 2, 2)>(fP); f[3] = dppf<qperm(3, 3, 3, 3)>(fP);
-    f[4] = dppf<qperm(0, 0, 0, 0)>(fQ); f[5] = dppf<qperm(1, 1, 1, 1)>(fQ);
-    f[6] = dppf<qperm(2, 2, 2, 2)>(fQ); f[7] = dppf<qperm(3, 3, 3, 3)>(fQ);
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-#pragma unroll
-      for (int ch = 0; ch < MAXCH; ++ch) C[c][ch] *= f[c];
-    }
-    dP = 1.f; dQ = 1.f;
-  };
-  auto exact_norms = [&](int rows) {
-    float p[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      float a = 0.f;
-#pragma unroll
-      for (int ch = 0; ch < MAXCH; ++ch) {
-        const int r = roff + CHR * ch;
-        const v4f x = C[c][ch];
-        const float mx = (r + 0 < rows) ? 1.f : 0.f, my = (r + 1 < rows) ? 1.f : 0.f;
-        const float mz = (r + 2 < rows) ? 1.f : 0.f, mw = (r + 3 < rows) ? 1.f : 0.f;
-        a = fmaf(mx * x.x, x.x, fmaf(my * x.y, x.y, fmaf(mz * x.z, x.z, fmaf(mw * x.w, x.w, a))));
-      }
-      p[c] = a;
-    }
-    nP = reduce_scatter4<LANES>(p[0], p[1], p[2], p[3], bit0, bit1);
-    nQ = reduce_scatter4<LANES>(p[4], p[5], p[6], p[7], bit0, bit1);
-  };
-
-  int used_sweeps = 0;
-  bool converged = false;
-  int step = 0;                                    // even = blocks (2k, 2k+1); nbe is even, sweeps start and end there
-#pragma unroll 1
-  for (int sweep = 0; sweep < max_sweeps; ++sweep) {
-    rotated = false;
-    bigrot = false;
-    fold(false, false);
-    exact_norms(1 << 30);
-    if (live && sub < 4) atomicMax(&s_flag[4 + (sweep & 1)], __float_as_int(fmaxf(nP, nQ)));
-    lds_barrier();
-    {
-      const float debris = __int_as_float(s_flag[4 + (sweep & 1)]) * BASD_JACOBI_DEBRIS;
-      const bool zP = nP < debris, zQ = nQ < debris;       // debris columns become exact zero columns
-      if (__builtin_amdgcn_ballot_w64(zP || zQ) != 0) {
-        fold(zP, zQ);
-        if (zP) nP = 0.f;
-        if (zQ) nQ = 0.f;
-      }
-    }
-    // the six pairs inside each block, once per sweep: three rounds of two pairs per block
-    round(RoundMap<0, 1, 2, 3, 4, 5, 6, 7>{}, live);
-    round(RoundMap<0, 2, 1, 3, 4, 6, 5, 7>{}, live);
-    round(RoundMap<0, 3, 1, 2, 4, 7, 5, 6>{}, live);
-#pragma unroll 1
-    for (int t = 0; t < nbe; ++t, ++step) {
-      const bool even_view = (step & 1) == 0;
-      const bool pair_ok = live & (even_view | !last);
-      round(RoundMap<0, 4, 1, 5, 2, 6, 3, 7>{}, pair_ok);
-      round(RoundMap<0, 5, 1, 6, 2, 7, 3, 4>{}, pair_ok);
-      round(RoundMap<0, 6, 1, 7, 2, 4, 3, 5>{}, pair_ok);
-      round(RoundMap<0, 7, 1, 4, 2, 5, 3, 6>{}, pair_ok);
-      // ---- hand one block over (positions swap after a meeting: the pair is then stored as lo = Q, hi = P).
-      // ONE base address per lane for the boxes and one for their bookkeeping entries; everything else is an
-      // immediate offset (box k at 0, box k + 1 at LDB; norms / scales 104 entries apart)
-      if (even_view) {
-        // Q (block position 2k) goes to slot k-1 through box k (slot 0's stays parked there); the last slot has no
-        // right neighbour: it parks its P in box S and takes it back as Q (its lone block of the odd view)
-        if (live) {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-#pragma unroll
-            for (int ch = 0; ch < MAXCH; ++ch) *reinterpret_cast<v4f*>(mybox + c * LDC + CHR * ch) = C[4 + c][ch];
-          }
-          if (sub < 4) { mymeta[0] = nQ; mymeta[104] = dQ; }
-          if (last) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-#pragma unroll
-              for (int ch = 0; ch < MAXCH; ++ch) *reinterpret_cast<v4f*>(mybox + LDB + c * LDC + CHR * ch) = C[c][ch];
-            }
-            if (sub < 4) { mymeta[4] = nP; mymeta[104 + 4] = dP; }
-          }
-        }
-        lds_barrier();
-        if (live) {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-#pragma unroll
-            for (int ch = 0; ch < MAXCH; ++ch) C[4 + c][ch] = *reinterpret_cast<const v4f*>(mybox + LDB + c * LDC + CHR * ch);
-          }
-          nQ = mymeta[4]; dQ = mymeta[104 + 4];
-        }
-      } else {
-        // P (position 2k+2 after the swap) goes to slot k+1 through box k+1; slot 0 takes the parked block back
-        if (live && !last) {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-#pragma unroll
-            for (int ch = 0; ch < MAXCH; ++ch) *reinterpret_cast<v4f*>(mybox + LDB + c * LDC + CHR * ch) = C[c][ch];
-          }
-          if (sub < 4) { mymeta[4] = nP; mymeta[104 + 4] = dP; }
-        }
-        lds_barrier();
-        if (live) {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-#pragma unroll
-            for (int ch = 0; ch < MAXCH; ++ch) C[c][ch] = *reinterpret_cast<const v4f*>(mybox + c * LDC + CHR * ch);
-          }
-          nP = mymeta[0]; dP = mymeta[104];
-        }
-      }
-      // no second barrier: the next write to a box comes from the slot that has just read it (see the header)
-    }
-    used_sweeps = sweep + 1;
-    if (rotated) s_flag[sweep & 1] = 1;
-    if (bigrot) s_flag[2 + (sweep & 1)] = 1;
-    lds_barrier();
-    const int any = s_flag[sweep & 1], anybig = s_flag[2 + (sweep & 1)];
-    if (tid == 0) { s_flag[(sweep + 1) & 1] = 0; s_flag[2 + ((sweep + 1) & 1)] = 0; s_flag[4 + ((sweep + 1) & 1)] = 0; }
-    lds_barrier();
-    if (!any || !anybig) { converged = true; break; }
-  }
-
-  // ---- singular values = norms of the true columns over the first norm_rows rows
-  fold(false, false);
-  exact_norms(norm_rows);
-  lds_barrier();                                   // every wave is out of the sweep loop (mailbox reads done)
-  // The thread-derived indices are re-derived here from an opaque copy of the thread id: kept live across the sweep
-  // loop they cost registers the rotation rounds need (the allocator spills them into the inner loop otherwise).
-  int tid2 = threadIdx.x;
-  asm volatile("" : "+v"(tid2));
-  const int k2 = tid2 / LANES, sub2 = tid2 % LANES, q2 = sub2 & 3, roff2 = sub2 * 4;
-  const bool live2 = k2 < S;
-  // column ids by position: live slots hold block (sweeps odd ? nbe - 1 - p : p) at block position p; slots beyond
-  // the tournament never moved.  Ranking levels: active columns >= 0, inactive real columns -1, phantoms (id >= n) -2.
-  const bool odd = (used_sweeps & 1) != 0;
-  const int bP = live2 ? (odd ? nbe - 1 - 2 * k2 : 2 * k2) : 2 * k2;
-  const int bQ = live2 ? (odd ? nbe - 2 - 2 * k2 : 2 * k2 + 1) : 2 * k2 + 1;
-  if (k2 < S_all && sub2 < 4) {
-    const int idP = 4 * bP + q2, idQ = 4 * bQ + q2;
-    s_sig[8 * k2 + q2] = idP >= n ? -2.f : ((live2 && idP < n_act) ? sqrtf(nP) : -1.f);
-    s_sig[8 * k2 + 4 + q2] = idQ >= n ? -2.f : ((live2 && idQ < n_act) ? sqrtf(nQ) : -1.f);
-  }
-  lds_barrier();
-  const int n_tot = 8 * S_all;                     // >= n
-  for (int p = tid2; p < n_tot; p += blockDim.x) {
-    int rank = p;
-    if (sort) {
-      const float mine = s_sig[p];
-      rank = 0;
-      for (int c = 0; c < n_tot; ++c) {
-        const float o = s_sig[c];
-        rank += (o > mine) || (o == mine && c < p);
-      }
-    }
-    s_rank[p] = rank;
-  }
-  lds_barrier();
-  if (k2 < S_all) {
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const int idc = 4 * (c < 4 ? bP : bQ) + (c & 3);
-      const int d = sort ? s_rank[8 * k2 + c] : idc;
-      const float sg = s_sig[8 * k2 + c];
-      if (idc < n && d < n) {
-#pragma unroll
-        for (int ch = 0; ch < MAXCH; ++ch) {
-          const int r = roff2 + CHR * ch;
-          if (r < ld) *reinterpret_cast<v4f*>(src + (size_t)d * ld + r) = (live2 && r < mr) ? C[c][ch] : (v4f){0.f, 0.f, 0.f, 0.f};
-        }
-        if (sub2 == 0) sigma[(size_t)mat * n + d] = sg < 0.f ? 0.f : sg;
-      }
-    }
-  }
-  if (sweeps_out && tid2 == 0) sweeps_out[mat] = converged ? used_sweeps : -used_sweeps;
-  report_status(status, converged, s_sig, n_tot, tid2, blockDim.x, 6, mat);
+// ceil(x / D) for x >= 0: a shift where D is a power of two (the signed division costs three instructions more)
+template <int D> __host__ __device__ constexpr int ceil_div(int x) {
+  return (D & (D - 1)) == 0 ? (x + D - 1) >> __builtin_ctz(D) : (x + D - 1) / D;
 }
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a template argument
+template <int N, int I = 0, class F> __device__ __forceinline__ void static_for(F&& f) {
+  if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for<N, I + 1>(f); }
+}
+
+// What jacobi_block_kernel (below) needs to know about an ordering with blocks of BC columns: how a round's BC partial
+// dot products are formed and reduced, how (norm, scale) entries and rotation parameters travel between lanes, which
+// lanes hold them, and the round schedule.  Everything here is resolved at compile time.
+template <int BC> struct BlockOrder;
+
+// Quad-block: lane q of every quad computes rotation q and owns column q of either block; entries move with quad
+// permutes (DPP), so every quad of the slot carries a full replica of the bookkeeping.
+template <> struct BlockOrder<4> {
+  struct Lane {
+    int q;                                         // lane within its quad
+    bool bit0, bit1;
+    static constexpr bool rlane = true;            // every lane computes a rotation
+  };
+  __device__ __forceinline__ static Lane lane(int /*tid*/, int sub) { return {sub & 3, (sub & 1) != 0, (sub & 2) != 0}; }
+  // the lanes that speak for the slot's column entries (largest norm of the sweep): one replica is enough
+  __device__ __forceinline__ static bool owner(const Lane&, int sub) { return sub < 4; }
+  __device__ __forceinline__ static int meta_col(const Lane& L) { return L.q; }   // mailbox entry this lane reads
+  // LANES = 16: rows 4 sub + 64 ch; 32: rows 4 sub + 128 ch (columns of up to 384 rows at the same 96 column VGPRs,
+  // 768 threads -- the block pairs of the D_s = 384 eigensolver).  MAXCH = 4 at 16 lanes (193 .. 256 rows: the
+  // 196 x 196 token-side Procrustes cores of the wide students) holds 128 column VGPRs: two waves per SIMD.
+  static constexpr int max_threads(int maxch, int lanes) { return lanes == 32 ? 768 : (maxch > 3 ? 448 : 384); }
+  static constexpr int status_kind = 6;           // the kernel variant in the health word (report_status)
+  // quad permutes have no latency to hide: a round fetches the entries of its columns where it uses them (after the
+  // dot products) and hands the new ones back before it broadcasts the rotation parameters
+  static constexpr bool entries_first = false;
+
+  template <class M, int MAXCH> __device__ __forceinline__ static void dots(const v4f (&C)[8][MAXCH], float (&p)[4]) {
+    dot4_cols<MAXCH>(C[M::X(0)], C[M::Y(0)], C[M::X(1)], C[M::Y(1)], C[M::X(2)], C[M::Y(2)], C[M::X(3)], C[M::Y(3)], p);
+  }
+  template <int LANES> __device__ __forceinline__ static float reduce_scatter(const float (&p)[4], const Lane& L) {
+    return reduce_scatter4<LANES>(p[0], p[1], p[2], p[3], L.bit0, L.bit1);
+  }
+  // entry (held as mp for block P, mq for block Q) of the column this lane's rotation takes as X / as Y
+  template <class M> __device__ __forceinline__ static float gather_x(float mp, float mq, const Lane& L) {
+    return meta_gather<M::gx, M::xq_mask>(mp, mq, L.q);
+  }
+  template <class M> __device__ __forceinline__ static float gather_y(float mp, float mq, const Lane& L) {
+    return meta_gather<M::gy, M::yq_mask>(mp, mq, L.q);
+  }
+  // new entry of the column of block P / Q this lane owns, from the rotation that held it (as its X: xn, as its Y: yn)
+  template <class M> __device__ __forceinline__ static float scatter_p(float xn, float yn, const Lane& L) {
+    return meta_scatter<M::sp, M::py_mask>(xn, yn, L.q);
+  }
+  template <class M> __device__ __forceinline__ static float scatter_q(float xn, float yn, const Lane& L) {
+    return meta_scatter<M::sq, M::qy_mask>(xn, yn, L.q);
+  }
+  // v of the lane that computes rotation I / owns column I
+  template <int I> __device__ __forceinline__ static float bcast(float v) { return dppf<qperm(I, I, I, I)>(v); }
+  // the six pairs inside each block, once per sweep: three rounds of two pairs per block
+  template <class F> __device__ __forceinline__ static void inner_rounds(F&& round, bool ok) {
+    round(RoundMap<0, 1, 2, 3, 4, 5, 6, 7>{}, ok);
+    round(RoundMap<0, 2, 1, 3, 4, 6, 5, 7>{}, ok);
+    round(RoundMap<0, 3, 1, 2, 4, 7, 5, 6>{}, ok);
+  }
+  // a meeting of blocks P and Q: 16 cross rotations in four rounds
+  template <class F> __device__ __forceinline__ static void cross_rounds(F&& round, bool ok) {
+    round(RoundMap<0, 4, 1, 5, 2, 6, 3, 7>{}, ok);
+    round(RoundMap<0, 5, 1, 6, 2, 7, 3, 4>{}, ok);
+    round(RoundMap<0, 6, 1, 7, 2, 4, 3, 5>{}, ok);
+    round(RoundMap<0, 7, 1, 4, 2, 5, 3, 6>{}, ok);
+  }
+};
 
 // ---------------------------------------------------------------------------------------------
 // Hex-block ordering: blocks of SIX columns, 16 slots of 16 lanes for 192 columns -- FOUR
@@ -830,7 +599,7 @@ __attribute__((amdgpu_waves_per_eu((LANES == 16 && MAXCH > 3) ? 2 : 3, (LANES ==
 // the per-column bookkeeping no longer moves with quad permutes: partner entries travel by ds_bpermute, rotation
 // parameters are broadcast with ds_swizzle (lane i of every group of 8) -- 16 LDS-crossbar operations per round,
 // no LDS memory.  Everything else (scaled rotations as two shears, scales folded once per sweep, one barrier per
-// hand-over, analytic column ids) is the quad-block kernel's.
+// hand-over, analytic column ids) is shared with the quad-block ordering: jacobi_block_kernel below.
 __device__ __forceinline__ float bperm(int idx4, float v) {
   return __int_as_float(__builtin_amdgcn_ds_bpermute(idx4, __float_as_int(v)));
 }
@@ -944,59 +713,131 @@ __device__ __forceinline__ float meta_move6(float mp, float mq, int q8, int idx4
   }
 }
 
-// OCC = waves per SIMD the register allocation aims at: 1 (a batch that leaves every CU at most one matrix at a time:
-// no spills, the latency of the parameter stream is all that counts) or 2 (two matrices per CU hide each other's
-// parameter stream)
-// LANES = 32: columns of up to 384 rows at the same 144 column VGPRs, eight waves (the block pairs of the D_s = 384
-// eigensolver).
-template <int MAXCH, int OCC, int LANES>
-__global__ __launch_bounds__(16 * LANES) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void jacobi_b6_kernel(
+// Hex-block: lane i < 6 of every group of 8 computes rotation i and owns column i of either block (lanes 6, 7 idle
+// along: their entries are kept at zero and they never rotate); entries move over the LDS crossbar.
+template <> struct BlockOrder<6> {
+  struct Lane {
+    int q8;                                        // lane within its group of 8
+    bool bit0, bit1, bit2;
+    bool rlane;                                    // this lane computes a rotation / owns a column entry
+    int grp4;                                      // byte index of lane 0 of this lane's group of 8 (ds_bpermute)
+  };
+  __device__ __forceinline__ static Lane lane(int tid, int sub) {
+    return {sub & 7, (sub & 1) != 0, (sub & 2) != 0, (sub & 4) != 0, (sub & 7) < 6, ((tid & 63) & ~7) << 2};
+  }
+  __device__ __forceinline__ static bool owner(const Lane& L, int /*sub*/) { return L.rlane; }
+  __device__ __forceinline__ static int meta_col(const Lane& L) { return L.rlane ? L.q8 : 5; }
+  // 16 slots: four waves at 16 lanes, eight at 32 (columns of up to 384 rows at the same 144 column VGPRs: the block
+  // pairs of the D_s = 384 eigensolver)
+  static constexpr int max_threads(int /*maxch*/, int lanes) { return 16 * lanes; }
+  static constexpr int status_kind = 7;
+  // the crossbar has latency: a round asks for the entries of its columns before the dot products, which hide it, and
+  // hands the new ones back after the parameter broadcasts
+  static constexpr bool entries_first = true;
+
+  template <class M, int MAXCH> __device__ __forceinline__ static void dots(const v4f (&C)[12][MAXCH], float (&p)[6]) {
+    dot6_cols<MAXCH>(C[M::X(0)], C[M::Y(0)], C[M::X(1)], C[M::Y(1)], C[M::X(2)], C[M::Y(2)], C[M::X(3)], C[M::Y(3)],
+                     C[M::X(4)], C[M::Y(4)], C[M::X(5)], C[M::Y(5)], p);
+  }
+  template <int LANES> __device__ __forceinline__ static float reduce_scatter(const float (&p)[6], const Lane& L) {
+    return reduce_scatter6<LANES>(p, L.bit0, L.bit1, L.bit2);
+  }
+  template <unsigned TBL, unsigned MASK, unsigned IDENT>
+  __device__ __forceinline__ static float move(float mp, float mq, const Lane& L) {
+    return meta_move6<TBL, MASK, IDENT>(mp, mq, L.q8, L.grp4 | (((TBL >> (3 * L.q8)) & 7) << 2));
+  }
+  template <class M> __device__ __forceinline__ static float gather_x(float mp, float mq, const Lane& L) {
+    return move<M::gx, M::xq, M::IDENT>(mp, mq, L);
+  }
+  template <class M> __device__ __forceinline__ static float gather_y(float mp, float mq, const Lane& L) {
+    return move<M::gy, M::yq, M::IDENT>(mp, mq, L);
+  }
+  template <class M> __device__ __forceinline__ static float scatter_p(float xn, float yn, const Lane& L) {
+    return move<M::sp, M::py, M::IDENT>(xn, yn, L);
+  }
+  template <class M> __device__ __forceinline__ static float scatter_q(float xn, float yn, const Lane& L) {
+    return move<M::sq, M::qy, M::IDENT>(xn, yn, L);
+  }
+  // (measured for the (a, b) pairs of a round: through 96 bytes of LDS per slot -- one 8-byte write by the parameter
+  // lanes, three 16-byte broadcast reads by all lanes -- instead of twelve swizzles: 3.335 vs 3.32 ms per 1024 x 192^2,
+  // 0.97 vs 0.98 for a single matrix: the crossbar operations are not what a round waits for; not kept)
+  template <int I> __device__ __forceinline__ static float bcast(float v) { return bcast8<I>(v); }
+  // the fifteen pairs inside each block, once per sweep: five rounds of three pairs per block
+  template <class F> __device__ __forceinline__ static void inner_rounds(F&& round, bool ok) {
+    round(Round6<0, 5, 1, 4, 2, 3, 6, 11, 7, 10, 8, 9>{}, ok);
+    round(Round6<0, 4, 5, 3, 1, 2, 6, 10, 11, 9, 7, 8>{}, ok);
+    round(Round6<0, 3, 4, 2, 5, 1, 6, 9, 10, 8, 11, 7>{}, ok);
+    round(Round6<0, 2, 3, 1, 4, 5, 6, 8, 9, 7, 10, 11>{}, ok);
+    round(Round6<0, 1, 2, 5, 3, 4, 6, 7, 8, 11, 9, 10>{}, ok);
+  }
+  // a meeting of blocks P and Q: 36 cross rotations in six rounds
+  template <class F> __device__ __forceinline__ static void cross_rounds(F&& round, bool ok) {
+    round(Round6<0, 6, 1, 7, 2, 8, 3, 9, 4, 10, 5, 11>{}, ok);
+    round(Round6<0, 7, 1, 8, 2, 9, 3, 10, 4, 11, 5, 6>{}, ok);
+    round(Round6<0, 8, 1, 9, 2, 10, 3, 11, 4, 6, 5, 7>{}, ok);
+    round(Round6<0, 9, 1, 10, 2, 11, 3, 6, 4, 7, 5, 8>{}, ok);
+    round(Round6<0, 10, 1, 11, 2, 6, 3, 7, 4, 8, 5, 9>{}, ok);
+    round(Round6<0, 11, 1, 6, 2, 7, 3, 8, 4, 9, 5, 10>{}, ok);
+  }
+};
+
+// The block kernel: one workgroup per matrix, a slot of LANES lanes owns two blocks (P, Q) of BC columns, 4 * LANES
+// rows per chunk, MAXCH chunks.  BlockOrder<BC> supplies what depends on the block width; the sweep, the debris pass,
+// the hand-over, convergence, ranking and write-back below are the same for both orderings.
+// OCC = waves per SIMD the register allocation aims at.  Hex-block at three chunks: 1 (a batch that leaves every CU at
+// most one matrix at a time: no spills, the latency of the parameter stream is all that counts) or 2 (two matrices
+// per CU hide each other's parameter stream).
+template <int BC, int MAXCH, int OCC, int LANES>
+__global__ __launch_bounds__(BlockOrder<BC>::max_threads(MAXCH, LANES))
+__attribute__((amdgpu_waves_per_eu(OCC, OCC))) void jacobi_block_kernel(
     float* __restrict__ wg, int batch, int m, int n, int ld, int norm_rows, float tol, int max_sweeps, int sort,
     float* __restrict__ sigma, int32_t* __restrict__ sweeps_out, int32_t* __restrict__ status,
     const int32_t* __restrict__ active, int active_mode) {
-  // active_mode as in jacobi_b4_kernel
+  // active_mode 0: no `active`; 1: active[mat] = number of leading non-zero columns (the tournament runs over those,
+  // the other columns are zero and stay zero); 2: the same and only the leading active[mat] ROWS are non-zero;
+  // 3: `active` is a mask (< 0: skip the matrix, otherwise solve it completely)
+  using P = BlockOrder<BC>;
   extern __shared__ __align__(16) float lds[];
   const int mat = blockIdx.x;
   int n_act = n;
   if (active_mode != 0) {
     const int av = active[mat];
-    if (av < 0) {
+    if (av < 0) {                                  // masked problem (any mode): nothing is read or written
       if (sweeps_out && threadIdx.x == 0) sweeps_out[mat] = 0;
       return;
     }
     if (active_mode != 3) n_act = av < 2 ? 2 : (av > n ? n : av);
   }
-  constexpr int CHR = 4 * LANES;
-  constexpr int LDC = CHR * MAXCH;
-  constexpr int LDB = 6 * LDC;
+  constexpr int NC = 2 * BC;                       // columns of a slot: 0 .. BC-1 block P, BC .. NC-1 block Q
+  constexpr int CHR = 4 * LANES;                   // rows of one chunk (4 per lane)
+  constexpr int LDC = CHR * MAXCH;                 // one column in the mailbox
+  constexpr int LDB = BC * LDC;                    // one block
   const int tid = threadIdx.x;
-  const int k = tid / LANES, sub = tid % LANES, roff = sub * 4, q8 = sub & 7;
-  const bool bit0 = (sub & 1) != 0, bit1 = (sub & 2) != 0, bit2 = (sub & 4) != 0;
-  const bool rlane = q8 < 6;                       // this lane computes a rotation / owns a column entry
-  const int grp4 = ((tid & 63) & ~7) << 2;         // byte index of lane 0 of this lane's group of 8 (ds_bpermute)
-  const int nb_all = (n + 5) / 6;
-  const int S_all = (nb_all + 1) >> 1;
-  const int nb = (n_act + 5) / 6;
-  const int nbe = nb + (nb & 1);
-  const int S = nbe >> 1;
+  const int k = tid / LANES, sub = tid % LANES, roff = sub * 4;
+  const typename P::Lane L = P::lane(tid, sub);
+  const int nb_all = ceil_div<BC>(n);
+  const int S_all = (nb_all + 1) >> 1;             // slots the launch provides (threads / LANES, rounded up to waves)
+  const int nb = ceil_div<BC>(n_act);              // blocks that hold active columns
+  const int nbe = nb + (nb & 1);                   // line length in blocks (a zero phantom block pads odd nb)
+  const int S = nbe >> 1;                          // slots that take part
   float* mbox = lds;                               // [S_all + 1][LDB]
-  float* s_sig = mbox + (size_t)(S_all + 1) * LDB; // [12 S_all] by position
-  int* s_rank = reinterpret_cast<int*>(s_sig + 200);
-  float* s_nrm = reinterpret_cast<float*>(s_rank + 200);  // [S_all + 1][6]
-  float* s_scl = s_nrm + 104;
-  int* s_flag = reinterpret_cast<int*>(s_scl + 104);
+  float* s_sig = mbox + (size_t)(S_all + 1) * LDB; // [NC S_all] by position
+  int* s_rank = reinterpret_cast<int*>(s_sig + 200);      // [NC S_all]
+  float* s_nrm = reinterpret_cast<float*>(s_rank + 200);  // [S_all + 1][BC] squared norms travelling with the mailbox
+  float* s_scl = s_nrm + 104;                      // [S_all + 1][BC] scales
+  int* s_flag = reinterpret_cast<int*>(s_scl + 104);      // [2] any rotation, [2] any LARGE rotation, [2] max norm
 
   float* src = wg + (size_t)mat * n * ld;
   int mr = (m + 3) & ~3;
   if (active_mode == 2) { const int ma = (n_act + 3) & ~3; mr = ma < mr ? ma : mr; }
   const bool live = k < S;
   const bool last = k == S - 1;
-  float* const mybox = mbox + (size_t)k * LDB + roff;
-  float* const mymeta = s_nrm + 6 * k + (rlane ? q8 : 5);
-  v4f C[12][MAXCH];
+  float* const mybox = mbox + (size_t)k * LDB + roff;          // box k, this lane's rows
+  float* const mymeta = s_nrm + BC * k + P::meta_col(L);       // box k, this lane's column: norm, +104 scale
+  v4f C[NC][MAXCH];
 #pragma unroll
-  for (int c = 0; c < 12; ++c) {
-    const int idc = 12 * k + c;
+  for (int c = 0; c < NC; ++c) {
+    const int idc = NC * k + c;
 #pragma unroll
     for (int ch = 0; ch < MAXCH; ++ch) {
       const int r = roff + CHR * ch;
@@ -1004,6 +845,9 @@ __global__ __launch_bounds__(16 * LANES) __attribute__((amdgpu_waves_per_eu(OCC,
                                                  : (v4f){0.f, 0.f, 0.f, 0.f};
     }
   }
+  // distributed bookkeeping: an owner lane holds the entry of one column of block P (nP, dP) and of one of block Q.
+  // Column ids are NOT carried: blocks move as wholes on a data-independent schedule -- a sweep of the odd-even
+  // transposition line reverses the block order, so after s sweeps position p holds block (s odd ? nbe - 1 - p : p).
   float nP = 0.f, nQ = 0.f, dP = 1.f, dQ = 1.f;
   if (tid < 8) s_flag[tid] = 0;
   __syncthreads();
@@ -1011,20 +855,29 @@ __global__ __launch_bounds__(16 * LANES) __attribute__((amdgpu_waves_per_eu(OCC,
   const float inv_tol = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(1.0f / tol)));
   bool rotated = false, bigrot = false;
 
+  // one round: BC independent rotations (M::X(i), M::Y(i)) covering all NC columns of the slot
   auto round = [&](auto map, bool ok) {
     using M = decltype(map);
-    // partner entries first: the crossbar latency hides under the dot products
-    const int ixx = grp4 | (((M::gx >> (3 * q8)) & 7) << 2), ixy = grp4 | (((M::gy >> (3 * q8)) & 7) << 2);
-    const float al = meta_move6<M::gx, M::xq, M::IDENT>(nP, nQ, q8, ixx), be = meta_move6<M::gy, M::yq, M::IDENT>(nP, nQ, q8, ixy);
-    const float dx = meta_move6<M::gx, M::xq, M::IDENT>(dP, dQ, q8, ixx), dy = meta_move6<M::gy, M::yq, M::IDENT>(dP, dQ, q8, ixy);
-    float p[6];
-    dot6_cols<MAXCH>(C[M::X(0)], C[M::Y(0)], C[M::X(1)], C[M::Y(1)], C[M::X(2)], C[M::Y(2)], C[M::X(3)], C[M::Y(3)],
-                     C[M::X(4)], C[M::Y(4)], C[M::X(5)], C[M::Y(5)], p);
-    const float gt = reduce_scatter6<LANES>(p, bit0, bit1, bit2);
-    const float g = gt * dx * dy;
+    // WHERE the entries of the round's columns are fetched and handed back is the ordering's (P::entries_first): the
+    // instruction schedule and the register allocation of these kernels follow the statement order
+    float al, be, dx, dy;
+    auto fetch = [&] {
+      al = P::template gather_x<M>(nP, nQ, L); be = P::template gather_y<M>(nP, nQ, L);
+      dx = P::template gather_x<M>(dP, dQ, L); dy = P::template gather_y<M>(dP, dQ, L);
+    };
+    if constexpr (P::entries_first) fetch();
+    float p[BC];
+    P::template dots<M, MAXCH>(C, p);
+    const float gt = P::template reduce_scatter<LANES>(p, L);
+    if constexpr (!P::entries_first) fetch();
+    const float g = gt * dx * dy;                 // dot product of the true columns
     const float gsc = g * inv_tol;
     const float ab_ = al * be;
-    const bool rot = ok & rlane & (gsc * gsc > fmaxf(ab_, BASD_JACOBI_TINY));
+    const bool rot = ok & L.rlane & (gsc * gsc > fmaxf(ab_, BASD_JACOBI_TINY));
+    // no branch around the rotation: a round in which all rotations of the wave are below the threshold only
+    // occurs on padded / rank-deficient columns (the solve stops after the first sweep of small rotations), and a
+    // merge point after the in-place shears costs 48 register moves per round (the allocator does not coalesce the
+    // halves of the column registers across it); converged pairs run the shears with a = b = 0, an exact no-op
     rotated |= rot;
     const float gq = g * (1.0f / BASD_JACOBI_QUAD);
     const bool big_cos = gq * gq > ab_;
@@ -1037,52 +890,46 @@ __global__ __launch_bounds__(16 * LANES) __attribute__((amdgpu_waves_per_eu(OCC,
     c = c * fmaf(-0.5f * w, c * c, 1.5f);
     const float sn = c * t;
     const float u = sn * __builtin_amdgcn_rcpf(1.0f + c);
-    const float h = sn * u, hp = t * u;
+    const float h = sn * u, hp = t * u;            // 1 - c and 1 / c - 1, no cancellation
     const float aln = fmaf(-t, g, al), ben = fmaf(t, g, be);
     const float a = t * (dy * __builtin_amdgcn_rcpf(dx));
     const float b = (sn * c) * (dx * __builtin_amdgcn_rcpf(dy));
     const float dxn = fmaf(-dx, h, dx), dyn = fmaf(dy, hp, dy);
-    // (measured: the six (a, b) pairs through 96 bytes of LDS per slot -- one 8-byte write by the parameter lanes, three
-    // 16-byte broadcast reads by all lanes -- instead of these twelve swizzles: 3.335 vs 3.32 ms per 1024 x 192^2,
-    // 0.97 vs 0.98 for a single matrix: the crossbar operations are not what a round waits for; not kept)
-    v2f_rot ab[6];
-    ab[0] = (v2f_rot){bcast8<0>(a), bcast8<0>(b)};
-    ab[1] = (v2f_rot){bcast8<1>(a), bcast8<1>(b)};
-    ab[2] = (v2f_rot){bcast8<2>(a), bcast8<2>(b)};
-    ab[3] = (v2f_rot){bcast8<3>(a), bcast8<3>(b)};
-    ab[4] = (v2f_rot){bcast8<4>(a), bcast8<4>(b)};
-    ab[5] = (v2f_rot){bcast8<5>(a), bcast8<5>(b)};
-    const int isp = grp4 | (((M::sp >> (3 * q8)) & 7) << 2), isq = grp4 | (((M::sq >> (3 * q8)) & 7) << 2);
-    nP = meta_move6<M::sp, M::py, M::IDENT>(aln, ben, q8, isp);
-    nQ = meta_move6<M::sq, M::qy, M::IDENT>(aln, ben, q8, isq);
-    dP = meta_move6<M::sp, M::py, M::IDENT>(dxn, dyn, q8, isp);
-    dQ = meta_move6<M::sq, M::qy, M::IDENT>(dxn, dyn, q8, isq);
+    auto hand_back = [&] {
+      nP = P::template scatter_p<M>(aln, ben, L);
+      nQ = P::template scatter_q<M>(aln, ben, L);
+      dP = P::template scatter_p<M>(dxn, dyn, L);
+      dQ = P::template scatter_q<M>(dxn, dyn, L);
+    };
+    if constexpr (!P::entries_first) hand_back();
+    v2f_rot ab[BC];
+    static_for<BC>([&](auto i) { ab[i] = (v2f_rot){P::template bcast<i>(a), P::template bcast<i>(b)}; });
+    if constexpr (P::entries_first) hand_back();
 #pragma unroll
-    for (int i = 0; i < 6; ++i) {
+    for (int i = 0; i < BC; ++i) {
 #pragma unroll
       for (int ch = 0; ch < MAXCH; ++ch) shear_in_place(C[M::X(i)][ch], C[M::Y(i)][ch], ab[i]);
     }
     __builtin_amdgcn_sched_barrier(0);
   };
 
+  // fold the scales into the columns (x <- d x~, d <- 1); `kill` zeroes a column instead
   auto fold = [&](bool killP, bool killQ) {
     const float fP = killP ? 0.f : dP, fQ = killQ ? 0.f : dQ;
-    float f[12];
-    f[0] = bcast8<0>(fP); f[1] = bcast8<1>(fP); f[2] = bcast8<2>(fP);
-    f[3] = bcast8<3>(fP); f[4] = bcast8<4>(fP); f[5] = bcast8<5>(fP);
-    f[6] = bcast8<0>(fQ); f[7] = bcast8<1>(fQ); f[8] = bcast8<2>(fQ);
-    f[9] = bcast8<3>(fQ); f[10] = bcast8<4>(fQ); f[11] = bcast8<5>(fQ);
+    float f[2][BC];
+    static_for<BC>([&](auto i) { f[0][i] = P::template bcast<i>(fP); });
+    static_for<BC>([&](auto i) { f[1][i] = P::template bcast<i>(fQ); });
 #pragma unroll
-    for (int c = 0; c < 12; ++c) {
+    for (int c = 0; c < NC; ++c) {
 #pragma unroll
-      for (int ch = 0; ch < MAXCH; ++ch) C[c][ch] *= f[c];
+      for (int ch = 0; ch < MAXCH; ++ch) C[c][ch] *= f[c / BC][c % BC];
     }
     dP = 1.f; dQ = 1.f;
   };
   auto exact_norms = [&](int rows) {
-    float p[12];
+    float p[2][BC];
 #pragma unroll
-    for (int c = 0; c < 12; ++c) {
+    for (int c = 0; c < NC; ++c) {
       float a = 0.f;
 #pragma unroll
       for (int ch = 0; ch < MAXCH; ++ch) {
@@ -1092,95 +939,91 @@ __global__ __launch_bounds__(16 * LANES) __attribute__((amdgpu_waves_per_eu(OCC,
         const float mz = (r + 2 < rows) ? 1.f : 0.f, mw = (r + 3 < rows) ? 1.f : 0.f;
         a = fmaf(mx * x.x, x.x, fmaf(my * x.y, x.y, fmaf(mz * x.z, x.z, fmaf(mw * x.w, x.w, a))));
       }
-      p[c] = a;
+      p[c / BC][c % BC] = a;
     }
-    const float pp[6] = {p[0], p[1], p[2], p[3], p[4], p[5]}, pq[6] = {p[6], p[7], p[8], p[9], p[10], p[11]};
-    nP = reduce_scatter6<LANES>(pp, bit0, bit1, bit2);
-    nQ = reduce_scatter6<LANES>(pq, bit0, bit1, bit2);
-    if (!rlane) { nP = 0.f; nQ = 0.f; }
+    nP = P::template reduce_scatter<LANES>(p[0], L);
+    nQ = P::template reduce_scatter<LANES>(p[1], L);
+    if (!L.rlane) { nP = 0.f; nQ = 0.f; }
   };
 
   int used_sweeps = 0;
   bool converged = false;
-  int step = 0;
+  int step = 0;                                    // even = blocks (2k, 2k+1); nbe is even, sweeps start and end there
 #pragma unroll 1
   for (int sweep = 0; sweep < max_sweeps; ++sweep) {
     rotated = false;
     bigrot = false;
     fold(false, false);
     exact_norms(1 << 30);
-    if (live && rlane) atomicMax(&s_flag[4 + (sweep & 1)], __float_as_int(fmaxf(nP, nQ)));
+    if (live && P::owner(L, sub)) atomicMax(&s_flag[4 + (sweep & 1)], __float_as_int(fmaxf(nP, nQ)));
     lds_barrier();
     {
       const float debris = __int_as_float(s_flag[4 + (sweep & 1)]) * BASD_JACOBI_DEBRIS;
-      const bool zP = rlane & (nP < debris), zQ = rlane & (nQ < debris);
+      const bool zP = L.rlane & (nP < debris), zQ = L.rlane & (nQ < debris);   // debris columns become exact zero columns
       if (__builtin_amdgcn_ballot_w64(zP || zQ) != 0) {
         fold(zP, zQ);
         if (zP) nP = 0.f;
         if (zQ) nQ = 0.f;
       }
     }
-    // the fifteen pairs inside each block, once per sweep: five rounds of three pairs per block
-    round(Round6<0, 5, 1, 4, 2, 3, 6, 11, 7, 10, 8, 9>{}, live);
-    round(Round6<0, 4, 5, 3, 1, 2, 6, 10, 11, 9, 7, 8>{}, live);
-    round(Round6<0, 3, 4, 2, 5, 1, 6, 9, 10, 8, 11, 7>{}, live);
-    round(Round6<0, 2, 3, 1, 4, 5, 6, 8, 9, 7, 10, 11>{}, live);
-    round(Round6<0, 1, 2, 5, 3, 4, 6, 7, 8, 11, 9, 10>{}, live);
+    P::inner_rounds(round, live);
 #pragma unroll 1
     for (int t = 0; t < nbe; ++t, ++step) {
       const bool even_view = (step & 1) == 0;
       const bool pair_ok = live & (even_view | !last);
-      round(Round6<0, 6, 1, 7, 2, 8, 3, 9, 4, 10, 5, 11>{}, pair_ok);
-      round(Round6<0, 7, 1, 8, 2, 9, 3, 10, 4, 11, 5, 6>{}, pair_ok);
-      round(Round6<0, 8, 1, 9, 2, 10, 3, 11, 4, 6, 5, 7>{}, pair_ok);
-      round(Round6<0, 9, 1, 10, 2, 11, 3, 6, 4, 7, 5, 8>{}, pair_ok);
-      round(Round6<0, 10, 1, 11, 2, 6, 3, 7, 4, 8, 5, 9>{}, pair_ok);
-      round(Round6<0, 11, 1, 6, 2, 7, 3, 8, 4, 9, 5, 10>{}, pair_ok);
+      P::cross_rounds(round, pair_ok);
+      // ---- hand one block over (positions swap after a meeting: the pair is then stored as lo = Q, hi = P).
+      // ONE base address per lane for the boxes and one for their bookkeeping entries; everything else is an
+      // immediate offset (box k at 0, box k + 1 at LDB; norms / scales 104 entries apart)
       if (even_view) {
+        // Q (block position 2k) goes to slot k-1 through box k (slot 0's stays parked there); the last slot has no
+        // right neighbour: it parks its P in box S and takes it back as Q (its lone block of the odd view)
         if (live) {
 #pragma unroll
-          for (int c = 0; c < 6; ++c) {
+          for (int c = 0; c < BC; ++c) {
 #pragma unroll
-            for (int ch = 0; ch < MAXCH; ++ch) *reinterpret_cast<v4f*>(mybox + c * LDC + CHR * ch) = C[6 + c][ch];
+            for (int ch = 0; ch < MAXCH; ++ch) *reinterpret_cast<v4f*>(mybox + c * LDC + CHR * ch) = C[BC + c][ch];
           }
-          if (sub < 6) { mymeta[0] = nQ; mymeta[104] = dQ; }
+          if (sub < BC) { mymeta[0] = nQ; mymeta[104] = dQ; }
           if (last) {
 #pragma unroll
-            for (int c = 0; c < 6; ++c) {
+            for (int c = 0; c < BC; ++c) {
 #pragma unroll
               for (int ch = 0; ch < MAXCH; ++ch) *reinterpret_cast<v4f*>(mybox + LDB + c * LDC + CHR * ch) = C[c][ch];
             }
-            if (sub < 6) { mymeta[6] = nP; mymeta[104 + 6] = dP; }
+            if (sub < BC) { mymeta[BC] = nP; mymeta[104 + BC] = dP; }
           }
         }
         lds_barrier();
         if (live) {
 #pragma unroll
-          for (int c = 0; c < 6; ++c) {
+          for (int c = 0; c < BC; ++c) {
 #pragma unroll
-            for (int ch = 0; ch < MAXCH; ++ch) C[6 + c][ch] = *reinterpret_cast<const v4f*>(mybox + LDB + c * LDC + CHR * ch);
+            for (int ch = 0; ch < MAXCH; ++ch) C[BC + c][ch] = *reinterpret_cast<const v4f*>(mybox + LDB + c * LDC + CHR * ch);
           }
-          nQ = mymeta[6]; dQ = mymeta[104 + 6];
+          nQ = mymeta[BC]; dQ = mymeta[104 + BC];
         }
       } else {
+        // P (position 2k+2 after the swap) goes to slot k+1 through box k+1; slot 0 takes the parked block back
         if (live && !last) {
 #pragma unroll
-          for (int c = 0; c < 6; ++c) {
+          for (int c = 0; c < BC; ++c) {
 #pragma unroll
             for (int ch = 0; ch < MAXCH; ++ch) *reinterpret_cast<v4f*>(mybox + LDB + c * LDC + CHR * ch) = C[c][ch];
           }
-          if (sub < 6) { mymeta[6] = nP; mymeta[104 + 6] = dP; }
+          if (sub < BC) { mymeta[BC] = nP; mymeta[104 + BC] = dP; }
         }
         lds_barrier();
         if (live) {
 #pragma unroll
-          for (int c = 0; c < 6; ++c) {
+          for (int c = 0; c < BC; ++c) {
 #pragma unroll
             for (int ch = 0; ch < MAXCH; ++ch) C[c][ch] = *reinterpret_cast<const v4f*>(mybox + c * LDC + CHR * ch);
           }
           nP = mymeta[0]; dP = mymeta[104];
         }
       }
+      // no second barrier: the next write to a box comes from the slot that has just read it (see the quad-block header)
     }
     used_sweeps = sweep + 1;
     if (rotated) s_flag[sweep & 1] = 1;
@@ -1192,23 +1035,28 @@ __global__ __launch_bounds__(16 * LANES) __attribute__((amdgpu_waves_per_eu(OCC,
     if (!any || !anybig) { converged = true; break; }
   }
 
+  // ---- singular values = norms of the true columns over the first norm_rows rows
   fold(false, false);
   exact_norms(norm_rows);
-  lds_barrier();
+  lds_barrier();                                   // every wave is out of the sweep loop (mailbox reads done)
+  // The thread-derived indices are re-derived here from an opaque copy of the thread id: kept live across the sweep
+  // loop they cost registers the rotation rounds need (the allocator spills them into the inner loop otherwise).
   int tid2 = threadIdx.x;
   asm volatile("" : "+v"(tid2));
   const int k2 = tid2 / LANES, sub2 = tid2 % LANES, roff2 = sub2 * 4;
   const bool live2 = k2 < S;
+  // column ids by position: live slots hold block (sweeps odd ? nbe - 1 - p : p) at block position p; slots beyond
+  // the tournament never moved.  Ranking levels: active columns >= 0, inactive real columns -1, phantoms (id >= n) -2.
   const bool odd = (used_sweeps & 1) != 0;
   const int bP = live2 ? (odd ? nbe - 1 - 2 * k2 : 2 * k2) : 2 * k2;
   const int bQ = live2 ? (odd ? nbe - 2 - 2 * k2 : 2 * k2 + 1) : 2 * k2 + 1;
-  if (k2 < S_all && sub2 < 6) {
-    const int idP = 6 * bP + sub2, idQ = 6 * bQ + sub2;
-    s_sig[12 * k2 + sub2] = idP >= n ? -2.f : ((live2 && idP < n_act) ? sqrtf(nP) : -1.f);
-    s_sig[12 * k2 + 6 + sub2] = idQ >= n ? -2.f : ((live2 && idQ < n_act) ? sqrtf(nQ) : -1.f);
+  if (k2 < S_all && sub2 < BC) {
+    const int idP = BC * bP + sub2, idQ = BC * bQ + sub2;
+    s_sig[NC * k2 + sub2] = idP >= n ? -2.f : ((live2 && idP < n_act) ? sqrtf(nP) : -1.f);
+    s_sig[NC * k2 + BC + sub2] = idQ >= n ? -2.f : ((live2 && idQ < n_act) ? sqrtf(nQ) : -1.f);
   }
   lds_barrier();
-  const int n_tot = 12 * S_all;
+  const int n_tot = NC * S_all;                    // >= n
   for (int p = tid2; p < n_tot; p += blockDim.x) {
     int rank = p;
     if (sort) {
@@ -1224,10 +1072,10 @@ __global__ __launch_bounds__(16 * LANES) __attribute__((amdgpu_waves_per_eu(OCC,
   lds_barrier();
   if (k2 < S_all) {
 #pragma unroll
-    for (int c = 0; c < 12; ++c) {
-      const int idc = 6 * (c < 6 ? bP : bQ) + (c % 6);
-      const int d = sort ? s_rank[12 * k2 + c] : idc;
-      const float sg = s_sig[12 * k2 + c];
+    for (int c = 0; c < NC; ++c) {
+      const int idc = BC * (c < BC ? bP : bQ) + (c % BC);
+      const int d = sort ? s_rank[NC * k2 + c] : idc;
+      const float sg = s_sig[NC * k2 + c];
       if (idc < n && d < n) {
 #pragma unroll
         for (int ch = 0; ch < MAXCH; ++ch) {
@@ -1239,7 +1087,7 @@ __global__ __launch_bounds__(16 * LANES) __attribute__((amdgpu_waves_per_eu(OCC,
     }
   }
   if (sweeps_out && tid2 == 0) sweeps_out[mat] = converged ? used_sweeps : -used_sweeps;
-  report_status(status, converged, s_sig, n_tot, tid2, blockDim.x, 7, mat);
+  report_status(status, converged, s_sig, n_tot, tid2, blockDim.x, P::status_kind, mat);
 }
 
 }  // namespace basd
@@ -1297,20 +1145,20 @@ extern "C" int basd_jacobi_svd(float* w, int batch, int m_rows, int n_cols, int 
   // win -- 48 x 64^2: 0.136 vs 0.210 ms)
   if (n_cols > 128 && n_cols <= 192 && (rows4 <= 192 || (rows4 > 256 && rows4 <= 384))) {
     const char* what = "jacobi_svd (hex-block, scaled rotations)";
-    if (lanes == 32) return launch_block(jacobi_b6_kernel<3, 2, 32>, 6, what);
-    if (chn == 1) return launch_block(jacobi_b6_kernel<1, 2, 16>, 6, what);
-    if (chn == 2) return launch_block(jacobi_b6_kernel<2, 2, 16>, 6, what);
+    if (lanes == 32) return launch_block(jacobi_block_kernel<6, 3, 2, 32>, 6, what);
+    if (chn == 1) return launch_block(jacobi_block_kernel<6, 1, 2, 16>, 6, what);
+    if (chn == 2) return launch_block(jacobi_block_kernel<6, 2, 2, 16>, 6, what);
     // 144 column VGPRs: a second workgroup per SIMD only pays once every CU has more than one matrix
-    if (batch > 256) return launch_block(jacobi_b6_kernel<3, 2, 16>, 6, what);
-    return launch_block(jacobi_b6_kernel<3, 1, 16>, 6, what);
+    if (batch > 256) return launch_block(jacobi_block_kernel<6, 3, 2, 16>, 6, what);
+    return launch_block(jacobi_block_kernel<6, 3, 1, 16>, 6, what);
   }
   if (n_cols >= 8 && rows4 <= 384 && n_cols <= ((rows4 > 192 && rows4 <= 256) ? 196 : 192)) {
     const char* what = "jacobi_svd (quad-block, scaled rotations)";
-    if (lanes == 32) return launch_block(jacobi_b4_kernel<3, 32>, 4, what);
-    if (chn == 1) return launch_block(jacobi_b4_kernel<1, 16>, 4, what);
-    if (chn == 2) return launch_block(jacobi_b4_kernel<2, 16>, 4, what);
-    if (chn == 3) return launch_block(jacobi_b4_kernel<3, 16>, 4, what);
-    return launch_block(jacobi_b4_kernel<4, 16>, 4, what);
+    if (lanes == 32) return launch_block(jacobi_block_kernel<4, 3, 3, 32>, 4, what);
+    if (chn == 1) return launch_block(jacobi_block_kernel<4, 1, 3, 16>, 4, what);
+    if (chn == 2) return launch_block(jacobi_block_kernel<4, 2, 3, 16>, 4, what);
+    if (chn == 3) return launch_block(jacobi_block_kernel<4, 3, 3, 16>, 4, what);
+    return launch_block(jacobi_block_kernel<4, 4, 2, 16>, 4, what);
   }
   if (rows4 <= 224) {
     // 2, 4, 6 or 7 chunks of 32 rows in registers; double-buffered mailbox if it fits, else a single one (more than
