@@ -34,6 +34,8 @@
  *   basd_procrustes_prep   src/losses/relational.py:29-46, src/losses/combined.py:9-14
  *   basd_mix_grad_dots     autograd of layer_selector.py:111-112 w.r.t. the mixing weights
  *   basd_gemm_bf16         timm nn.Linear (+ nn.GELU) forward of the ViT blocks, teacher.py:212 / trainer.py:33
+ *   basd_gemm_bf16_act     the same with the MLP activation of a timm CLIP / SigLIP teacher (QuickGELU, tanh-GELU)
+ *   basd_vit_embed_bf16    timm VisionTransformer._pos_embed + norm_pre of a frozen teacher (teacher.py:113-148 loads any)
  *   basd_gemm_bf16_gelu_fwd, basd_gemm_bf16_gelu_bwd
  *                          timm Mlp (fc1 -> nn.GELU -> fc2) of the TRAINED student: forward and autograd (trainer.py:33,157)
  *   basd_gemm_bf16x3_f32   the teacher-token projection tokens.reshape(-1, D_t) @ proj_t.T (layer_selector.py:72 / :135)
@@ -373,6 +375,17 @@ int basd_bgemm_f64_masked(const void* a, int a_dtype, int64_t a_stride, int lda,
 int basd_gemm_bf16(const void* x, const void* w, const void* bias, void* y, int64_t M, int N, int K,
                    int epilogue, int tile_run, void* stream);
 
+/* The same GEMM with the activation of a frozen teacher's MLP named explicitly (timm Mlp.act of the CLIP / SigLIP ViTs):
+ *   y[m][n] = bf16(act(sum_k x[m][k] w[n][k] + bias[n])),   bias nullable,
+ * act: 0 = none, 1 = exact-erf GELU (bitwise basd_gemm_bf16 with epilogue 2), 2 = QuickGELU x sigmoid(1.702 x)
+ * (OpenAI-weight CLIP), 3 = tanh-GELU 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3))) (SigLIP).  The activation is
+ * taken in fp32 on the fp32 sum before the single rounding to bf16; 2 and 3 are evaluated as x / (1 + 2^(-s log2 e))
+ * with the hardware's 1-ulp exp2 and reciprocal: absolute error <= 8 * 2^-24 * max(1, |x|) before the rounding, no
+ * overflow for any finite x (a saturated exponential gives 0 or x).  Shapes, tile_run, kernels and schedule as
+ * basd_gemm_bf16.  Any other act is BASD_ERR_SHAPE before anything is enqueued. */
+int basd_gemm_bf16_act(const void* x, const void* w, const void* bias, void* y, int64_t M, int N, int K,
+                       int act, int tile_run, void* stream);
+
 /* Teacher-statistics projection z = X P^T at student widths > 256 (src/losses/layer_selector.py:72 / :135: the fixed fp32 projection of
  * the teacher tokens in front of the subspace SVD): x [M, K] bf16 row-major, w3 [ceil(N / 256) * 256, 3 K] bf16 = the
  * (hi | mid | lo) bf16 splits of P's rows side by side (zero rows behind N), y [M, N] fp32.  One persistent bf16-MFMA
@@ -416,6 +429,17 @@ int basd_layernorm_fwd_bf16(const void* x, const float* gamma, const float* beta
 int basd_add_layernorm_fwd_bf16(const void* x, const void* residual, const float* gamma, const float* beta,
                                 int64_t rows, int D, float eps, void* sum_out, void* y, float* mean,
                                 float* rstd, const float* row_scale, int rows_per_scale, void* stream);
+/* Token assembly in front of block 0 of a ViT (timm _pos_embed + CLIP's norm_pre) in one launch:
+ *   out[b, t, :] = LN(bf16(src(b, t) + pos[t, :])),   src = cls for t = 0 when cls != NULL, else the patch row.
+ * patches [B, N, D] bf16 (the patch-embedding GEMM's output), cls [D] bf16 or NULL, pos [T, D] bf16 with
+ * T = N + (cls != NULL), out [B, T, D] bf16, must not overlap patches.  gamma / beta fp32 [D], both or neither: NULL =
+ * the plain assembly, bitwise torch's cat + add on bf16; otherwise the rounded sum is layer-normalised with the
+ * arithmetic of basd_layernorm_fwd_bf16 (fp32 two-pass statistics, one rounding) and only the normalised row is written.
+ * 16-byte accesses when all four pointers are 16-byte aligned, element accesses otherwise.  No workspace, no
+ * allocation, no synchronisation.  D % 8 == 0, 8 <= D <= 2048, B >= 0, N >= 0, T >= 1, else BASD_ERR_SHAPE before
+ * anything is enqueued. */
+int basd_vit_embed_bf16(const void* patches, const void* cls, const void* pos, const float* gamma, const float* beta,
+                        float eps, int B, int N, int D, void* out, void* stream);
 /* dx = LayerNorm backward (+ dres when given: the gradient that arrives through the residual connection of a pre-norm
  * block, so dx is the whole gradient of the block's residual stream); dbranch (nullable) = row_scale * dx, the
  * gradient of the branch input of basd_add_layernorm_fwd_bf16.  dgamma / dbeta are accumulated (nullable). */

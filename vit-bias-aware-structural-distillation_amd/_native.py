@@ -39,7 +39,7 @@ EXPORTS = (
     "basd_tap_grad_scatter", "basd_resample_tokens", "basd_resample_tokens_adjoint", "basd_procrustes_importance_bwd",
     "basd_conv3x3_bf16", "basd_conv7x7s2_relu_bf16", "basd_maxpool3x3s2_bf16", "basd_add_relu_bf16",
     "basd_sym_tridiag_f64_workspace_bytes", "basd_sym_tridiag_f64", "basd_tridiag_mp_rank",
-    "basd_window_attention_fwd_bf16", "basd_patch_merge_ln_bf16",
+    "basd_window_attention_fwd_bf16", "basd_patch_merge_ln_bf16", "basd_gemm_bf16_act", "basd_vit_embed_bf16",
 )
 
 
@@ -81,11 +81,13 @@ _SIGNATURES = {
     "basd_wgrad_workspace_bytes": (_I64, _I, _I),
     "basd_wgrad_bf16_ws": (_P, _P, _I64, _I, _I, _P, _P, _P, _I64, _P),
     "basd_gemm_bf16": (_P, _P, _P, _P, _I64, _I, _I, _I, _I, _P),
+    "basd_gemm_bf16_act": (_P, _P, _P, _P, _I64, _I, _I, _I, _I, _P),
     "basd_gemm_bf16_gelu_fwd": (_P, _P, _P, _P, _P, _I64, _I, _I, _I, _P),
     "basd_gemm_bf16x3_f32": (_P, _P, _P, _I64, _I, _I, _P),
     "basd_gemm_bf16_gelu_bwd": (_P, _P, _P, _P, _I64, _I, _I, _I, _P),
     "basd_layernorm_fwd_bf16": (_P, _P, _P, _I64, _I, _F, _P, _P, _P, _P),
     "basd_add_layernorm_fwd_bf16": (_P, _P, _P, _P, _I64, _I, _F, _P, _P, _P, _P, _P, _I, _P),
+    "basd_vit_embed_bf16": (_P, _P, _P, _P, _P, _F, _I, _I, _I, _P, _P),
     "basd_layernorm_bwd_bf16": (_P, _P, _P, _P, _P, _I64, _I, _P, _P, _P, _P, _P, _P, _I, _P),
     "basd_procrustes_bwd_rows": (_P, _P, _P, _P, _I64, _I, _I, _P, _I, _P, _P),
     "basd_cls_importance_bf16": (_P, _I, _I, _I, _I, _F, _P, _P),
@@ -905,11 +907,19 @@ def gemm_supported(n: int, k: int) -> bool:
     return k % 64 == 0 and k >= 64 and n >= 128 and (n % 256 == 0 or n % 192 == 0 or n % 128 == 0)
 
 
-def gemm_bf16(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None, gelu: bool = False) -> torch.Tensor:
+# activation names of gemm_bf16(act=...) -> ``act`` of basd_gemm_bf16_act (nn.GELU(), QuickGELU, nn.GELU("tanh"))
+GEMM_ACTS = {"gelu": 1, "quick_gelu": 2, "gelu_tanh": 3}
+
+
+def gemm_bf16(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None, gelu: bool = False,
+              act: str | None = None) -> torch.Tensor:
     """x [..., K], w [N, K], bias [N] | None (all bf16) -> epi(x w^T + bias) [..., N] bf16; epi = exact-erf GELU if
-    ``gelu``.  Inference / explicit-backward building block (no autograd)."""
+    ``gelu`` or ``act == "gelu"``, QuickGELU / tanh-GELU for ``act`` "quick_gelu" / "gelu_tanh" (basd_gemm_bf16_act).
+    Inference / explicit-backward building block (no autograd)."""
     _need_cuda(x, w, bias)
     assert x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and (bias is None or bias.dtype == torch.bfloat16)
+    if act is not None and act not in GEMM_ACTS:
+        raise BasdNativeError(f"gemm_bf16: unknown activation {act!r} (known: {sorted(GEMM_ACTS)})")
     k = x.shape[-1]
     n = w.shape[0]
     assert w.shape[1] == k and gemm_supported(n, k), (tuple(w.shape), k)
@@ -918,8 +928,13 @@ def gemm_bf16(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None
         x2 = x2.contiguous()
     w = w.contiguous()
     y = torch.empty(x2.shape[0], n, dtype=torch.bfloat16, device=x.device)
-    epi = 2 if gelu else (1 if bias is not None else 0)
-    _check(lib().basd_gemm_bf16(_ptr(x2), _ptr(w), _ptr(None if bias is None else bias.contiguous()), _ptr(y),
+    b = None if bias is None else bias.contiguous()
+    if act is not None and act != "gelu":
+        _check(lib().basd_gemm_bf16_act(_ptr(x2), _ptr(w), _ptr(b), _ptr(y), ctypes.c_int64(x2.shape[0]), n, k,
+                                        GEMM_ACTS[act], GEMM_TILE_RUN, _stream()), "basd_gemm_bf16_act")
+        return y.view(*x.shape[:-1], n)
+    epi = 2 if gelu or act == "gelu" else (1 if bias is not None else 0)
+    _check(lib().basd_gemm_bf16(_ptr(x2), _ptr(w), _ptr(b), _ptr(y),
                                 ctypes.c_int64(x2.shape[0]), n, k, epi, GEMM_TILE_RUN, _stream()), "basd_gemm_bf16")
     return y.view(*x.shape[:-1], n)
 
@@ -1140,6 +1155,33 @@ def layernorm_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps:
                                          d, ctypes.c_float(eps), _ptr(y), _ptr(mean), _ptr(rstd), _stream()),
            "basd_layernorm_fwd_bf16")
     return y, mean, rstd
+
+
+def vit_embed_supported(d: int) -> bool:
+    return layernorm_supported(d)
+
+
+def vit_embed(patches: torch.Tensor, cls: torch.Tensor | None, pos: torch.Tensor, gamma: torch.Tensor | None = None,
+              beta: torch.Tensor | None = None, eps: float = 1e-5) -> torch.Tensor:
+    """patches [B, N, D], cls [D] (any shape with D elements) | None, pos [T, D] (or [1, T, D]), T = N + (cls given),
+    all bf16 -> [B, T, D] bf16: the rows ``src + pos`` rounded to bf16 (torch's cat + add), layer-normalised when
+    gamma / beta (fp32 [D]) are given.  One launch (basd_vit_embed_bf16)."""
+    _need_cuda(patches, cls, pos, gamma, beta)
+    assert patches.dtype == torch.bfloat16 and pos.dtype == torch.bfloat16 and patches.dim() == 3
+    assert cls is None or cls.dtype == torch.bfloat16
+    assert (gamma is None) == (beta is None)
+    assert gamma is None or (gamma.dtype == torch.float32 and beta.dtype == torch.float32)
+    b, n, d = patches.shape
+    t = n + (cls is not None)
+    assert pos.numel() == t * d and (cls is None or cls.numel() == d), (tuple(pos.shape), t, d)
+    assert gamma is None or (gamma.numel() == d and beta.numel() == d)
+    patches, pos = patches.contiguous(), pos.contiguous()
+    out = torch.empty(b, t, d, dtype=torch.bfloat16, device=patches.device)
+    _check(lib().basd_vit_embed_bf16(_ptr(patches), _ptr(None if cls is None else cls.contiguous()), _ptr(pos),
+                                     _ptr(None if gamma is None else gamma.contiguous()),
+                                     _ptr(None if beta is None else beta.contiguous()), ctypes.c_float(eps), b, n, d,
+                                     _ptr(out), _stream()), "basd_vit_embed_bf16")
+    return out
 
 
 def add_layernorm_fwd(x: torch.Tensor, residual: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float,

@@ -1,5 +1,6 @@
 // Device-side bf16 / matrix-core helpers shared by the kernels: vector typedefs of the MFMA operands, fp32 <-> bf16
-// packing, and the MFMA fragments read from LDS through the gfx950 transposing read ds_read_b64_tr_b16.
+// packing, the row reduction of the LayerNorm-shaped kernels, and the MFMA fragments read from LDS through the gfx950
+// transposing read ds_read_b64_tr_b16.
 // A helper lives here once a second kernel file needs it; what only one file uses stays in that file.
 #pragma once
 #include "basd_common.h"
@@ -46,6 +47,31 @@ __device__ __forceinline__ unsigned int pack2(float a, float b) {
 }
 __device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
   return make_uint4(pack2(f[0], f[1]), pack2(f[2], f[3]), pack2(f[4], f[5]), pack2(f[6], f[7]));
+}
+
+// ---- row helpers of the LayerNorm-shaped kernels (layernorm.hip, vit_embed.hip): their results are compared bit for
+// bit, so both files reduce a row through this one summation order
+typedef unsigned int ln_u32x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ float round_bf16(float a) {
+  __hip_bfloat16 x = __float2bfloat16(a);
+  return bf16_bits_to_f32(*reinterpret_cast<unsigned short*>(&x));
+}
+
+// sum over the G lanes of a row group, result in every lane of the group
+template <int G>
+__device__ __forceinline__ float group_allsum(float v) {
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true));   // row_half_mirror
+  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true));   // row_mirror
+  ln_u32x2 r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  v = __uint_as_float(r.x) + __uint_as_float(r.y);                                                 // rows 0+1, 2+3
+  if (G == 64) {
+    r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    v = __uint_as_float(r.x) + __uint_as_float(r.y);
+  }
+  return v;
 }
 
 // Transposing LDS fragment reads from a row-major bf16 tile of row stride ld: two 4-row ds_read_b64_tr_b16.

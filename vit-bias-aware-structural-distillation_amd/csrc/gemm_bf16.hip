@@ -83,6 +83,36 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
   return fmaf(x * 0.3989422804014327f, e, 0.5f * (1.0f + copysignf(erf_abs, x)));
 }
 
+// The two other activations of the frozen teachers (basd_gemm_bf16_act; CLIP's QuickGELU and SigLIP's tanh-GELU).  Both
+// are x * sigmoid(s) -- for the tanh form because 0.5 (1 + tanh(u)) == sigmoid(2 u) exactly -- and are evaluated as
+//     x * v_rcp_f32(1 + v_exp_f32(-s * log2(e)))
+// with no tanh and no division.  v_exp_f32 (2^t) and v_rcp_f32 are each documented to 1 ulp (relative 2^-23); the sum
+// 1 + e and the products round to half an ulp.  The argument s carries the roundings of its own products (one for
+// QuickGELU, four for the cubic of the tanh form, plus the rounded constant): relative delta in s moves e by |s| delta,
+// and |x| sigma (1 - sigma) |s| <= 0.3 for both forms, so the argument's share stays below 2 units of 2^-24.  Altogether
+// |error| <= 8 * 2^-24 * max(1, |x|) before the single rounding to bf16 (the figure tests/test_gemm_act_gpu.py uses).
+// Saturation needs no clamp: s -> -inf gives 2^t = +inf, v_rcp_f32(+inf) = 0 and x * 0 = -0; s -> +inf gives 2^t = 0
+// (flushed) and x * 1 = x.  Neither form can overflow into a NaN for finite x: |x|^3 stays finite below 2^42.
+__device__ __forceinline__ float quick_gelu_fwd(float x) {
+  const float e = __builtin_amdgcn_exp2f(x * -2.4554669595930156f);          // -1.702 * log2(e)
+  return x * __builtin_amdgcn_rcpf(1.0f + e);
+}
+
+__device__ __forceinline__ float gelu_tanh_fwd(float x) {
+  // -2 sqrt(2 / pi) log2(e) (x + 0.044715 x^3)
+  const float t = x * fmaf(x * x, -0.10294324f, -2.3022082f);
+  const float e = __builtin_amdgcn_exp2f(t);
+  return x * __builtin_amdgcn_rcpf(1.0f + e);
+}
+
+template <int EPI>
+__device__ __forceinline__ float gemm_act(float v) {      // the forward activation of an epilogue without a saved tile
+  if (EPI == 2) return gelu_fwd(v);
+  if (EPI == 6) return quick_gelu_fwd(v);
+  if (EPI == 7) return gelu_tanh_fwd(v);
+  return v;
+}
+
 // Epilogue shared by both kernels.  The accumulator tile of a wave is [n][m] with 4 consecutive n per lane: stored
 // straight from registers that is an 8-byte store per (lane, tile), 16 rows x 32 B per wave instruction -- partial
 // lines, 18 us per 256 x 256 tile (as much as 13 K steps).  Instead every wave parks its 128 x (BN / 4) bf16 results
@@ -123,7 +153,7 @@ __device__ __forceinline__ void gemm_epilogue(f32x4 (&acc)[NT][8], unsigned char
   for (int i = 0; i < NT; ++i) {
     const int nl = i * 16 + 4 * (lane >> 4);       // local column of this lane's 4 values
     float bv[4] = {0.f, 0.f, 0.f, 0.f};
-    if ((EPI == 1 || EPI == 2 || EPI == 3) && bias != nullptr) {
+    if ((EPI == 1 || EPI == 2 || EPI == 3 || EPI == 6 || EPI == 7) && bias != nullptr) {
       const u16x4 b4 = *reinterpret_cast<const u16x4*>(bias + n0 + wn * WN + nl);
 #pragma unroll
       for (int r = 0; r < 4; ++r) bv[r] = bf16_bits_to_f32(b4[r]);
@@ -136,7 +166,7 @@ __device__ __forceinline__ void gemm_epilogue(f32x4 (&acc)[NT][8], unsigned char
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float v = acc[i][j][r] + bv[r];
-        if (EPI == 2) v = gelu_fwd(v);
+        if (EPI == 2 || EPI == 6 || EPI == 7) v = gemm_act<EPI>(v);
         if (EPI == 4) v *= gelu_erf_grad(bf16_bits_to_f32(pre[r]));
         o[r] = f32_to_bf16_bits(v);
       }
@@ -162,6 +192,7 @@ __device__ __forceinline__ void gemm_epilogue(f32x4 (&acc)[NT][8], unsigned char
 }
 
 // EPI: 0 = none, 1 = + bias, 2 = gelu(+ bias), 3 = aux <- (+ bias), y <- gelu(aux), 4 = y <- acc * gelu'(aux)
+// (5 = fp32 output of the bf16x3 product: persistent kernel only), 6 = QuickGELU(+ bias), 7 = tanh-GELU(+ bias)
 template <int BN, int EPI>
 __global__ __launch_bounds__(512) void gemm_bf16_nt_kernel(const unsigned short* __restrict__ X,
                                                            const unsigned short* __restrict__ W,
@@ -437,7 +468,7 @@ __device__ __forceinline__ void gemm_epilogue_direct(f32x4 (&acc)[4][8], const u
   for (int h = 0; h < 2; ++h)
 #pragma unroll
     for (int k = 0; k < 8; ++k) bv[h][k] = 0.f;
-  if ((EPI == 1 || EPI == 2 || EPI == 3) && bias != nullptr) {
+  if ((EPI == 1 || EPI == 2 || EPI == 3 || EPI == 6 || EPI == 7) && bias != nullptr) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const uint4 b8 = *reinterpret_cast<const uint4*>(bias + col0 + h * 32 + q * 8);
@@ -470,9 +501,9 @@ __device__ __forceinline__ void gemm_epilogue_direct(f32x4 (&acc)[4][8], const u
         float f[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) f[k] = v[2 * h + (k >> 2)][k & 3] + bv[h][k];
-        if (EPI == 2) {
+        if (EPI == 2 || EPI == 6 || EPI == 7) {
 #pragma unroll
-          for (int k = 0; k < 8; ++k) f[k] = gelu_fwd(f[k]);
+          for (int k = 0; k < 8; ++k) f[k] = gemm_act<EPI>(f[k]);
         }
         if (EPI == 4) {
           const uint4 p8 = *reinterpret_cast<const uint4*>(aux + off + h * 32);
@@ -820,6 +851,8 @@ static int gemm_dispatch(const void* x, const void* w, const void* bias, void* a
       case 1: LAUNCH(1); break;                                        \
       case 2: LAUNCH(2); break;                                        \
       case 3: LAUNCH(3); break;                                        \
+      case 6: LAUNCH(6); break;                                        \
+      case 7: LAUNCH(7); break;                                        \
       default: LAUNCH(4); break;                                       \
     }                                                                  \
   } while (0)
@@ -864,6 +897,15 @@ extern "C" int basd_gemm_bf16(const void* x, const void* w, const void* bias, vo
   if (epilogue < 0 || epilogue > 2) return fail(BASD_ERR_SHAPE, "gemm_bf16: epilogue %d not in {0, 1, 2}", epilogue);
   if (epilogue == 1 && bias == nullptr) epilogue = 0;
   return gemm_dispatch(x, w, bias, nullptr, y, M, N, K, epilogue, tile_run, stream, "gemm_bf16");
+}
+
+extern "C" int basd_gemm_bf16_act(const void* x, const void* w, const void* bias, void* y, int64_t M, int N, int K,
+                                  int act, int tile_run, void* stream) {
+  using namespace basd;
+  if (act < 0 || act > 3) return fail(BASD_ERR_SHAPE, "gemm_bf16_act: act %d not in {0, 1, 2, 3}", act);
+  // act -> EPI: none = + bias (or nothing), erf-GELU = the epilogue basd_gemm_bf16 runs, QuickGELU, tanh-GELU
+  const int epilogue = act == 0 ? (bias != nullptr ? 1 : 0) : act == 1 ? 2 : act == 2 ? 6 : 7;
+  return gemm_dispatch(x, w, bias, nullptr, y, M, N, K, epilogue, tile_run, stream, "gemm_bf16_act");
 }
 
 extern "C" int basd_gemm_bf16x3_f32(const void* x, const void* w3, float* y, int64_t M, int N, int K, void* stream) {

@@ -18,29 +18,6 @@
 
 namespace basd {
 
-typedef unsigned int ln_u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float round_bf16(float a) {
-  __hip_bfloat16 x = __float2bfloat16(a);
-  return bf16_bits_to_f32(*reinterpret_cast<unsigned short*>(&x));
-}
-
-// sum over the G lanes of a row group, result in every lane of the group
-template <int G>
-__device__ __forceinline__ float group_allsum(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true));   // row_half_mirror
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, true));   // row_mirror
-  ln_u32x2 r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = __uint_as_float(r.x) + __uint_as_float(r.y);                                                 // rows 0+1, 2+3
-  if (G == 64) {
-    r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(r.x) + __uint_as_float(r.y);
-  }
-  return v;
-}
-
 // FUSE_ADD: s = bf16(x + res) is written to `sum_out` and normalised; otherwise x is normalised.
 // U rows per group are in flight at a time (all their loads are issued before the first reduction): with one row per
 // group and iteration a CU holds ~18 KB of loads in flight and the narrow student rows (D = 192: 384 bytes) ran at

@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from ..losses.layer_selector import marchenko_pastur_rank, marchenko_pastur_rank_wide, mp_rank_route
-from .vit import VIT_PRESETS, create_vit
+from .vit import IMAGENET_MEAN, IMAGENET_STD, VIT_PRESETS, create_vit, vit_preset
 
 
 class TeacherModel(NamedTuple):
@@ -41,8 +41,7 @@ class TeacherModel(NamedTuple):
     std: tuple
 
 
-_IMAGENET_MEAN = (0.485, 0.456, 0.406)
-_IMAGENET_STD = (0.229, 0.224, 0.225)
+_IMAGENET_MEAN, _IMAGENET_STD = IMAGENET_MEAN, IMAGENET_STD
 
 
 _STAGE_CONTAINERS = ("blocks", "layers", "stages")
@@ -147,20 +146,27 @@ def _probe_scope(model: nn.Module):
 
 
 def load_teacher(model_name: str, img_size: int, *, weights: str | None = None, device="cuda",
-                 seed: int = 42, patch_size: int | None = None, dtype=torch.bfloat16) -> TeacherModel:
+                 seed: int = 42, patch_size: int | None = None, dtype=torch.bfloat16, act: str | None = None,
+                 norm_eps: float | None = None) -> TeacherModel:
     """Build (not download: reference teacher.py:113-148 fetches from the network) the named teacher -- a ViT preset of
     ``models/vit.py`` or a feature-map preset of ``models/cnn.py`` (ResNet, ConvNeXt-V2 and the Swin family of
     ``models/swin.py``) -- frozen, in eval mode, weights pre-cast to bf16; ``weights`` = a local state dict (timm /
-    torchvision parameter names)."""
+    torchvision parameter names).  The returned ``mean`` / ``std`` are the preset's (the reference reads them from
+    timm's ``pretrained_cfg``, teacher.py:119-120): CLIP's own statistics, 0.5 / 0.5 for SigLIP, ImageNet's otherwise.
+    ``act`` / ``norm_eps`` override a ViT preset's MLP activation and LayerNorm epsilon."""
     from .cnn import CNN_PRESETS, create_cnn
-    if model_name not in VIT_PRESETS and model_name not in CNN_PRESETS and model_name.split(".", 1)[0] in CNN_PRESETS:
-        model_name = model_name.split(".", 1)[0]      # timm's pretrained tag ("convnextv2_tiny.fcmae"): weights are local
+    base = model_name.split(".", 1)[0]
+    if model_name not in VIT_PRESETS and model_name not in CNN_PRESETS and (base in CNN_PRESETS or base in VIT_PRESETS):
+        model_name = base      # timm's pretrained tag ("convnextv2_tiny.fcmae", "..._clip_224.openai"): weights are local
     gen_state = torch.random.get_rng_state()
     torch.manual_seed(seed)
     if model_name in VIT_PRESETS:
-        model = create_vit(model_name, num_classes=0, img_size=img_size, patch_size=patch_size)
+        model = create_vit(model_name, num_classes=0, img_size=img_size, patch_size=patch_size, act=act,
+                           norm_eps=norm_eps)
+        mean, std = vit_preset(model_name).mean, vit_preset(model_name).std
     elif model_name in CNN_PRESETS:
         model = create_cnn(model_name)
+        mean, std = _IMAGENET_MEAN, _IMAGENET_STD
     else:
         raise ValueError(f"teacher {model_name!r}: not a known preset ({sorted(VIT_PRESETS) + sorted(CNN_PRESETS)}); "
                          "wrap your own module in TeacherModel(...) with the fields probe_model() returns")
@@ -185,7 +191,7 @@ def load_teacher(model_name: str, img_size: int, *, weights: str | None = None, 
     return TeacherModel(model=model, embed_dim=info["embed_dim"], heads_per_layer=info["heads_per_layer"],
                         depth=info["depth"], mlp_ratio=info["mlp_ratio"], layer_paths=info["layer_paths"],
                         attn_subpath=info["attn_subpath"], has_cls_token=info["has_cls_token"],
-                        feature_format=info["feature_format"], mean=_IMAGENET_MEAN, std=_IMAGENET_STD)
+                        feature_format=info["feature_format"], mean=mean, std=std)
 
 
 def _to_token_format(t: torch.Tensor, feature_format: str, has_cls_token: bool) -> torch.Tensor:

@@ -19,11 +19,19 @@ that has to take a PyTorch-ROCm library kernel instead is counted in
 ``losses._ops.FALLBACKS`` (an error in strict mode).  Parity of the ViT
 arithmetic itself is UNPINNED by the reference (it has no tests and timm is
 absent) -- see DESIGN.md.
+
+The image-text teachers (timm's CLIP and SigLIP ViTs) are the same model with three switches: ``pre_norm`` (a LayerNorm
+on the assembled tokens in front of block 0, patch embedding without bias), the MLP activation ``act`` ("gelu",
+"quick_gelu", "gelu_tanh") and ``norm_eps``.  They exist for FROZEN teachers: the activation rides in the fc1 GEMM's
+epilogue (``basd_gemm_bf16_act``) and the token assembly + ``norm_pre`` is one kernel (``basd_vit_embed_bf16``).  A
+TRAINED block with a non-erf activation has no backward epilogue: it takes the unfused path and is counted as a library
+fallback -- students with these activations or with ``pre_norm`` are out of scope.
 """
 from __future__ import annotations
 
 import math
 import os
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -215,6 +223,9 @@ class _FusedAttention(torch.autograd.Function):
 
 
 _FUSED_TEACHER_ATTENTION = os.environ.get("BASD_FUSED_ATTN", "1") == "1"     # 0: library SDPA + separate tap (A/B runs)
+# 0: QuickGELU / tanh-GELU as a torch op behind a bias-only GEMM, torch token assembly + norm_pre (A/B runs:
+# scripts/time_clip_teacher.py flips it inside one process)
+_FUSED_CLIP_DISPATCH = os.environ.get("BASD_FUSED_CLIP", "1") == "1"
 _packed_attention_ok = True      # cleared on the first failure of the direct library call (other torch builds)
 
 
@@ -293,17 +304,38 @@ class Attention(nn.Module):
         return attn.mean(dim=(1, 2))
 
 
+class QuickGELU(nn.Module):
+    """x * sigmoid(1.702 x): the activation of the OpenAI-weight CLIP towers (timm ``quick_gelu``)"""
+
+    def forward(self, x):
+        return x * torch.sigmoid(1.702 * x)
+
+
+MLP_ACTS = ("gelu", "quick_gelu", "gelu_tanh")
+
+
 class Mlp(nn.Module):
-    def __init__(self, dim: int, hidden: int):
+    """timm Mlp.  ``act``: "gelu" (exact erf), "quick_gelu" or "gelu_tanh".  Only the erf form has a backward epilogue:
+    a TRAINED Mlp with another activation runs unfused (a counted library fallback, an error in strict mode)."""
+
+    def __init__(self, dim: int, hidden: int, act: str = "gelu"):
         super().__init__()
+        if act not in MLP_ACTS:
+            raise ValueError(f"Mlp: unknown activation {act!r}; known: {MLP_ACTS}")
+        self.act_name = act
         self.fc1 = BasdLinear(dim, hidden)
-        self.act = nn.GELU()
+        self.act = nn.GELU() if act == "gelu" else nn.GELU(approximate="tanh") if act == "gelu_tanh" else QuickGELU()
         self.fc2 = BasdLinear(hidden, dim)
 
     def forward(self, x):
-        if self.fc1.fused_inference_ok(x):        # frozen block: exact-erf GELU in the epilogue of the fc1 GEMM
-            return self.fc2(get_ops().gemm_bf16(x, self.fc1.weight, self.fc1.bias, gelu=True))
-        if fused_mlp_ok(x, self.fc1, self.fc2):   # trained block: GELU forward / backward inside the GEMM epilogues
+        if self.fc1.fused_inference_ok(x):        # frozen block: the activation in the epilogue of the fc1 GEMM
+            if self.act_name == "gelu":
+                return self.fc2(get_ops().gemm_bf16(x, self.fc1.weight, self.fc1.bias, gelu=True))
+            if _FUSED_CLIP_DISPATCH:
+                return self.fc2(get_ops().gemm_bf16(x, self.fc1.weight, self.fc1.bias, act=self.act_name))
+            return self.fc2(self.act(self.fc1(x)))
+        # trained block: GELU forward / backward inside the GEMM epilogues (exact erf only)
+        if self.act_name == "gelu" and fused_mlp_ok(x, self.fc1, self.fc2):
             return fused_mlp(x, self.fc1, self.fc2)
         if get_ops().handles(x):
             library_fallback("MLP GELU", f"fc1 {self.fc1.in_features}->{self.fc1.out_features} dtype={x.dtype}")
@@ -311,14 +343,14 @@ class Mlp(nn.Module):
 
 
 class Block(nn.Module):
-    def __init__(self, dim, num_heads, mlp_ratio=4.0, drop_path=0.0, init_values=None, eps=1e-6):
+    def __init__(self, dim, num_heads, mlp_ratio=4.0, drop_path=0.0, init_values=None, eps=1e-6, act="gelu"):
         super().__init__()
         self.norm1 = MixedLayerNorm(dim, eps=eps)
         self.attn = Attention(dim, num_heads)
         self.ls1 = LayerScale(dim, init_values) if init_values else nn.Identity()
         self.drop_path1 = DropPath(drop_path)
         self.norm2 = MixedLayerNorm(dim, eps=eps)
-        self.mlp = Mlp(dim, int(dim * mlp_ratio))
+        self.mlp = Mlp(dim, int(dim * mlp_ratio), act)
         self.ls2 = LayerScale(dim, init_values) if init_values else nn.Identity()
         self.drop_path2 = DropPath(drop_path)
 
@@ -420,11 +452,11 @@ class Block(nn.Module):
 
 
 class PatchEmbed(nn.Module):
-    def __init__(self, img_size, patch_size, in_chans, embed_dim):
+    def __init__(self, img_size, patch_size, in_chans, embed_dim, bias=True):
         super().__init__()
         self.img_size, self.patch_size = img_size, patch_size
         self.num_patches = (img_size // patch_size) ** 2
-        self.proj = nn.Conv2d(in_chans, embed_dim, kernel_size=patch_size, stride=patch_size)
+        self.proj = nn.Conv2d(in_chans, embed_dim, kernel_size=patch_size, stride=patch_size, bias=bias)
 
     def forward(self, x):
         # non-overlapping patches: the stride-p convolution IS a GEMM on unfolded patches
@@ -437,7 +469,7 @@ class PatchEmbed(nn.Module):
         ops = get_ops()
         trained = torch.is_grad_enabled() and self.proj.weight.requires_grad
         if ops.handles(x) and self._bf16_compute(x) and ops.gemm_supported(d, k) and (
-                not trained or ops.wgrad_supported(d, k)) and self.proj.bias is not None:
+                not trained or ops.wgrad_supported(d, k)) and (self.proj.bias is not None or self._frozen_bf16_no_bias()):
             # own GEMM (forward) / split-M weight gradient; the unfold and the cast to bf16 are ONE copy kernel
             patches = torch.empty(b, (h // p) * (w // p), k, dtype=torch.bfloat16, device=x.device)
             patches.view(b, h // p, w // p, c, p, p).copy_(unfolded)
@@ -445,13 +477,14 @@ class PatchEmbed(nn.Module):
             if trained:
                 with torch.autocast(device_type=x.device.type, enabled=False):
                     return _LinearFn.apply(patches, w2, self.proj.bias)
-            if not torch.is_grad_enabled() and w2.dtype == torch.bfloat16 and self.proj.bias.dtype == torch.bfloat16:
+            if not torch.is_grad_enabled() and w2.dtype == torch.bfloat16 and (
+                    self.proj.bias is None or self.proj.bias.dtype == torch.bfloat16):
                 return ops.gemm_bf16(patches, w2, self.proj.bias)
             library_fallback("patch embedding", f"K={k} D={d}: bf16 compute of fp32 frozen weights")
             return F.linear(patches, w2.to(torch.bfloat16), self.proj.bias.to(torch.bfloat16))
         k_pad = (k + 63) // 64 * 64
         if (ops.handles(x) and not torch.is_grad_enabled() and self.proj.weight.dtype == torch.bfloat16
-                and self.proj.bias is not None and self.proj.bias.dtype == torch.bfloat16 and ops.gemm_supported(d, k_pad)):
+                and (self.proj.bias is None or self.proj.bias.dtype == torch.bfloat16) and ops.gemm_supported(d, k_pad)):
             # frozen bf16 layer whose patch is not a multiple of 64 values (ViT-H/14: 3 x 14 x 14 = 588): K padded with
             # zero columns on both operands (the padded weight is kept: the layer is frozen)
             patches = torch.zeros(b, (h // p) * (w // p), k_pad, dtype=torch.bfloat16, device=x.device)
@@ -474,6 +507,10 @@ class PatchEmbed(nn.Module):
         if ops.handles(x):
             library_fallback("patch embedding", f"K={k} D={d} dtype={x.dtype}")
         return F.linear(unfolded.reshape(b, -1, k), self.proj.weight.reshape(d, -1), self.proj.bias)
+
+    def _frozen_bf16_no_bias(self) -> bool:
+        """the patch embedding of a frozen pre-norm teacher (CLIP: ``norm_pre`` carries the offset)"""
+        return (self.proj.bias is None and not torch.is_grad_enabled() and self.proj.weight.dtype == torch.bfloat16)
 
     def _bf16_compute(self, x) -> bool:
         if self.proj.weight.dtype == torch.bfloat16:
@@ -527,18 +564,21 @@ def _matrix_view(weight: torch.Tensor) -> torch.Tensor:
 
 class VisionTransformer(nn.Module):
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dim=768, depth=12,
-                 num_heads=12, mlp_ratio=4.0, drop_path_rate=0.0, init_values=None, class_token=True):
+                 num_heads=12, mlp_ratio=4.0, drop_path_rate=0.0, init_values=None, class_token=True,
+                 pre_norm=False, act="gelu", norm_eps=1e-6):
         super().__init__()
         self.embed_dim = self.num_features = embed_dim
         self.num_classes = num_classes
-        self.patch_embed = PatchEmbed(img_size, patch_size, in_chans, embed_dim)
+        self.patch_embed = PatchEmbed(img_size, patch_size, in_chans, embed_dim, bias=not pre_norm)
         n = self.patch_embed.num_patches
         self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim)) if class_token else None
         self.pos_embed = nn.Parameter(torch.randn(1, n + int(class_token), embed_dim) * 0.02)
         dpr = [drop_path_rate * i / max(depth - 1, 1) for i in range(depth)]
         self.blocks = nn.ModuleList([
-            Block(embed_dim, num_heads, mlp_ratio, dpr[i], init_values) for i in range(depth)])
-        self.norm = MixedLayerNorm(embed_dim, eps=1e-6)
+            Block(embed_dim, num_heads, mlp_ratio, dpr[i], init_values, eps=norm_eps, act=act) for i in range(depth)])
+        self.norm = MixedLayerNorm(embed_dim, eps=norm_eps)
+        # timm's name; None (not nn.Identity) without pre_norm: the module tree of every other model stays as it was
+        self.norm_pre = MixedLayerNorm(embed_dim, eps=norm_eps) if pre_norm else None
         for i, blk in enumerate(self.blocks):
             blk._next_norm.append(self.blocks[i + 1].norm1 if i + 1 < depth else self.norm)
         self.head = nn.Linear(embed_dim, num_classes) if num_classes > 0 else nn.Identity()
@@ -564,7 +604,7 @@ class VisionTransformer(nn.Module):
         pe, p = self.patch_embed, self.patch_embed.patch_size
         w = pe.proj.weight
         t = self.pos_embed.shape[1]
-        return (pe.proj.bias is not None and w.dtype == torch.float32 and pe.proj.bias.dtype == torch.float32
+        return (self.norm_pre is None and pe.proj.bias is not None and w.dtype == torch.float32 and pe.proj.bias.dtype == torch.float32
                 and w.is_contiguous() and x.shape[2] % p == 0 and x.shape[3] % p == 0
                 and (x.shape[2] // p) * (x.shape[3] // p) + int(self.cls_token is not None) == t
                 and ops.f32x3_gemm_supported(self.embed_dim, _pad32(w[0].numel()))
@@ -601,9 +641,17 @@ class VisionTransformer(nn.Module):
         if self._f32x3_ok(x):
             return self._forward_features_f32x3(x)
         x = self.patch_embed(x)
-        if self.cls_token is not None:
-            x = torch.cat([self.cls_token.expand(x.shape[0], -1, -1).to(x.dtype), x], dim=1)
-        x = x + self.pos_embed.to(x.dtype)
+        if self._fused_embed_ok(x):
+            # frozen pre-norm teacher: CLS row, position embedding and norm_pre in one kernel (csrc/vit_embed.hip)
+            n = self.norm_pre
+            x = get_ops().vit_embed(x, self.cls_token, self.pos_embed, n.weight.detach().float(),
+                                    n.bias.detach().float(), n.eps)
+        else:
+            if self.cls_token is not None:
+                x = torch.cat([self.cls_token.expand(x.shape[0], -1, -1).to(x.dtype), x], dim=1)
+            x = x + self.pos_embed.to(x.dtype)
+            if self.norm_pre is not None:
+                x = self.norm_pre(x)
         masks = self._draw_drop_path_masks(x)
         for i, blk in enumerate(self.blocks):
             dp = None if masks is None else (masks[0][2 * i], masks[0][2 * i + 1], masks[1][2 * i], masks[1][2 * i + 1])
@@ -612,6 +660,15 @@ class VisionTransformer(nn.Module):
             else:
                 x = blk(x, dp)
         return self.norm(x)
+
+    def _fused_embed_ok(self, x) -> bool:
+        """frozen bf16 model with ``norm_pre`` on the device; every model without it keeps the torch assembly"""
+        n, cls = self.norm_pre, self.cls_token
+        return (n is not None and _FUSED_CLIP_DISPATCH and not torch.is_grad_enabled() and x.dtype == torch.bfloat16
+                and x.dim() == 3 and get_ops().handles(x) and n.elementwise_affine
+                and self.pos_embed.dtype == torch.bfloat16 and (cls is None or cls.dtype == torch.bfloat16)
+                and x.shape[1] + int(cls is not None) == self.pos_embed.shape[1]
+                and get_ops().vit_embed_supported(x.shape[-1]))
 
     def _draw_drop_path_masks(self, x):
         """All 2 * depth stochastic-depth masks of one forward from ONE bernoulli launch (timm draws one per
@@ -635,7 +692,30 @@ class VisionTransformer(nn.Module):
         return self.head(x)
 
 
-# name -> (embed_dim, depth, heads, patch, layerscale init)
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+CLIP_MEAN, CLIP_STD = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)
+HALF_MEAN, HALF_STD = (0.5, 0.5, 0.5), (0.5, 0.5, 0.5)
+
+
+class ViTPreset(NamedTuple):
+    embed_dim: int
+    depth: int
+    heads: int
+    patch: int
+    layerscale: float | None
+    pre_norm: bool = False
+    act: str = "gelu"
+    class_token: bool = True
+    norm_eps: float = 1e-6
+    mean: tuple = IMAGENET_MEAN          # pretrained_cfg["mean"] / ["std"] of the timm model: the statistics that
+    std: tuple = IMAGENET_STD            # normalise the teacher's clean view
+
+
+# name -> (embed_dim, depth, heads, patch, layerscale init[, pre_norm, act, class_token, norm_eps, mean, std])
+# The CLIP / SigLIP rows were written WITHOUT timm at hand, from memory of timm 1.0.x (vision_transformer.py model
+# entrypoints and default_cfgs): check them against the installed timm before loading real weights, and override with
+# load_teacher(..., act=..., norm_eps=...) where they differ.  SigLIP's attention-pool head (attn_pool.*) is not built:
+# the teacher never uses a head, and load_state_dict(strict=False) drops those keys.
 VIT_PRESETS = {
     "deit_tiny_patch16_224": (192, 12, 3, 16, None),
     "deit_small_patch16_224": (384, 12, 6, 16, None),
@@ -648,17 +728,31 @@ VIT_PRESETS = {
     "dinov2_vits14": (384, 12, 6, 14, 1.0),
     "dinov2_vitb14": (768, 12, 12, 14, 1.0),
     "dinov2_vitl14": (1024, 24, 16, 14, 1.0),
+    "vit_base_patch32_clip_224": (768, 12, 12, 32, None, True, "gelu", True, 1e-5, CLIP_MEAN, CLIP_STD),
+    "vit_base_patch16_clip_224": (768, 12, 12, 16, None, True, "gelu", True, 1e-5, CLIP_MEAN, CLIP_STD),
+    "vit_large_patch14_clip_224": (1024, 24, 16, 14, None, True, "gelu", True, 1e-5, CLIP_MEAN, CLIP_STD),
+    "vit_base_patch16_clip_quickgelu_224": (768, 12, 12, 16, None, True, "quick_gelu", True, 1e-5, CLIP_MEAN, CLIP_STD),
+    "vit_large_patch14_clip_quickgelu_224": (1024, 24, 16, 14, None, True, "quick_gelu", True, 1e-5, CLIP_MEAN, CLIP_STD),
+    "vit_base_patch16_siglip_224": (768, 12, 12, 16, None, False, "gelu_tanh", False, 1e-6, HALF_MEAN, HALF_STD),
 }
 
 
-def create_vit(name: str, *, num_classes: int, img_size: int, drop_path_rate: float = 0.0,
-               patch_size: int | None = None, **overrides) -> VisionTransformer:
-    """timm.create_model stand-in for the presets above; ``overrides`` are the reference's
-    ``model.arch_overrides`` keys (embed_dim, depth, num_heads, mlp_ratio; src/train.py:57-66)."""
+def vit_preset(name: str) -> ViTPreset:
+    """the preset's full record (the short rows above take the defaults of a plain ImageNet ViT)"""
     if name not in VIT_PRESETS:
         raise ValueError(f"unknown ViT preset {name!r}; known: {sorted(VIT_PRESETS)}")
-    dim, depth, heads, patch, ls = VIT_PRESETS[name]
-    kw = dict(embed_dim=dim, depth=depth, num_heads=heads, mlp_ratio=4.0)
+    return ViTPreset(*VIT_PRESETS[name])
+
+
+def create_vit(name: str, *, num_classes: int, img_size: int, drop_path_rate: float = 0.0,
+               patch_size: int | None = None, act: str | None = None, norm_eps: float | None = None,
+               **overrides) -> VisionTransformer:
+    """timm.create_model stand-in for the presets above; ``overrides`` are the reference's
+    ``model.arch_overrides`` keys (embed_dim, depth, num_heads, mlp_ratio; src/train.py:57-66); ``act`` / ``norm_eps``
+    replace the preset's MLP activation / LayerNorm epsilon."""
+    ps = vit_preset(name)
+    kw = dict(embed_dim=ps.embed_dim, depth=ps.depth, num_heads=ps.heads, mlp_ratio=4.0)
     kw.update({k: v for k, v in overrides.items() if k in ("embed_dim", "depth", "num_heads", "mlp_ratio")})
-    return VisionTransformer(img_size=img_size, patch_size=patch_size or patch, num_classes=num_classes,
-                             drop_path_rate=drop_path_rate, init_values=ls, **kw)
+    return VisionTransformer(img_size=img_size, patch_size=patch_size or ps.patch, num_classes=num_classes,
+                             drop_path_rate=drop_path_rate, init_values=ps.layerscale, class_token=ps.class_token,
+                             pre_norm=ps.pre_norm, act=act or ps.act, norm_eps=norm_eps or ps.norm_eps, **kw)
