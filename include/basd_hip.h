@@ -60,6 +60,9 @@
  *   basd_attention_fwd_long_bf16, basd_attention_bwd_long_bf16
  *                          the same forward (with both taps) and backward for 1 <= T <= 1024 tokens (hd 64 | 80):
  *                          /14 grids, 384 px inputs and hd-80 students, where the kernels above refuse the shape
+ *   basd_attention_fwd_relbias_bf16
+ *                          timm Beit Attention.forward of a frozen BEiT / BEiT-v2 teacher (learned relative-position
+ *                          bias on the logits, teacher.py:118 creates it) with the CLS-row tap
  *   basd_layernorm_fwd_bf16 / _bwd_bf16, basd_add_layernorm_fwd_bf16
  *                          timm nn.LayerNorm of the ViT blocks (student: with backward; frozen teacher: fused with
  *                          the residual add in front of it)
@@ -476,6 +479,22 @@ int basd_attention_fwd_bf16(const void* qkv, int B, int T, int H, int hd, float 
  * sum_q softmax(q . k * scale)[q][key] / (H T) -- the tap is the sum over the H axis.  Same shapes as above. */
 int basd_attention_fwd_qmean_bf16(const void* qkv, int B, int T, int H, int hd, float scale, void* out,
                                   float* importance, void* stream);
+
+/* The same forward for a frozen block whose attention carries BEiT's learned relative-position bias (timm Beit /
+ * BEiT-v2 Attention.forward): qkv [B, T, 3, H, hd] bf16 with the CLS token first, T = gh * gw + 1 -> out [B, T, H * hd]
+ * bf16 = softmax(Q K^T * scale + bias) V per head.  table: fp32 [R, H], R = (2 gh - 1)(2 gw - 1) + 3 -- timm's
+ * relative_position_bias_table, heads on the fast axis.  Logit of query i and key j:
+ *   fp32(q_i . k_j) * scale + table[idx(i, j)][h],
+ *   idx = (y_i - y_j + gh - 1)(2 gw - 1) + (x_i - x_j + gw - 1)   both patches, patch p at (y, x) = ((p - 1) / gw, (p - 1) % gw)
+ *   idx = R - 3 (i == 0, j >= 1),  R - 2 (i >= 1, j == 0),  R - 1 (i == j == 0).
+ * The bias is gathered in the kernel from the head's column of the table (staged in LDS): no [T, T] or [H, T, T] array
+ * is read or written.  importance (nullable): [B, H, T-1] fp32; receives per head the CLS row of that biased softmax
+ * (fp32 logits) without the CLS column, divided by H (the tap is the sum over the H axis).  Arithmetic otherwise as
+ * basd_attention_fwd_bf16: bf16 products with fp32 accumulation, fp32 logits and softmax (maximum subtracted), P rounded
+ * to bf16 for the second product, one rounding at the store.  hd == 64, gh, gw >= 1, 2 <= T <= 272; anything else is
+ * BASD_ERR_SHAPE without a launch.  No allocation, no synchronisation. */
+int basd_attention_fwd_relbias_bf16(const void* qkv, const float* table, int B, int gh, int gw, int H, int hd,
+                                    float scale, void* out, float* importance, void* stream);
 
 /* Fused attention backward of a trained block (the student; reference src/training/trainer.py:157 through timm
  * Attention.forward): qkv [B, T, 3, H, hd] bf16, out / dout [B, T, H * hd] bf16 (forward output and its gradient),

@@ -40,6 +40,7 @@ EXPORTS = (
     "basd_conv3x3_bf16", "basd_conv7x7s2_relu_bf16", "basd_maxpool3x3s2_bf16", "basd_add_relu_bf16",
     "basd_sym_tridiag_f64_workspace_bytes", "basd_sym_tridiag_f64", "basd_tridiag_mp_rank",
     "basd_window_attention_fwd_bf16", "basd_patch_merge_ln_bf16", "basd_gemm_bf16_act", "basd_vit_embed_bf16",
+    "basd_attention_fwd_relbias_bf16",
 )
 
 
@@ -93,6 +94,7 @@ _SIGNATURES = {
     "basd_cls_importance_bf16": (_P, _I, _I, _I, _I, _F, _P, _P),
     "basd_attention_fwd_bf16": (_P, _I, _I, _I, _I, _F, _P, _P, _P, _P),
     "basd_attention_fwd_qmean_bf16": (_P, _I, _I, _I, _I, _F, _P, _P, _P),
+    "basd_attention_fwd_relbias_bf16": (_P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P),
     "basd_attention_bwd_bf16": (_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P),
     "basd_attention_fwd_long_bf16": (_P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P),
     "basd_attention_bwd_long_workspace_bytes": (_I, _I, _I, _I),
@@ -1104,6 +1106,46 @@ def _attention_fwd_long(qkv, out, heads, head_dim, scale, want_importance, want_
         return out, qm.sum(dim=1)
     imp = cls.sum(dim=1) if cls is not None else None
     return (out, imp, lse) if want_lse else (out, imp)
+
+
+def relbias_index(i: int, j: int, gh: int, gw: int) -> int:
+    """Row of BEiT's ``relative_position_bias_table`` ([(2 gh - 1)(2 gw - 1) + 3, H]) that biases the logit of query
+    token i and key token j (token 0 = CLS, patch p at (y, x) = ((p - 1) // gw, (p - 1) % gw)): the closed form the
+    kernel of ``attention_fwd_relbias`` evaluates per logit (csrc/attention.hip, RELBIAS).  Written from memory of
+    timm's ``beit.py`` (``gen_relative_position_index``), without timm at hand: check it against the
+    ``relative_position_index`` buffer of the installed timm before loading real weights."""
+    rows = (2 * gh - 1) * (2 * gw - 1) + 3
+    if i == 0:
+        return rows - 1 if j == 0 else rows - 3
+    if j == 0:
+        return rows - 2
+    yi, xi = divmod(i - 1, gw)
+    yj, xj = divmod(j - 1, gw)
+    return (yi - yj + gh - 1) * (2 * gw - 1) + (xi - xj + gw - 1)
+
+
+def attention_fwd_relbias_supported(gh: int, gw: int, hd: int) -> bool:
+    """the range of ``basd_attention_fwd_relbias_bf16``: the short kernel's token count, head dim 64"""
+    return hd == 64 and gh >= 1 and gw >= 1 and gh * gw + 1 <= 272
+
+
+def attention_fwd_relbias(qkv: torch.Tensor, table: torch.Tensor, gh: int, gw: int, heads: int, head_dim: int,
+                          scale: float, want_importance: bool = False):
+    """qkv [B, gh * gw + 1, 3 * heads * head_dim] bf16 (CLS token first), table [(2 gh - 1)(2 gw - 1) + 3, heads] fp32
+    (timm's ``relative_position_bias_table``) -> (out [B, T, heads * head_dim] bf16, importance | None) with
+    softmax(q k^T * scale + table[relbias_index(i, j)]) per head; importance: the CLS row of the head-averaged biased
+    map without its first entry, [B, T-1] fp32.  The bias is gathered inside the kernel: nothing [T, T] is built."""
+    _need_cuda(qkv, table)
+    b, t = qkv.shape[0], qkv.shape[1]
+    assert qkv.dtype == torch.bfloat16 and qkv.shape[-1] == 3 * heads * head_dim and t == gh * gw + 1
+    assert table.dtype == torch.float32 and tuple(table.shape) == ((2 * gh - 1) * (2 * gw - 1) + 3, heads)
+    qkv, table = qkv.contiguous(), table.contiguous()
+    out = torch.empty(b, t, heads * head_dim, dtype=torch.bfloat16, device=qkv.device)
+    imp = torch.empty(b, heads, t - 1, dtype=torch.float32, device=qkv.device) if want_importance else None
+    _check(lib().basd_attention_fwd_relbias_bf16(_ptr(qkv), _ptr(table), b, gh, gw, heads, head_dim,
+                                                 ctypes.c_float(scale), _ptr(out), _ptr(imp), _stream()),
+           "basd_attention_fwd_relbias_bf16")
+    return out, (imp.sum(dim=1) if want_importance else None)
 
 
 def _short_attention_bwd_ok(t: int, hd: int) -> bool:

@@ -36,10 +36,24 @@ template <int CTRL> __device__ __forceinline__ float at_dpp_add(float v) {
 // QMEAN: the tap of a teacher WITHOUT a CLS token (reference src/losses/relational.py:25-27: the attention map averaged
 // over heads AND queries): importance[b, h, key] = sum_q P[q][key] / (H T) from the probabilities of the main softmax
 // (fp32 logits, as the torch form of this tap used before), [B, H, T]; the caller sums over h as for the CLS tap.
-template <int NKT, int AT_HD, bool QMEAN = false>   // key tiles of 16: T <= 16 * NKT; head dim 64 or 80
+//
+// RELBIAS: BEiT's learned relative-position bias (basd_attention_fwd_relbias_bf16): the logit of query i and key j is
+// fp32(q_i . k_j) * scale + table[idx(i, j)][h].  No [T, T] bias exists anywhere: the head's column of the table
+// (R = (2 gh - 1)(2 gw - 1) + 3 floats) is staged in LDS next to koff[key] = y_k (2 gw - 1) + x_k of every patch key, and
+// a lane forms idx = (y_q + gh - 1)(2 gw - 1) + x_q + gw - 1 - koff[key] per logit (one division per lane and query
+// tile); a CLS query reads row R - 3 (R - 1 against the CLS key), a patch query row R - 2 against the CLS key.  The tap is
+// row 0 of the main softmax (fp32 logits, bias included), not the bf16-rounded side computation of the plain kernel.
+struct RelBias {
+  const float* table;                                // [R, H] fp32, heads on the fast axis
+  int gh, gw;                                        // patch grid: T = gh * gw + 1, CLS token first
+};
+
+template <int NKT, int AT_HD, bool QMEAN = false, bool RELBIAS = false>   // key tiles of 16: T <= 16 * NKT; head dim 64 or 80
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void attention_fwd_kernel(const unsigned short* __restrict__ qkv, int T, int H,
                                                             float scale, unsigned short* __restrict__ out,
-                                                            float* __restrict__ importance, float* __restrict__ lse) {
+                                                            float* __restrict__ importance, float* __restrict__ lse,
+                                                            RelBias rb) {
+  static_assert(!(QMEAN && RELBIAS), "the relative-position bias comes with the CLS tap only");
   constexpr int NKS = (NKT + 1) / 2;                 // 32-key steps of the P V product
   constexpr int KROWS = 32 * NKS;                    // LDS rows (zero padded)
   constexpr int NDS = (AT_HD + 31) / 32;             // 32-deep steps of the Q K^T contraction
@@ -51,6 +65,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   unsigned short* Ks = sm;                           // [KROWS][AT_LD]
   unsigned short* Vs = Ks + KROWS * AT_LD;           // [KROWS][AT_LD]
   unsigned short* Os = Vs + KROWS * AT_LD;           // [4 waves][16][AT_LD]
+  int* koff = reinterpret_cast<int*>(Os + 4 * 16 * AT_LD);   // RELBIAS: [KROWS] key offsets, then the table column [R]
+  float* tab = reinterpret_cast<float*>(koff + KROWS);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 15, g = lane >> 4;
   const int b = blockIdx.x / H, h = blockIdx.x - b * H;
@@ -74,6 +90,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       vreg[i] = *reinterpret_cast<const uint4*>(p + (size_t)2 * H * AT_HD);
     }
   }
+  const int R = RELBIAS ? (2 * rb.gh - 1) * (2 * rb.gw - 1) + 3 : 0;
+  const int rl = RELBIAS ? 2 * rb.gw - 1 : 0;        // table rows per step in y
+  if constexpr (RELBIAS) {
+    constexpr int NTAB = (1084 + 255) / 256;         // R <= 1084 for gh * gw <= 271
+    float tv[NTAB];
+#pragma unroll
+    for (int i = 0; i < NTAB; ++i) tv[i] = (tid + 256 * i < R) ? rb.table[(size_t)(tid + 256 * i) * H + h] : 0.f;
+#pragma unroll
+    for (int i = 0; i < NTAB; ++i)
+      if (tid + 256 * i < R) tab[tid + 256 * i] = tv[i];
+    for (int key = tid; key < KROWS; key += 256) {   // CLS and padding keys: 0 (never used / masked)
+      const int yk = (key >= 1 && key < T) ? (key - 1) / rb.gw : 0;
+      koff[key] = (key >= 1 && key < T) ? yk * rl + (key - 1 - yk * rb.gw) : 0;
+    }
+  }
 #pragma unroll
   for (int i = 0; i < NLD; ++i) {
     const int idx = tid + 256 * i;
@@ -85,7 +116,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
   __syncthreads();
 
-  const float sl2 = scale * 1.4426950408889634f;     // exp(x * scale) = exp2(x * sl2)
+  // exp(x * scale) = exp2(x * sl2); RELBIAS: the logits are scaled when the bias is added
+  const float sl2 = RELBIAS ? 1.4426950408889634f : scale * 1.4426950408889634f;
   const int nqt = (T + 15) >> 4;
   const int full_tiles = T >> 4;                     // key tiles without padding
   unsigned short* Ow = Os + wave * 16 * AT_LD;
@@ -124,8 +156,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       s[kt] = acc;
       if ((kt & 3) == 3) __builtin_amdgcn_sched_barrier(0);     // keep at most four tiles of K fragments in flight
     }
+    if constexpr (RELBIAS) {
+      // ---- s = s * scale + table[idx(query, key)]: query q0 + li, keys 16 kt + 4 g + r
+      const int qi = q0 + li;
+      const bool qcls = qi == 0 || qi >= T;          // padding queries read the CLS rows: any valid index will do
+      const int yq = qcls ? 0 : (qi - 1) / rb.gw;
+      const int qb = qcls ? R - 3 : (yq + rb.gh - 1) * rl + (qi - 1 - yq * rb.gw) + rb.gw - 1;
+      const int c0 = qcls ? R - 1 : R - 2;           // against the CLS key
+#pragma unroll
+      for (int kt = 0; kt < NKT; ++kt) {
+        const int4 ko = *reinterpret_cast<const int4*>(koff + 16 * kt + 4 * g);
+        const int kk[4] = {ko.x, ko.y, ko.z, ko.w};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          int idx = qcls ? qb : qb - kk[r];
+          if (kt == 0 && r == 0 && g == 0) idx = c0;
+          s[kt][r] = fmaf(s[kt][r], scale, tab[idx]);
+        }
+      }
+    }
     // ---- the attention tap: CLS query (column 0 of tile 0) with bf16-rounded logits, head-averaged
-    if (!QMEAN && importance != nullptr && qt == 0) {
+    if (!QMEAN && !RELBIAS && importance != nullptr && qt == 0) {
       float lr[NKT][4];                              // transient: dead before the P V product needs registers
       float tmx = -3.0e38f;
 #pragma unroll
@@ -188,6 +239,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     sum += __shfl_xor(sum, 16, 64);
     sum += __shfl_xor(sum, 32, 64);
     const float inv = 1.f / sum;
+    if constexpr (RELBIAS) {
+      // the tap: the CLS row (query 0 = column li 0 of tile 0) of this softmax without the CLS column, divided by H
+      if (importance != nullptr && qt == 0 && li == 0) {
+        const float tinv = inv / (float)H;
+#pragma unroll
+        for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int key = 16 * kt + 4 * g + r;
+            if (key >= 1 && key < T) importance[((size_t)b * H + h) * (T - 1) + key - 1] = s[kt][r] * tinv;
+          }
+      }
+    }
     if constexpr (QMEAN) {
       const float qinv = (q0 + li < T) ? inv : 0.f;  // padding queries (zero rows of Q) are not part of the mean
 #pragma unroll
@@ -196,7 +260,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         for (int r = 0; r < 4; ++r) csum[kt][r] = fmaf(s[kt][r], qinv, csum[kt][r]);
     }
     // log-sum-exp of the scaled logits (natural log): what the backward kernel recomputes P from
-    if (lse != nullptr && g == 0 && q0 + li < T) lse[((size_t)b * H + h) * T + q0 + li] = fmaf(mx, scale, __logf(sum));
+    if (!RELBIAS && lse != nullptr && g == 0 && q0 + li < T) lse[((size_t)b * H + h) * T + q0 + li] = fmaf(mx, scale, __logf(sum));
     // ---- O = P V
     f32x4 o[NDT];
 #pragma unroll
@@ -269,16 +333,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
 }
 
-template <int NKT, int HD, bool QMEAN = false>
+template <int NKT, int HD, bool QMEAN = false, bool RELBIAS = false>
 static void launch_attention(const void* qkv, int B, int T, int H, float scale, void* out, float* importance,
-                             float* lse, hipStream_t st) {
+                             float* lse, hipStream_t st, RelBias rb = RelBias{nullptr, 0, 0}) {
   constexpr int KROWS = 32 * ((NKT + 1) / 2);
   constexpr int LD = (HD + 31) / 32 * 32 + 8;
-  const size_t lds = ((size_t)2 * KROWS * LD + 4 * 16 * LD) * sizeof(unsigned short);
+  size_t lds = ((size_t)2 * KROWS * LD + 4 * 16 * LD) * sizeof(unsigned short);
   static_assert(8 * LD >= KROWS, "the output staging tile of a wave holds its query-mean column sums");
-  allow_full_lds((const void*)attention_fwd_kernel<NKT, HD, QMEAN>);
-  hipLaunchKernelGGL((attention_fwd_kernel<NKT, HD, QMEAN>), dim3(B * H), dim3(256), lds, st, (const unsigned short*)qkv, T, H,
-                     scale, (unsigned short*)out, importance, lse);
+  static_assert((2 * KROWS * LD + 4 * 16 * LD) % 8 == 0, "the key offsets behind the tiles are read 16 bytes at a time");
+  if (RELBIAS) lds += ((size_t)KROWS + (size_t)(2 * rb.gh - 1) * (2 * rb.gw - 1) + 3) * sizeof(float);
+  allow_full_lds((const void*)attention_fwd_kernel<NKT, HD, QMEAN, RELBIAS>);
+  hipLaunchKernelGGL((attention_fwd_kernel<NKT, HD, QMEAN, RELBIAS>), dim3(B * H), dim3(256), lds, st,
+                     (const unsigned short*)qkv, T, H, scale, (unsigned short*)out, importance, lse, rb);
 }
 
 }  // namespace basd
@@ -319,4 +385,20 @@ extern "C" int basd_attention_fwd_qmean_bf16(const void* qkv, int B, int T, int 
     else launch_attention<17, 80, true>(qkv, B, T, H, scale, out, importance, nullptr, st);
   }
   return check_launch("attention_fwd_qmean");
+}
+
+extern "C" int basd_attention_fwd_relbias_bf16(const void* qkv, const float* table, int B, int gh, int gw, int H, int hd,
+                                               float scale, void* out, float* importance, void* stream) {
+  using namespace basd;
+  if (hd != 64 || gh < 1 || gw < 1 || gh > 271 || gw > 271 || gh * gw > 271 || H < 1)
+    return fail(BASD_ERR_SHAPE, "attention_fwd_relbias: grid %d x %d H=%d hd=%d unsupported (hd 64, 2 <= gh * gw + 1 <= 272)",
+                gh, gw, H, hd);
+  if (B <= 0) return BASD_OK;
+  const int T = gh * gw + 1;
+  const RelBias rb{table, gh, gw};
+  hipStream_t st = (hipStream_t)stream;
+  if (T <= 64) launch_attention<4, 64, false, true>(qkv, B, T, H, scale, out, importance, nullptr, st, rb);
+  else if (T <= 208) launch_attention<13, 64, false, true>(qkv, B, T, H, scale, out, importance, nullptr, st, rb);
+  else launch_attention<17, 64, false, true>(qkv, B, T, H, scale, out, importance, nullptr, st, rb);
+  return check_launch("attention_fwd_relbias");
 }

@@ -149,14 +149,16 @@ def load_teacher(model_name: str, img_size: int, *, weights: str | None = None, 
                  seed: int = 42, patch_size: int | None = None, dtype=torch.bfloat16, act: str | None = None,
                  norm_eps: float | None = None) -> TeacherModel:
     """Build (not download: reference teacher.py:113-148 fetches from the network) the named teacher -- a ViT preset of
-    ``models/vit.py`` or a feature-map preset of ``models/cnn.py`` (ResNet, ConvNeXt-V2 and the Swin family of
-    ``models/swin.py``) -- frozen, in eval mode, weights pre-cast to bf16; ``weights`` = a local state dict (timm /
-    torchvision parameter names).  The returned ``mean`` / ``std`` are the preset's (the reference reads them from
-    timm's ``pretrained_cfg``, teacher.py:119-120): CLIP's own statistics, 0.5 / 0.5 for SigLIP, ImageNet's otherwise.
+    ``models/vit.py``, a BEiT / BEiT-v2 preset of ``models/beit.py`` or a feature-map preset of ``models/cnn.py``
+    (ResNet, ConvNeXt-V2 and the Swin family of ``models/swin.py``) -- frozen, in eval mode, weights pre-cast to bf16;
+    ``weights`` = a local state dict (timm / torchvision parameter names).  The returned ``mean`` / ``std`` are the preset's (the reference reads them from
+    timm's ``pretrained_cfg``, teacher.py:119-120): CLIP's own statistics, 0.5 / 0.5 for SigLIP and BEiT v1, ImageNet's otherwise.
     ``act`` / ``norm_eps`` override a ViT preset's MLP activation and LayerNorm epsilon."""
+    from .beit import BEIT_PRESETS, create_beit, load_timm_state_dict
     from .cnn import CNN_PRESETS, create_cnn
     base = model_name.split(".", 1)[0]
-    if model_name not in VIT_PRESETS and model_name not in CNN_PRESETS and (base in CNN_PRESETS or base in VIT_PRESETS):
+    known = (VIT_PRESETS, CNN_PRESETS, BEIT_PRESETS)
+    if not any(model_name in k for k in known) and any(base in k for k in known):
         model_name = base      # timm's pretrained tag ("convnextv2_tiny.fcmae", "..._clip_224.openai"): weights are local
     gen_state = torch.random.get_rng_state()
     torch.manual_seed(seed)
@@ -167,13 +169,23 @@ def load_teacher(model_name: str, img_size: int, *, weights: str | None = None, 
     elif model_name in CNN_PRESETS:
         model = create_cnn(model_name)
         mean, std = _IMAGENET_MEAN, _IMAGENET_STD
+    elif model_name in BEIT_PRESETS:
+        model = create_beit(model_name, img_size=img_size, patch_size=patch_size)
+        mean, std = BEIT_PRESETS[model_name][5:7]
     else:
-        raise ValueError(f"teacher {model_name!r}: not a known preset ({sorted(VIT_PRESETS) + sorted(CNN_PRESETS)}); "
+        raise ValueError(f"teacher {model_name!r}: not a known preset "
+                         f"({sorted(VIT_PRESETS) + sorted(CNN_PRESETS) + sorted(BEIT_PRESETS)}); "
                          "wrap your own module in TeacherModel(...) with the fields probe_model() returns")
     torch.random.set_rng_state(gen_state)
     if weights:
         state = torch.load(weights, map_location="cpu", weights_only=True)
-        model.load_state_dict(state.get("model_state_dict", state), strict=False)
+        state = state.get("model_state_dict", state)
+        if model_name in BEIT_PRESETS:
+            load_timm_state_dict(model, state)       # timm's gamma_1 / gamma_2 names, a checked bias-table size
+        else:
+            model.load_state_dict(state, strict=False)
+    if model_name in BEIT_PRESETS:
+        model.materialize_qkv_bias()                 # cat(q_bias, 0, v_bias) as the qkv layer's bias: one fused GEMM
     model = model.to(device).eval()
     for p in model.parameters():
         p.requires_grad = False

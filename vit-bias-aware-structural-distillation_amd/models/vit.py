@@ -343,10 +343,12 @@ class Mlp(nn.Module):
 
 
 class Block(nn.Module):
-    def __init__(self, dim, num_heads, mlp_ratio=4.0, drop_path=0.0, init_values=None, eps=1e-6, act="gelu"):
+    def __init__(self, dim, num_heads, mlp_ratio=4.0, drop_path=0.0, init_values=None, eps=1e-6, act="gelu",
+                 attn_cls=None):
         super().__init__()
         self.norm1 = MixedLayerNorm(dim, eps=eps)
-        self.attn = Attention(dim, num_heads)
+        # attn_cls(dim, num_heads): the attention of another model family (models/beit.py); default: Attention
+        self.attn = (attn_cls or Attention)(dim, num_heads)
         self.ls1 = LayerScale(dim, init_values) if init_values else nn.Identity()
         self.drop_path1 = DropPath(drop_path)
         self.norm2 = MixedLayerNorm(dim, eps=eps)
