@@ -36,6 +36,8 @@
  *   basd_gemm_bf16         timm nn.Linear (+ nn.GELU) forward of the ViT blocks, teacher.py:212 / trainer.py:33
  *   basd_gemm_bf16_act     the same with the MLP activation of a timm CLIP / SigLIP teacher (QuickGELU, tanh-GELU)
  *   basd_vit_embed_bf16    timm VisionTransformer._pos_embed + norm_pre of a frozen teacher (teacher.py:113-148 loads any)
+ *   basd_gemm_bf16_swiglu  w12 + SiLU gate of DINOv2's SwiGLU MLP (dinov2_vitg14: teacher.py:114-116 loads every dinov2_* name)
+ *   basd_vit_embed_reg_bf16  the DINOv2 forward's token assembly with register tokens (the dinov2_*_reg models, same lines)
  *   basd_gemm_bf16_gelu_fwd, basd_gemm_bf16_gelu_bwd
  *                          timm Mlp (fc1 -> nn.GELU -> fc2) of the TRAINED student: forward and autograd (trainer.py:33,157)
  *   basd_gemm_bf16x3_f32   the teacher-token projection tokens.reshape(-1, D_t) @ proj_t.T (layer_selector.py:72 / :135)
@@ -389,6 +391,24 @@ int basd_gemm_bf16(const void* x, const void* w, const void* bias, void* y, int6
 int basd_gemm_bf16_act(const void* x, const void* w, const void* bias, void* y, int64_t M, int N, int K,
                        int act, int tile_run, void* stream);
 
+/* The first half of a SwiGLU MLP (DINOv2 ViT-g/14: w3(silu(x1) * x2) with x1, x2 = w12(x).chunk(2, -1)) as ONE GEMM
+ * with the gate in its epilogue:
+ *   y[m][h] = bf16(silu(a1) * a2),   a1 = sum_k x[m][k] w1[h][k] + b1[h],   a2 = sum_k x[m][k] w2[h][k] + b2[h],
+ * both sums, the sigmoid and the two products in fp32, one rounding to bf16.  x [M, K] bf16, y [M, H] bf16 with row
+ * pitch H.  The sigmoid is 1 / (1 + 2^(-a1 log2 e)) on the hardware's exp2 and reciprocal, as in basd_gemm_bf16_act:
+ * no overflow for any finite input (a saturated exponential gives -0 or a1 * a2).
+ * w12p [2 H, K] / bias12p [2 H] (nullable) are the PACKED forms of the hub's w12.weight / w12.bias, whose rows
+ * 0 .. H - 1 are w1 (the x1 half) and H .. 2 H - 1 are w2.  Row map, with p the packed row:
+ *   p = 64 * (h / 32) + 32 * s + h % 32   <->   source row s * H + h      (s = 0: w1 / x1, s = 1: w2 / x2, 0 <= h < H)
+ * i.e. blocks of 32 w1 rows alternate with the 32 w2 rows of the same h: a wave of the 256-column tile owns 64 packed
+ * columns = both pre-activations of 32 outputs, in matching registers.  Build it once per frozen layer
+ * (_native.swiglu_pack).  H % 128 == 0 and K % 64 == 0, else BASD_ERR_SHAPE before anything is enqueued (the caller
+ * runs the unfused composition).  Kernels: only the 256-column ring kernels carry this epilogue -- the persistent ring
+ * where basd_gemm_bf16 would choose it for N = 2 H (large M, K >= 192), the ring kernel for every other shape; the
+ * 192- and 128-column tiles are never chosen.  tile_run as basd_gemm_bf16; the output does not depend on it. */
+int basd_gemm_bf16_swiglu(const void* x, const void* w12p, const void* bias12p, void* y, int64_t M, int H, int K,
+                          int tile_run, void* stream);
+
 /* Teacher-statistics projection z = X P^T at student widths > 256 (src/losses/layer_selector.py:72 / :135: the fixed fp32 projection of
  * the teacher tokens in front of the subspace SVD): x [M, K] bf16 row-major, w3 [ceil(N / 256) * 256, 3 K] bf16 = the
  * (hi | mid | lo) bf16 splits of P's rows side by side (zero rows behind N), y [M, N] fp32.  One persistent bf16-MFMA
@@ -443,6 +463,16 @@ int basd_add_layernorm_fwd_bf16(const void* x, const void* residual, const float
  * anything is enqueued. */
 int basd_vit_embed_bf16(const void* patches, const void* cls, const void* pos, const float* gamma, const float* beta,
                         float eps, int B, int N, int D, void* out, void* stream);
+/* The same assembly for a model with R register tokens (the DINOv2 "_reg" models): R learned rows behind the CLS row,
+ * which take no position embedding:
+ *   out[b, 0] = cls + pos[0],   out[b, 1 + r] = reg[r] (r < R),   out[b, 1 + R + n] = patches[b, n] + pos[1 + n],
+ * reg [R, D] bf16, pos [1 + N, D], out [B, 1 + R + N, D]; every row then goes through LN when gamma / beta are given
+ * (register rows included), exactly as above.  R > 0 needs cls and reg (BASD_ERR_SHAPE otherwise: no model of the
+ * family lacks a CLS token).  R = 0: reg is ignored and the output is bitwise basd_vit_embed_bf16's -- one kernel
+ * serves both entries.  Limits, alignment rule (reg counts among the pointers when R > 0) and errors as above. */
+int basd_vit_embed_reg_bf16(const void* patches, const void* cls, const void* reg, int R, const void* pos,
+                            const float* gamma, const float* beta, float eps, int B, int N, int D, void* out,
+                            void* stream);
 /* dx = LayerNorm backward (+ dres when given: the gradient that arrives through the residual connection of a pre-norm
  * block, so dx is the whole gradient of the block's residual stream); dbranch (nullable) = row_scale * dx, the
  * gradient of the branch input of basd_add_layernorm_fwd_bf16.  dgamma / dbeta are accumulated (nullable). */

@@ -40,7 +40,7 @@ EXPORTS = (
     "basd_conv3x3_bf16", "basd_conv7x7s2_relu_bf16", "basd_maxpool3x3s2_bf16", "basd_add_relu_bf16",
     "basd_sym_tridiag_f64_workspace_bytes", "basd_sym_tridiag_f64", "basd_tridiag_mp_rank",
     "basd_window_attention_fwd_bf16", "basd_patch_merge_ln_bf16", "basd_gemm_bf16_act", "basd_vit_embed_bf16",
-    "basd_attention_fwd_relbias_bf16",
+    "basd_attention_fwd_relbias_bf16", "basd_gemm_bf16_swiglu", "basd_vit_embed_reg_bf16",
 )
 
 
@@ -83,12 +83,14 @@ _SIGNATURES = {
     "basd_wgrad_bf16_ws": (_P, _P, _I64, _I, _I, _P, _P, _P, _I64, _P),
     "basd_gemm_bf16": (_P, _P, _P, _P, _I64, _I, _I, _I, _I, _P),
     "basd_gemm_bf16_act": (_P, _P, _P, _P, _I64, _I, _I, _I, _I, _P),
+    "basd_gemm_bf16_swiglu": (_P, _P, _P, _P, _I64, _I, _I, _I, _P),
     "basd_gemm_bf16_gelu_fwd": (_P, _P, _P, _P, _P, _I64, _I, _I, _I, _P),
     "basd_gemm_bf16x3_f32": (_P, _P, _P, _I64, _I, _I, _P),
     "basd_gemm_bf16_gelu_bwd": (_P, _P, _P, _P, _I64, _I, _I, _I, _P),
     "basd_layernorm_fwd_bf16": (_P, _P, _P, _I64, _I, _F, _P, _P, _P, _P),
     "basd_add_layernorm_fwd_bf16": (_P, _P, _P, _P, _I64, _I, _F, _P, _P, _P, _P, _P, _I, _P),
     "basd_vit_embed_bf16": (_P, _P, _P, _P, _P, _F, _I, _I, _I, _P, _P),
+    "basd_vit_embed_reg_bf16": (_P, _P, _P, _I, _P, _P, _P, _F, _I, _I, _I, _P, _P),
     "basd_layernorm_bwd_bf16": (_P, _P, _P, _P, _P, _I64, _I, _P, _P, _P, _P, _P, _P, _I, _P),
     "basd_procrustes_bwd_rows": (_P, _P, _P, _P, _I64, _I, _I, _P, _I, _P, _P),
     "basd_cls_importance_bf16": (_P, _I, _I, _I, _I, _F, _P, _P),
@@ -941,6 +943,47 @@ def gemm_bf16(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None
     return y.view(*x.shape[:-1], n)
 
 
+def gemm_swiglu_supported(h: int, k: int) -> bool:
+    """shapes basd_gemm_bf16_swiglu takes: only the 256-column tiles pair the two halves (2 H % 256 == 0)"""
+    return h >= 128 and h % 128 == 0 and k >= 64 and k % 64 == 0
+
+
+def swiglu_pack_index(h: int) -> torch.Tensor:
+    """source row of every packed row (int64 [2 H], CPU): packed row p = 64 * (i // 32) + 32 * s + i % 32 holds row
+    s * H + i of the hub layout (s = 0: the x1 / w1 half, rows 0 .. H - 1; s = 1: the x2 / w2 half) -- the row map in
+    the header of basd_gemm_bf16_swiglu."""
+    assert h % 32 == 0, h
+    p = torch.arange(2 * h)
+    return ((p // 32) % 2) * h + (p // 64) * 32 + p % 32
+
+
+def swiglu_pack(w12: torch.Tensor, b12: torch.Tensor | None = None):
+    """hub ``w12.weight`` [2 H, K] (+ ``w12.bias`` [2 H]) -> the packed operands of basd_gemm_bf16_swiglu: blocks of
+    32 w1 rows alternating with the 32 w2 rows of the same outputs.  Pure torch (any device, any dtype): a row
+    permutation, built once per frozen layer."""
+    idx = swiglu_pack_index(w12.shape[0] // 2).to(w12.device)
+    return w12.index_select(0, idx).contiguous(), (None if b12 is None else b12.index_select(0, idx).contiguous())
+
+
+def gemm_bf16_swiglu(x: torch.Tensor, w12p: torch.Tensor, b12p: torch.Tensor | None) -> torch.Tensor:
+    """x [..., K], w12p [2 H, K], b12p [2 H] | None (bf16; the PACKED forms of swiglu_pack) -> bf16(silu(x1) * x2)
+    [..., H] with x1, x2 the two halves of the hub's w12(x): one GEMM with the gate in its epilogue
+    (basd_gemm_bf16_swiglu).  Inference building block (no autograd)."""
+    _need_cuda(x, w12p, b12p)
+    assert x.dtype == torch.bfloat16 and w12p.dtype == torch.bfloat16 and (b12p is None or b12p.dtype == torch.bfloat16)
+    k, h = x.shape[-1], w12p.shape[0] // 2
+    assert w12p.shape == (2 * h, k) and gemm_swiglu_supported(h, k), (tuple(w12p.shape), k)
+    assert b12p is None or b12p.numel() == 2 * h
+    x2 = x.reshape(-1, k)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    y = torch.empty(x2.shape[0], h, dtype=torch.bfloat16, device=x.device)
+    _check(lib().basd_gemm_bf16_swiglu(_ptr(x2), _ptr(w12p.contiguous()), _ptr(None if b12p is None else b12p.contiguous()),
+                                       _ptr(y), ctypes.c_int64(x2.shape[0]), h, k, GEMM_TILE_RUN, _stream()),
+           "basd_gemm_bf16_swiglu")
+    return y.view(*x.shape[:-1], h)
+
+
 def gemm_gelu_fwd(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None):
     """x [..., K], w [N, K], bias [N] | None (bf16) -> (pre, act) [..., N] bf16: pre = x w^T + bias rounded to bf16,
     act = gelu(pre) -- fc1 + nn.GELU of a trained block in one launch, ``pre`` saved for ``gemm_gelu_bwd``."""
@@ -1204,10 +1247,13 @@ def vit_embed_supported(d: int) -> bool:
 
 
 def vit_embed(patches: torch.Tensor, cls: torch.Tensor | None, pos: torch.Tensor, gamma: torch.Tensor | None = None,
-              beta: torch.Tensor | None = None, eps: float = 1e-5) -> torch.Tensor:
+              beta: torch.Tensor | None = None, eps: float = 1e-5, reg: torch.Tensor | None = None) -> torch.Tensor:
     """patches [B, N, D], cls [D] (any shape with D elements) | None, pos [T, D] (or [1, T, D]), T = N + (cls given),
     all bf16 -> [B, T, D] bf16: the rows ``src + pos`` rounded to bf16 (torch's cat + add), layer-normalised when
-    gamma / beta (fp32 [D]) are given.  One launch (basd_vit_embed_bf16)."""
+    gamma / beta (fp32 [D]) are given.  One launch (basd_vit_embed_bf16).  ``reg`` [R, D] (or [1, R, D]): R register
+    rows behind the CLS row, without a position row -> [B, T + R, D] (basd_vit_embed_reg_bf16)."""
+    if reg is not None:
+        return _vit_embed_reg(patches, cls, reg, pos, gamma, beta, eps)
     _need_cuda(patches, cls, pos, gamma, beta)
     assert patches.dtype == torch.bfloat16 and pos.dtype == torch.bfloat16 and patches.dim() == 3
     assert cls is None or cls.dtype == torch.bfloat16
@@ -1223,6 +1269,25 @@ def vit_embed(patches: torch.Tensor, cls: torch.Tensor | None, pos: torch.Tensor
                                      _ptr(None if gamma is None else gamma.contiguous()),
                                      _ptr(None if beta is None else beta.contiguous()), ctypes.c_float(eps), b, n, d,
                                      _ptr(out), _stream()), "basd_vit_embed_bf16")
+    return out
+
+
+def _vit_embed_reg(patches, cls, reg, pos, gamma, beta, eps):
+    _need_cuda(patches, cls, reg, pos, gamma, beta)
+    assert patches.dtype == torch.bfloat16 and pos.dtype == torch.bfloat16 and patches.dim() == 3
+    assert cls is not None and cls.dtype == torch.bfloat16 and reg.dtype == torch.bfloat16
+    assert (gamma is None) == (beta is None)
+    assert gamma is None or (gamma.dtype == torch.float32 and beta.dtype == torch.float32)
+    b, n, d = patches.shape
+    r = reg.numel() // d
+    assert reg.numel() == r * d and pos.numel() == (n + 1) * d and cls.numel() == d, (tuple(reg.shape), tuple(pos.shape), n, d)
+    assert gamma is None or (gamma.numel() == d and beta.numel() == d)
+    patches, pos = patches.contiguous(), pos.contiguous()
+    out = torch.empty(b, 1 + r + n, d, dtype=torch.bfloat16, device=patches.device)
+    _check(lib().basd_vit_embed_reg_bf16(_ptr(patches), _ptr(cls.contiguous()), _ptr(reg.contiguous()), r, _ptr(pos),
+                                         _ptr(None if gamma is None else gamma.contiguous()),
+                                         _ptr(None if beta is None else beta.contiguous()), ctypes.c_float(eps), b, n, d,
+                                         _ptr(out), _stream()), "basd_vit_embed_reg_bf16")
     return out
 
 

@@ -105,6 +105,14 @@ __device__ __forceinline__ float gelu_tanh_fwd(float x) {
   return x * __builtin_amdgcn_rcpf(1.0f + e);
 }
 
+// SwiGLU gate of DINOv2's ViT-g/14 MLP (basd_gemm_bf16_swiglu, EPI 8): silu(a) * b = (a * sigmoid(a)) * b with the
+// sigmoid of quick_gelu_fwd (s = a: no product in front of the exponent's scale); the same saturation: a -> -inf gives
+// a * 0 = -0, a -> +inf gives a * 1.  Two fp32 products behind the sigmoid, one rounding to bf16 at the store.
+__device__ __forceinline__ float swiglu_gate(float a, float b) {
+  const float e = __builtin_amdgcn_exp2f(a * -1.4426950408889634f);           // -log2(e)
+  return (a * __builtin_amdgcn_rcpf(1.0f + e)) * b;
+}
+
 template <int EPI>
 __device__ __forceinline__ float gemm_act(float v) {      // the forward activation of an epilogue without a saved tile
   if (EPI == 2) return gelu_fwd(v);
@@ -191,8 +199,52 @@ __device__ __forceinline__ void gemm_epilogue(f32x4 (&acc)[NT][8], unsigned char
   flush(Y);
 }
 
+// The gated epilogue (EPI 8, basd_gemm_bf16_swiglu; 256-column tiles only).  The operand is the PACKED w12 (header of
+// the entry): of the 64 columns a wave owns, the first 32 are w1 rows h0 .. h0 + 31 and the last 32 the w2 rows of the
+// same h, h0 = n0 / 2 + wn * 32.  Lane, j and r address the same (row, column-within-tile) cell in acc[i] and
+// acc[i + 2], so the gate silu(acc[i] + b1) * (acc[i + 2] + b2) is formed in registers.  The OUTPUT tile is half as
+// wide as the operand tile: 32 columns per wave, row pitch H -- tile_off, the flush stride and the chunks per row are
+// all written in H and WH, the bias reads in the packed index.
+__device__ __forceinline__ void gemm_epilogue_swiglu(f32x4 (&acc)[4][8], unsigned char* lds, const unsigned short* bias,
+                                                     unsigned short* Y, int M, int H, int m0, int n0, int wm, int wn,
+                                                     int lane, int wave) {
+  constexpr int WN = 64, WH = WN / 2;              // packed columns / output columns of a wave
+  constexpr int ROWB = WH * 2 + 16;                // LDS row stride in bytes (80: 16-byte aligned)
+  constexpr int CH = WH * 2 / 16;                  // 16-byte chunks per OUTPUT row
+  unsigned char* region = lds + wave * (128 * ROWB);
+  const size_t tile_off = (size_t)(m0 + wm * 128) * H + (n0 >> 1) + wn * WH;
+  __builtin_amdgcn_s_barrier();                    // every wave is done with the operand ring
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int nl = i * 16 + 4 * (lane >> 4);       // local OUTPUT column of this lane's 4 values
+    float b1[4] = {0.f, 0.f, 0.f, 0.f}, b2[4] = {0.f, 0.f, 0.f, 0.f};
+    if (bias != nullptr) {
+      const u16x4 p1 = *reinterpret_cast<const u16x4*>(bias + n0 + wn * WN + nl);
+      const u16x4 p2 = *reinterpret_cast<const u16x4*>(bias + n0 + wn * WN + WH + nl);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { b1[r] = bf16_bits_to_f32(p1[r]); b2[r] = bf16_bits_to_f32(p2[r]); }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      u16x4 o;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[r] = f32_to_bf16_bits(swiglu_gate(acc[i][j][r] + b1[r], acc[i + 2][j][r] + b2[r]));
+      *reinterpret_cast<u16x4*>(region + (j * 16 + (lane & 15)) * ROWB + nl * 2) = o;
+    }
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");               // wave-private region: no barrier
+#pragma unroll
+  for (int it = 0; it < 2 * CH; ++it) {            // 128 rows x CH chunks, 16 bytes per lane along the rows
+    const int item = it * 64 + lane;
+    const int row = item / CH, ch = item - row * CH;
+    const uint4 v = *reinterpret_cast<const uint4*>(region + row * ROWB + ch * 16);
+    if (m0 + wm * 128 + row < M) *reinterpret_cast<uint4*>(Y + tile_off + (size_t)row * H + ch * 8) = v;
+  }
+}
+
 // EPI: 0 = none, 1 = + bias, 2 = gelu(+ bias), 3 = aux <- (+ bias), y <- gelu(aux), 4 = y <- acc * gelu'(aux)
-// (5 = fp32 output of the bf16x3 product: persistent kernel only), 6 = QuickGELU(+ bias), 7 = tanh-GELU(+ bias)
+// (5 = fp32 output of the bf16x3 product: persistent kernel only), 6 = QuickGELU(+ bias), 7 = tanh-GELU(+ bias),
+// 8 = SwiGLU gate over a packed w12 (ring and persistent ring kernels only; N = 2 H, output [M, H])
 template <int BN, int EPI>
 __global__ __launch_bounds__(512) void gemm_bf16_nt_kernel(const unsigned short* __restrict__ X,
                                                            const unsigned short* __restrict__ W,
@@ -413,7 +465,8 @@ __global__ __launch_bounds__(512) void gemm_bf16_ring_kernel(const unsigned shor
     k_step(t, std::false_type{});
   }
 
-  gemm_epilogue<BN, NT, EPI>(acc, g_lds, bias, aux, Y, M, N, m0, n0, wm, wn, lane, wave);
+  if constexpr (EPI == 8) gemm_epilogue_swiglu(acc, g_lds, bias, Y, M, N >> 1, m0, n0, wm, wn, lane, wave);
+  else gemm_epilogue<BN, NT, EPI>(acc, g_lds, bias, aux, Y, M, N, m0, n0, wm, wn, lane, wave);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -531,6 +584,52 @@ __device__ __forceinline__ void gemm_epilogue_direct(f32x4 (&acc)[4][8], const u
   }
 }
 
+// The gated epilogue (EPI 8) in the register -> global form.  The gate is formed BEFORE the butterflies, in the
+// accumulator layout (acc[i] and acc[i + 2] hold the same cell of the w1 and the w2 half, see gemm_epilogue_swiglu);
+// the two swaps of the pair (0, 1) then leave lane (r16, q) with the 8 consecutive output columns q * 8 + [0, 8) of
+// the wave's 32: ONE 16-byte store per lane and 16-row block, 8 per epilogue (the bias-only epilogues issue 16).
+// col0 is the wave's first PACKED column (bias index); the output column is col0 / 2, the output pitch H.
+__device__ __forceinline__ void gemm_epilogue_direct_swiglu(f32x4 (&acc)[4][8], const unsigned short* bias,
+                                                            unsigned short* Y, int M, int H, int row0, int col0,
+                                                            int lane) {
+  typedef unsigned int eu32x2 __attribute__((ext_vector_type(2)));
+  const int q = lane >> 4, r16 = lane & 15;
+  float b1[2][4], b2[2][4];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) b1[i][r] = b2[i][r] = 0.f;
+  if (bias != nullptr) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const u16x4 p1 = *reinterpret_cast<const u16x4*>(bias + col0 + i * 16 + 4 * q);
+      const u16x4 p2 = *reinterpret_cast<const u16x4*>(bias + col0 + 32 + i * 16 + 4 * q);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { b1[i][r] = bf16_bits_to_f32(p1[r]); b2[i][r] = bf16_bits_to_f32(p2[r]); }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float f[8];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float g0 = swiglu_gate(acc[0][j][r] + b1[0][r], acc[2][j][r] + b2[0][r]);
+      const float g1 = swiglu_gate(acc[1][j][r] + b1[1][r], acc[3][j][r] + b2[1][r]);
+      eu32x2 s1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(g0), __float_as_uint(g1), false, false);
+      eu32x2 s2 = __builtin_amdgcn_permlane16_swap(s1[0], s1[1], false, false);
+      f[r] = __uint_as_float(s2[0]);
+      f[4 + r] = __uint_as_float(s2[1]);
+    }
+    const int row = row0 + j * 16 + r16;
+    if (row < M) {
+      const size_t off = (size_t)row * H + (col0 >> 1) + q * 8;
+      const uint4 o = make_uint4(pack_bf16_bits(f[0], f[1]), pack_bf16_bits(f[2], f[3]), pack_bf16_bits(f[4], f[5]),
+                                 pack_bf16_bits(f[6], f[7]));
+      __builtin_nontemporal_store((u32x4){o.x, o.y, o.z, o.w}, reinterpret_cast<u32x4*>(Y + off));
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // PERSISTENT ring kernel.  One workgroup per CU; the LDS ring of five 32 KiB units never drains: the last two K steps
 // of a tile already issue the first units of the NEXT one, the epilogue goes register -> global
@@ -582,7 +681,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pring_kernel(const unsigned sho
   // split of the weights, whose rows hold the splits side by side: pitch K = 3 ka); N = columns stored = output pitch.
   extern __shared__ __align__(16) unsigned char g_lds[];
   constexpr int NT = 4, UNIT = 32768, NSLOT = 5;
-  constexpr int NST = (EPI == 3) ? 32 : 16;                 // global stores of a wave per epilogue
+  constexpr int NST = (EPI == 3) ? 32 : (EPI == 8) ? 8 : 16;   // global stores of a wave per epilogue
   const int KA = EPI == 5 ? ka : K;                         // row pitch of the activation panel
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -744,6 +843,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pring_kernel(const unsigned sho
       // an epilogue, its st_pending stores, which were issued before that unit
       if (t == 0 && st_pending != 0) {
         if (NST == 16) asm volatile("s_waitcnt vmcnt(20) lgkmcnt(0)" ::: "memory");
+        else if (NST == 8) asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(36) lgkmcnt(0)" ::: "memory");
       } else {
         asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
@@ -756,7 +856,8 @@ __global__ __launch_bounds__(512) void gemm_bf16_pring_kernel(const unsigned sho
       slot = s_a1;
     }
     const bool full_rows = m0 + GBM <= M;                   // every store of the epilogue is issued by every wave
-    gemm_epilogue_direct<EPI>(acc, bias, aux, Y, M, N, m0 + wm * 128, n0 + wn * 64, lane);
+    if constexpr (EPI == 8) gemm_epilogue_direct_swiglu(acc, bias, Y, M, N >> 1, m0 + wm * 128, n0 + wn * 64, lane);
+    else gemm_epilogue_direct<EPI>(acc, bias, aux, Y, M, N, m0 + wm * 128, n0 + wn * 64, lane);
     st_pending = (full_rows && EPI != 5) ? NST : 0;
     if (!full_rows || EPI == 5) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // ragged rows (EPI 5: columns): not every wave issues every store
     if (!has_next) break;
@@ -906,6 +1007,23 @@ extern "C" int basd_gemm_bf16_act(const void* x, const void* w, const void* bias
   // act -> EPI: none = + bias (or nothing), erf-GELU = the epilogue basd_gemm_bf16 runs, QuickGELU, tanh-GELU
   const int epilogue = act == 0 ? (bias != nullptr ? 1 : 0) : act == 1 ? 2 : act == 2 ? 6 : 7;
   return gemm_dispatch(x, w, bias, nullptr, y, M, N, K, epilogue, tile_run, stream, "gemm_bf16_act");
+}
+
+extern "C" int basd_gemm_bf16_swiglu(const void* x, const void* w12p, const void* bias12p, void* y, int64_t M, int H,
+                                     int K, int tile_run, void* stream) {
+  using namespace basd;
+  // only the 256-column kernels carry the gated epilogue (the 192-column tile has three 16-column tiles per wave and
+  // cannot pair them): persistent ring where basd_gemm_bf16 would take it for N = 2 H, else the ring kernel
+  if (H < 128 || H % 128 || H > (1 << 29) || K % GBK || K < GBK)
+    return fail(BASD_ERR_SHAPE, "gemm_bf16_swiglu: need H %% 128 == 0 and K %% 64 == 0 (got H=%d K=%d)", H, K);
+  if (M > 0x7fffff00LL) return fail(BASD_ERR_SHAPE, "gemm_bf16_swiglu: M = %lld too large", (long long)M);
+  if (M <= 0) return BASD_OK;
+  if (x == nullptr || w12p == nullptr || y == nullptr) return fail(BASD_ERR_SHAPE, "gemm_bf16_swiglu: null x / w12p / y");
+  const int m = (int)M, N = 2 * H;
+  hipStream_t st = (hipStream_t)stream;
+  if (pring_cus_per_xcd(m, N) == 32 && K >= 192) launch_gemm_pring<8>(x, w12p, bias12p, nullptr, y, m, N, K, tile_run, st);
+  else launch_gemm_ring<8>(x, w12p, bias12p, nullptr, y, m, N, K, st);
+  return check_launch("gemm_bf16_swiglu");
 }
 
 extern "C" int basd_gemm_bf16x3_f32(const void* x, const void* w3, float* y, int64_t M, int N, int K, void* stream) {

@@ -9,6 +9,11 @@
 // layernorm.hip on that rounded row -- same row ownership (G lanes of a wave, NCH chunks of 8 columns per lane), same
 // reduction (group_allsum), two-pass fp32 statistics, one rounding at the store -- so the output equals
 // basd_layernorm_fwd_bf16 of the torch-assembled tensor bit for bit.
+// Register tokens (DINOv2 "_reg" models, basd_vit_embed_reg_bf16): R learned rows stand between the CLS row and the
+// patch rows and take NO position embedding -- out[b, 1 + r] = reg[r], out[b, 1 + R + n] = patches[b, n] + pos[1 + n],
+// pos keeps its 1 + N rows.  The same kernel body: a register row adds -0.0 instead of a position row (x + -0.0 == x
+// for every x, a negative zero included, so the row passes through the fp32 add and the rounding bit for bit), and
+// with R = 0 no row takes that branch: basd_vit_embed_bf16 is this kernel with R = 0.
 // Access: 16 bytes per lane when every pointer is 16-byte aligned (D % 8 == 0 makes every row pitch a multiple of 16
 // bytes, so the bases decide), else the same chunks element by element (views that start at an odd offset).
 #include "basd_frag.h"
@@ -37,6 +42,7 @@ __device__ __forceinline__ void embed_store8(unsigned short* p, const uint4& v) 
 template <int G, int NCH, bool LN, bool WIDE, int U>
 __global__ __launch_bounds__(256) void vit_embed_kernel(const unsigned short* __restrict__ patches,
                                                         const unsigned short* __restrict__ cls,
+                                                        const unsigned short* __restrict__ reg, int R,
                                                         const unsigned short* __restrict__ pos,
                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
                                                         float eps, int64_t rows, int N, int T, int D,
@@ -67,8 +73,13 @@ __global__ __launch_bounds__(256) void vit_embed_kernel(const unsigned short* __
       const int64_t r = r0 + u * wstride;
       const int64_t smp = r / T;
       const int t = (int)(r - smp * T);
-      // rows beyond the end load nothing; a CLS row reads the [D] token, every other row its patch row
-      const unsigned short* src = (has_cls && t == 0) ? cls : patches + (smp * N + (t - has_cls)) * D;
+      // rows beyond the end load nothing; a CLS row reads the [D] token, a register row (has_cls <= t < has_cls + R)
+      // its [D] row of reg and no position row, every other row its patch row and the position row t - R
+      const bool is_reg = t >= has_cls && t < has_cls + R;
+      const unsigned short* src = (has_cls && t == 0) ? cls
+                                  : is_reg ? reg + (int64_t)(t - has_cls) * D
+                                           : patches + (smp * N + (t - has_cls - R)) * D;
+      const int tp = t < has_cls + R ? t : t - R;
 #pragma unroll
       for (int c = 0; c < NCH; ++c) {
         const int ch = lg + c * G;
@@ -76,7 +87,8 @@ __global__ __launch_bounds__(256) void vit_embed_kernel(const unsigned short* __
         pv[u][c] = make_uint4(0, 0, 0, 0);
         if (ch < nchunk && r < rows) {
           xv[u][c] = embed_load8<WIDE>(src + ch * 8);
-          pv[u][c] = embed_load8<WIDE>(pos + (int64_t)t * D + ch * 8);
+          pv[u][c] = is_reg ? make_uint4(0x80008000u, 0x80008000u, 0x80008000u, 0x80008000u)
+                            : embed_load8<WIDE>(pos + (int64_t)tp * D + ch * 8);
         }
       }
     }
@@ -135,9 +147,10 @@ __global__ __launch_bounds__(256) void vit_embed_kernel(const unsigned short* __
 }
 
 template <bool LN, bool WIDE>
-static int launch_vit_embed(const unsigned short* patches, const unsigned short* cls, const unsigned short* pos,
+static int launch_vit_embed(const unsigned short* patches, const unsigned short* cls, const unsigned short* reg, int R,
+                            const unsigned short* pos,
                             const float* gamma, const float* beta, float eps, int64_t rows, int N, int T, int D,
-                            unsigned short* out, hipStream_t st) {
+                            unsigned short* out, hipStream_t st, const char* what) {
   const int nchunk = D / 8;
   auto grid = [&](int rows_per_wg) {
     const int64_t g = (rows + rows_per_wg - 1) / rows_per_wg;
@@ -146,41 +159,61 @@ static int launch_vit_embed(const unsigned short* patches, const unsigned short*
   // the (G, NCH, U) table of launch_ln_fwd: the row ownership decides the summation order
 #define BASD_VIT_EMBED(G, NCH, U)                                                                                  \
   hipLaunchKernelGGL((vit_embed_kernel<G, NCH, LN, WIDE, U>), dim3(grid(4 * (64 / G) * U)), dim3(256), 0, st, patches, \
-                     cls, pos, gamma, beta, eps, rows, N, T, D, out)
+                     cls, reg, R, pos, gamma, beta, eps, rows, N, T, D, out)
   if (nchunk <= 32) BASD_VIT_EMBED(32, 1, 4);
   else if (nchunk <= 64) BASD_VIT_EMBED(64, 1, 4);
   else if (nchunk <= 128) BASD_VIT_EMBED(64, 2, 2);
   else if (nchunk <= 192) BASD_VIT_EMBED(64, 3, 1);
   else BASD_VIT_EMBED(64, 4, 1);
 #undef BASD_VIT_EMBED
-  return check_launch("vit_embed_bf16");
+  return check_launch(what);
 }
 
 }  // namespace basd
 
-extern "C" int basd_vit_embed_bf16(const void* patches, const void* cls, const void* pos, const float* gamma,
-                                   const float* beta, float eps, int B, int N, int D, void* out, void* stream) {
+// both entries; `what` names the caller in the messages
+static int vit_embed_entry(const char* what, const void* patches, const void* cls, const void* reg, int R,
+                           const void* pos, const float* gamma, const float* beta, float eps, int B, int N, int D,
+                           void* out, void* stream) {
   using namespace basd;
-  if (D % 8 || D < 8 || D > 2048) return fail(BASD_ERR_SHAPE, "vit_embed_bf16: D %% 8 != 0 or D outside 8 .. 2048 (%d)", D);
-  const int T = N + (cls != nullptr ? 1 : 0);
-  if (B < 0 || N < 0 || T < 1) return fail(BASD_ERR_SHAPE, "vit_embed_bf16: B = %d, N = %d and no CLS token: no rows", B, N);
-  if ((gamma == nullptr) != (beta == nullptr)) return fail(BASD_ERR_SHAPE, "vit_embed_bf16: gamma and beta go together");
+  if (D % 8 || D < 8 || D > 2048) return fail(BASD_ERR_SHAPE, "%s: D %% 8 != 0 or D outside 8 .. 2048 (%d)", what, D);
+  if (R < 0 || (R > 0 && (cls == nullptr || reg == nullptr)))
+    return fail(BASD_ERR_SHAPE, "%s: R = %d register rows need R >= 0, a CLS token and reg", what, R);
+  const int64_t T = (int64_t)N + R + (cls != nullptr ? 1 : 0);
+  if (B < 0 || N < 0 || T < 1) return fail(BASD_ERR_SHAPE, "%s: B = %d, N = %d and no CLS token: no rows", what, B, N);
+  if (T > 0x7fffffff) return fail(BASD_ERR_SHAPE, "%s: N + R = %lld rows per image", what, (long long)T);
+  if ((gamma == nullptr) != (beta == nullptr)) return fail(BASD_ERR_SHAPE, "%s: gamma and beta go together", what);
   if (pos == nullptr || out == nullptr || (patches == nullptr && N > 0))
-    return fail(BASD_ERR_SHAPE, "vit_embed_bf16: null patches / pos / out");
+    return fail(BASD_ERR_SHAPE, "%s: null patches / pos / out", what);
   if (B == 0) return BASD_OK;
   const int64_t rows = (int64_t)B * T;
   const uintptr_t p0 = (uintptr_t)patches, p1 = p0 + (uintptr_t)B * N * D * 2;
   const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)rows * D * 2;
-  if (N > 0 && p0 < o1 && o0 < p1) return fail(BASD_ERR_SHAPE, "vit_embed_bf16: out overlaps patches");
-  const bool wide = (((uintptr_t)patches | (uintptr_t)cls | (uintptr_t)pos | (uintptr_t)out) & 15) == 0;
+  if (N > 0 && p0 < o1 && o0 < p1) return fail(BASD_ERR_SHAPE, "%s: out overlaps patches", what);
+  const bool wide = (((uintptr_t)patches | (uintptr_t)cls | (uintptr_t)reg | (uintptr_t)pos | (uintptr_t)out) & 15) == 0;
   const unsigned short* pp = (const unsigned short*)patches;
   const unsigned short* cp = (const unsigned short*)cls;
+  const unsigned short* rp = (const unsigned short*)reg;
   const unsigned short* sp = (const unsigned short*)pos;
   unsigned short* op = (unsigned short*)out;
   hipStream_t st = (hipStream_t)stream;
+  const int t = (int)T;
   if (gamma != nullptr)
-    return wide ? launch_vit_embed<true, true>(pp, cp, sp, gamma, beta, eps, rows, N, T, D, op, st)
-                : launch_vit_embed<true, false>(pp, cp, sp, gamma, beta, eps, rows, N, T, D, op, st);
-  return wide ? launch_vit_embed<false, true>(pp, cp, sp, gamma, beta, eps, rows, N, T, D, op, st)
-              : launch_vit_embed<false, false>(pp, cp, sp, gamma, beta, eps, rows, N, T, D, op, st);
+    return wide ? launch_vit_embed<true, true>(pp, cp, rp, R, sp, gamma, beta, eps, rows, N, t, D, op, st, what)
+                : launch_vit_embed<true, false>(pp, cp, rp, R, sp, gamma, beta, eps, rows, N, t, D, op, st, what);
+  return wide ? launch_vit_embed<false, true>(pp, cp, rp, R, sp, gamma, beta, eps, rows, N, t, D, op, st, what)
+              : launch_vit_embed<false, false>(pp, cp, rp, R, sp, gamma, beta, eps, rows, N, t, D, op, st, what);
+}
+
+extern "C" int basd_vit_embed_bf16(const void* patches, const void* cls, const void* pos, const float* gamma,
+                                   const float* beta, float eps, int B, int N, int D, void* out, void* stream) {
+  return vit_embed_entry("vit_embed_bf16", patches, cls, nullptr, 0, pos, gamma, beta, eps, B, N, D, out, stream);
+}
+
+extern "C" int basd_vit_embed_reg_bf16(const void* patches, const void* cls, const void* reg, int R, const void* pos,
+                                       const float* gamma, const float* beta, float eps, int B, int N, int D, void* out,
+                                       void* stream) {
+  // R = 0: reg is not read (and does not take part in the alignment test)
+  return vit_embed_entry("vit_embed_reg_bf16", patches, cls, R > 0 ? reg : nullptr, R, pos, gamma, beta, eps, B, N, D,
+                         out, stream);
 }

@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from ..losses.layer_selector import marchenko_pastur_rank, marchenko_pastur_rank_wide, mp_rank_route
-from .vit import IMAGENET_MEAN, IMAGENET_STD, VIT_PRESETS, create_vit, vit_preset
+from .vit import IMAGENET_MEAN, IMAGENET_STD, VIT_PRESETS, create_vit, dinov2_state_dict, vit_preset
 
 
 class TeacherModel(NamedTuple):
@@ -116,13 +116,18 @@ def fold_layerscale(model: nn.Module) -> int:
     Returns the number of folded scales."""
     folded = 0
     for block in model.modules():
-        for ls_name, lin_path in (("ls1", "attn.proj"), ("ls2", "mlp.fc2")):
+        for ls_name, lin_paths in (("ls1", ("attn.proj",)), ("ls2", ("mlp.fc2", "mlp.w3"))):
             ls = getattr(block, ls_name, None)
             if ls is None or isinstance(ls, nn.Identity) or not hasattr(ls, "gamma"):
                 continue
-            try:
-                lin = block.get_submodule(lin_path)
-            except AttributeError:
+            lin = None
+            for lin_path in lin_paths:          # a SwiGLU MLP (DINOv2 ViT-g/14) has no fc2: its output layer is w3
+                try:
+                    lin = block.get_submodule(lin_path)
+                    break
+                except AttributeError:
+                    continue
+            if lin is None:
                 continue
             if not isinstance(lin, nn.Linear) or lin.weight.requires_grad:
                 continue
@@ -182,6 +187,8 @@ def load_teacher(model_name: str, img_size: int, *, weights: str | None = None, 
         state = state.get("model_state_dict", state)
         if model_name in BEIT_PRESETS:
             load_timm_state_dict(model, state)       # timm's gamma_1 / gamma_2 names, a checked bias-table size
+        elif model_name in VIT_PRESETS:
+            model.load_state_dict(dinov2_state_dict(model, state), strict=False)    # hub / timm names of the DINOv2 family
         else:
             model.load_state_dict(state, strict=False)
     if model_name in BEIT_PRESETS:

@@ -26,6 +26,13 @@ on the assembled tokens in front of block 0, patch embedding without bias), the 
 epilogue (``basd_gemm_bf16_act``) and the token assembly + ``norm_pre`` is one kernel (``basd_vit_embed_bf16``).  A
 TRAINED block with a non-erf activation has no backward epilogue: it takes the unfused path and is counted as a library
 fallback -- students with these activations or with ``pre_norm`` are out of scope.
+
+The DINOv2 family adds two more: ``reg_tokens`` (R learned rows placed behind the CLS row AFTER the position embedding
+has been added, so ``pos_embed`` keeps its 1 + N rows and every block runs on 1 + R + N tokens) and ``mlp="swiglu"``
+(ViT-g/14: ``w3(silu(x1) * x2)``, ``x1, x2 = w12(x).chunk(2, -1)``, hub parameter names).  Again for FROZEN teachers:
+the gate rides in the w12 GEMM's epilogue (``basd_gemm_bf16_swiglu`` on weights packed once) and the token assembly
+with registers is one kernel (``basd_vit_embed_reg_bf16``); a trained SwiGLU runs unfused and is a counted fallback.
+The reference strips only the CLS row, so the registers stay among the teacher tokens and in the importance vector.
 """
 from __future__ import annotations
 
@@ -226,6 +233,9 @@ _FUSED_TEACHER_ATTENTION = os.environ.get("BASD_FUSED_ATTN", "1") == "1"     # 0
 # 0: QuickGELU / tanh-GELU as a torch op behind a bias-only GEMM, torch token assembly + norm_pre (A/B runs:
 # scripts/time_clip_teacher.py flips it inside one process)
 _FUSED_CLIP_DISPATCH = os.environ.get("BASD_FUSED_CLIP", "1") == "1"
+# 0: SwiGLU as a bias-only w12 GEMM + a torch gate, register tokens through the torch assembly (A/B runs:
+# scripts/time_dinov2_teacher.py flips it inside one process)
+_FUSED_DINOV2_DISPATCH = os.environ.get("BASD_FUSED_DINOV2", "1") == "1"
 _packed_attention_ok = True      # cleared on the first failure of the direct library call (other torch builds)
 
 
@@ -342,9 +352,49 @@ class Mlp(nn.Module):
         return self.fc2(self.act(self.fc1(x)))
 
 
+MLP_KINDS = ("mlp", "swiglu")
+
+
+class SwiGLU(nn.Module):
+    """The MLP of DINOv2's ViT-g/14 (hub ``SwiGLUFFNFused``; parameter names ``w12`` / ``w3`` as in the hub checkpoint):
+    ``w3(silu(x1) * x2)`` with ``x1, x2 = w12(x).chunk(2, -1)``.  Frozen bf16 layer on the device: ONE GEMM over the
+    packed w12 with the gate in its epilogue (``basd_gemm_bf16_swiglu``), then the w3 GEMM; the packed operands are
+    built on the first such forward (after the bf16 cast) and kept: the teacher is frozen.  Anything else is the torch
+    composition -- on the device a counted library fallback (a trained SwiGLU has no backward epilogue)."""
+
+    def __init__(self, dim: int, hidden: int):
+        super().__init__()
+        self.w12 = BasdLinear(dim, 2 * hidden)
+        self.w3 = BasdLinear(hidden, dim)
+        self._packed = None            # (key of the w12 tensors, packed weight, packed bias)
+
+    def _packed_operands(self):
+        w, b = self.w12.weight, self.w12.bias
+        key = (w.data_ptr(), w._version, None if b is None else (b.data_ptr(), b._version))
+        if self._packed is None or self._packed[0] != key:
+            wp, bp = get_ops().swiglu_pack(w.detach(), None if b is None else b.detach())
+            self._packed = (key, wp, bp)
+        return self._packed[1], self._packed[2]
+
+    def forward(self, x):
+        hidden = self.w3.in_features
+        if self.w12.fused_inference_ok(x) and self.w3.fused_inference_ok(x):
+            if not _FUSED_DINOV2_DISPATCH:                 # A/B: bias-only GEMM, gate as torch ops
+                x1, x2 = self.w12(x).chunk(2, dim=-1)
+                return self.w3(F.silu(x1) * x2)
+            if get_ops().gemm_swiglu_supported(hidden, self.w12.in_features):
+                wp, bp = self._packed_operands()
+                return self.w3(get_ops().gemm_bf16_swiglu(x, wp, bp))
+        if get_ops().handles(x):
+            library_fallback("SwiGLU MLP", f"w12 {self.w12.in_features}->2x{hidden} dtype={x.dtype} "
+                                           f"grad={torch.is_grad_enabled()}")
+        x1, x2 = self.w12(x).chunk(2, dim=-1)
+        return self.w3(F.silu(x1) * x2)
+
+
 class Block(nn.Module):
     def __init__(self, dim, num_heads, mlp_ratio=4.0, drop_path=0.0, init_values=None, eps=1e-6, act="gelu",
-                 attn_cls=None):
+                 attn_cls=None, mlp="mlp", mlp_hidden=None):
         super().__init__()
         self.norm1 = MixedLayerNorm(dim, eps=eps)
         # attn_cls(dim, num_heads): the attention of another model family (models/beit.py); default: Attention
@@ -352,7 +402,10 @@ class Block(nn.Module):
         self.ls1 = LayerScale(dim, init_values) if init_values else nn.Identity()
         self.drop_path1 = DropPath(drop_path)
         self.norm2 = MixedLayerNorm(dim, eps=eps)
-        self.mlp = Mlp(dim, int(dim * mlp_ratio), act)
+        if mlp not in MLP_KINDS:
+            raise ValueError(f"Block: unknown MLP {mlp!r}; known: {MLP_KINDS}")
+        hidden = int(mlp_hidden) if mlp_hidden else int(dim * mlp_ratio)
+        self.mlp = SwiGLU(dim, hidden) if mlp == "swiglu" else Mlp(dim, hidden, act)
         self.ls2 = LayerScale(dim, init_values) if init_values else nn.Identity()
         self.drop_path2 = DropPath(drop_path)
 
@@ -567,17 +620,23 @@ def _matrix_view(weight: torch.Tensor) -> torch.Tensor:
 class VisionTransformer(nn.Module):
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dim=768, depth=12,
                  num_heads=12, mlp_ratio=4.0, drop_path_rate=0.0, init_values=None, class_token=True,
-                 pre_norm=False, act="gelu", norm_eps=1e-6):
+                 pre_norm=False, act="gelu", norm_eps=1e-6, reg_tokens=0, mlp="mlp", mlp_hidden=None):
         super().__init__()
+        if reg_tokens and not class_token:
+            raise ValueError("VisionTransformer: register tokens stand behind a CLS token (class_token=False given)")
         self.embed_dim = self.num_features = embed_dim
         self.num_classes = num_classes
         self.patch_embed = PatchEmbed(img_size, patch_size, in_chans, embed_dim, bias=not pre_norm)
         n = self.patch_embed.num_patches
         self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim)) if class_token else None
         self.pos_embed = nn.Parameter(torch.randn(1, n + int(class_token), embed_dim) * 0.02)
+        # timm's name (the hub checkpoint says register_tokens); None without registers: no new key in any other model.
+        # The registers take no position row: pos_embed keeps its 1 + N rows
+        self.reg_token = nn.Parameter(torch.randn(1, reg_tokens, embed_dim) * 0.02) if reg_tokens else None
         dpr = [drop_path_rate * i / max(depth - 1, 1) for i in range(depth)]
         self.blocks = nn.ModuleList([
-            Block(embed_dim, num_heads, mlp_ratio, dpr[i], init_values, eps=norm_eps, act=act) for i in range(depth)])
+            Block(embed_dim, num_heads, mlp_ratio, dpr[i], init_values, eps=norm_eps, act=act, mlp=mlp,
+                  mlp_hidden=mlp_hidden) for i in range(depth)])
         self.norm = MixedLayerNorm(embed_dim, eps=norm_eps)
         # timm's name; None (not nn.Identity) without pre_norm: the module tree of every other model stays as it was
         self.norm_pre = MixedLayerNorm(embed_dim, eps=norm_eps) if pre_norm else None
@@ -606,7 +665,7 @@ class VisionTransformer(nn.Module):
         pe, p = self.patch_embed, self.patch_embed.patch_size
         w = pe.proj.weight
         t = self.pos_embed.shape[1]
-        return (self.norm_pre is None and pe.proj.bias is not None and w.dtype == torch.float32 and pe.proj.bias.dtype == torch.float32
+        return (self.norm_pre is None and self.reg_token is None and pe.proj.bias is not None and w.dtype == torch.float32 and pe.proj.bias.dtype == torch.float32
                 and w.is_contiguous() and x.shape[2] % p == 0 and x.shape[3] % p == 0
                 and (x.shape[2] // p) * (x.shape[3] // p) + int(self.cls_token is not None) == t
                 and ops.f32x3_gemm_supported(self.embed_dim, _pad32(w[0].numel()))
@@ -644,14 +703,21 @@ class VisionTransformer(nn.Module):
             return self._forward_features_f32x3(x)
         x = self.patch_embed(x)
         if self._fused_embed_ok(x):
-            # frozen pre-norm teacher: CLS row, position embedding and norm_pre in one kernel (csrc/vit_embed.hip)
+            # frozen pre-norm and / or register-token teacher: CLS row, position embedding, register rows and norm_pre
+            # in one kernel (csrc/vit_embed.hip)
             n = self.norm_pre
-            x = get_ops().vit_embed(x, self.cls_token, self.pos_embed, n.weight.detach().float(),
-                                    n.bias.detach().float(), n.eps)
+            gamma, beta, eps = (None, None, 1e-6) if n is None else (n.weight.detach().float(), n.bias.detach().float(),
+                                                                      n.eps)
+            if self.reg_token is None:
+                x = get_ops().vit_embed(x, self.cls_token, self.pos_embed, gamma, beta, eps)
+            else:
+                x = get_ops().vit_embed(x, self.cls_token, self.pos_embed, gamma, beta, eps, reg=self.reg_token)
         else:
             if self.cls_token is not None:
                 x = torch.cat([self.cls_token.expand(x.shape[0], -1, -1).to(x.dtype), x], dim=1)
             x = x + self.pos_embed.to(x.dtype)
+            if self.reg_token is not None:      # behind the CLS row, after the position embedding (the DINOv2 forward)
+                x = torch.cat([x[:, :1], self.reg_token.expand(x.shape[0], -1, -1).to(x.dtype), x[:, 1:]], dim=1)
             if self.norm_pre is not None:
                 x = self.norm_pre(x)
         masks = self._draw_drop_path_masks(x)
@@ -664,10 +730,16 @@ class VisionTransformer(nn.Module):
         return self.norm(x)
 
     def _fused_embed_ok(self, x) -> bool:
-        """frozen bf16 model with ``norm_pre`` on the device; every model without it keeps the torch assembly"""
-        n, cls = self.norm_pre, self.cls_token
-        return (n is not None and _FUSED_CLIP_DISPATCH and not torch.is_grad_enabled() and x.dtype == torch.bfloat16
-                and x.dim() == 3 and get_ops().handles(x) and n.elementwise_affine
+        """frozen bf16 model with ``norm_pre`` or register tokens on the device; every model with neither keeps the
+        torch assembly"""
+        n, cls, reg = self.norm_pre, self.cls_token, self.reg_token
+        if reg is not None:
+            if not _FUSED_DINOV2_DISPATCH or cls is None or reg.dtype != torch.bfloat16:
+                return False
+        elif n is None or not _FUSED_CLIP_DISPATCH:
+            return False
+        return (not torch.is_grad_enabled() and x.dtype == torch.bfloat16
+                and x.dim() == 3 and get_ops().handles(x) and (n is None or n.elementwise_affine)
                 and self.pos_embed.dtype == torch.bfloat16 and (cls is None or cls.dtype == torch.bfloat16)
                 and x.shape[1] + int(cls is not None) == self.pos_embed.shape[1]
                 and get_ops().vit_embed_supported(x.shape[-1]))
@@ -711,13 +783,39 @@ class ViTPreset(NamedTuple):
     norm_eps: float = 1e-6
     mean: tuple = IMAGENET_MEAN          # pretrained_cfg["mean"] / ["std"] of the timm model: the statistics that
     std: tuple = IMAGENET_STD            # normalise the teacher's clean view
+    reg_tokens: int = 0                  # DINOv2 register tokens
+    mlp: str = "mlp"                     # "mlp" (fc1 -> act -> fc2) or "swiglu" (ViT-g/14)
+    mlp_hidden: int | None = None        # hidden width where it is not 4 x embed_dim
 
 
-# name -> (embed_dim, depth, heads, patch, layerscale init[, pre_norm, act, class_token, norm_eps, mean, std])
+# name -> (embed_dim, depth, heads, patch, layerscale init[, pre_norm, act, class_token, norm_eps, mean, std,
+#          reg_tokens, mlp, mlp_hidden])
 # The CLIP / SigLIP rows were written WITHOUT timm at hand, from memory of timm 1.0.x (vision_transformer.py model
 # entrypoints and default_cfgs): check them against the installed timm before loading real weights, and override with
 # load_teacher(..., act=..., norm_eps=...) where they differ.  SigLIP's attention-pool head (attn_pool.*) is not built:
 # the teacher never uses a head, and load_state_dict(strict=False) drops those keys.
+def _dinov2(dim, depth, heads, reg=0, mlp="mlp", hidden=None):
+    return (dim, depth, heads, 14, 1.0, False, "gelu", True, 1e-6, IMAGENET_MEAN, IMAGENET_STD, reg, mlp, hidden)
+
+
+# The rest of the DINOv2 family: the register-token models (4 registers), ViT-g/14 (1536 wide, 40 blocks, 24 heads of 64,
+# SwiGLU of hidden width 4096 = the hub's int(4 * 1536 * 2 / 3) rounded up to a multiple of 8) and timm's names for the
+# same weights.  Written WITHOUT the hub code or timm at hand, from memory of facebookresearch/dinov2 (hubconf,
+# vision_transformer.py, swiglu_ffn.py) and timm 1.0.x: check widths and the chunk order (x1 = the first half is the
+# gated one) against the checkpoint before loading real weights.
+_DINOV2_MORE = {
+    "dinov2_vits14_reg": _dinov2(384, 12, 6, 4),
+    "dinov2_vitb14_reg": _dinov2(768, 12, 12, 4),
+    "dinov2_vitl14_reg": _dinov2(1024, 24, 16, 4),
+    "dinov2_vitg14": _dinov2(1536, 40, 24, 0, "swiglu", 4096),
+    "dinov2_vitg14_reg": _dinov2(1536, 40, 24, 4, "swiglu", 4096),
+    "vit_small_patch14_reg4_dinov2": _dinov2(384, 12, 6, 4),
+    "vit_base_patch14_reg4_dinov2": _dinov2(768, 12, 12, 4),
+    "vit_large_patch14_reg4_dinov2": _dinov2(1024, 24, 16, 4),
+    "vit_giant_patch14_dinov2": _dinov2(1536, 40, 24, 0, "swiglu", 4096),
+    "vit_giant_patch14_reg4_dinov2": _dinov2(1536, 40, 24, 4, "swiglu", 4096),
+}
+
 VIT_PRESETS = {
     "deit_tiny_patch16_224": (192, 12, 3, 16, None),
     "deit_small_patch16_224": (384, 12, 6, 16, None),
@@ -736,6 +834,7 @@ VIT_PRESETS = {
     "vit_base_patch16_clip_quickgelu_224": (768, 12, 12, 16, None, True, "quick_gelu", True, 1e-5, CLIP_MEAN, CLIP_STD),
     "vit_large_patch14_clip_quickgelu_224": (1024, 24, 16, 14, None, True, "quick_gelu", True, 1e-5, CLIP_MEAN, CLIP_STD),
     "vit_base_patch16_siglip_224": (768, 12, 12, 16, None, False, "gelu_tanh", False, 1e-6, HALF_MEAN, HALF_STD),
+    **_DINOV2_MORE,
 }
 
 
@@ -757,4 +856,25 @@ def create_vit(name: str, *, num_classes: int, img_size: int, drop_path_rate: fl
     kw.update({k: v for k, v in overrides.items() if k in ("embed_dim", "depth", "num_heads", "mlp_ratio")})
     return VisionTransformer(img_size=img_size, patch_size=patch_size or ps.patch, num_classes=num_classes,
                              drop_path_rate=drop_path_rate, init_values=ps.layerscale, class_token=ps.class_token,
-                             pre_norm=ps.pre_norm, act=act or ps.act, norm_eps=norm_eps or ps.norm_eps, **kw)
+                             pre_norm=ps.pre_norm, act=act or ps.act, norm_eps=norm_eps or ps.norm_eps,
+                             reg_tokens=ps.reg_tokens, mlp=ps.mlp, mlp_hidden=ps.mlp_hidden, **kw)
+
+
+def dinov2_state_dict(model: VisionTransformer, state: dict) -> dict:
+    """A DINOv2 state dict under the hub's or timm's key names -> this model's names: the hub's ``register_tokens`` is
+    ``reg_token`` here (timm's name), ``mask_token`` (the iBOT mask embedding, unused in a forward without masks) is
+    dropped, and for a SwiGLU model timm's ``blocks.i.mlp.fc1`` / ``fc2`` (SwiGLUPacked) are the hub's ``w12`` / ``w3``.
+    Every other key passes through."""
+    swiglu = any(isinstance(blk.mlp, SwiGLU) for blk in model.blocks)
+    out = {}
+    for key, value in state.items():
+        if key == "mask_token":
+            continue
+        if key == "register_tokens":
+            key = "reg_token"
+        elif swiglu and ".mlp.fc1." in key:
+            key = key.replace(".mlp.fc1.", ".mlp.w12.")
+        elif swiglu and ".mlp.fc2." in key:
+            key = key.replace(".mlp.fc2.", ".mlp.w3.")
+        out[key] = value
+    return out
