@@ -19,6 +19,7 @@
 // bf16 rounding of the output); its derivative in the backward epilogue: the exact form via Abramowitz-Stegun 7.1.26;
 // fp32 accumulation, one rounding to bf16 at the store.
 #include <type_traits>
+#include <utility>
 #include "basd_frag.h"
 
 namespace basd {
@@ -44,6 +45,16 @@ __device__ __forceinline__ void gemm_tile_of(int lin, int tiles_n, int ngroup, i
   nb = ng * ngroup + nbi;
 }
 
+// the exact-erf GELU (Abramowitz-Stegun 7.1.26): the forward of a build with -DBASD_GELU_EXACT
+__device__ __forceinline__ float gelu_erf(float x) {
+  const float z = fabsf(x) * 0.70710678118654752f;
+  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
+  const float poly = t * fmaf(t, fmaf(t, fmaf(t, fmaf(t, 1.061405429f, -1.453152027f), 1.421413741f), -0.284496736f),
+                              0.254829592f);
+  const float erf_abs = fmaf(-poly, __expf(-z * z), 1.0f);
+  return 0.5f * x * (1.0f + copysignf(erf_abs, x));
+}
+
 // Forward GELU of the epilogues: x Phi(x) with Phi(x) ~ 1 / (1 + 2^(-x p(x^2))), p an even quartic fitted (minimax over
 // |x| <= 12) to the exact erf form: |error| <= 2.6e-5 ABSOLUTE everywhere -- 1/150 of a bf16 ulp at |y| = 1, and the
 // bf16 output is what every consumer sees; the exact form below costs ~16 VALU instructions per element (two of them
@@ -59,18 +70,8 @@ __device__ __forceinline__ float gelu_fwd(float x) {
   return x * __builtin_amdgcn_rcpf(1.0f + e);
 }
 #else
-__device__ __forceinline__ float gelu_erf(float x);
 __device__ __forceinline__ float gelu_fwd(float x) { return gelu_erf(x); }
 #endif
-
-__device__ __forceinline__ float gelu_erf(float x) {
-  const float z = fabsf(x) * 0.70710678118654752f;
-  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
-  const float poly = t * fmaf(t, fmaf(t, fmaf(t, fmaf(t, 1.061405429f, -1.453152027f), 1.421413741f), -0.284496736f),
-                              0.254829592f);
-  const float erf_abs = fmaf(-poly, __expf(-z * z), 1.0f);
-  return 0.5f * x * (1.0f + copysignf(erf_abs, x));
-}
 
 // d/dx of the exact-erf GELU: Phi(x) + x phi(x); exp(-x^2 / 2) is the exponential the erf evaluation already needs
 __device__ __forceinline__ float gelu_erf_grad(float x) {
@@ -113,13 +114,35 @@ __device__ __forceinline__ float swiglu_gate(float a, float b) {
   return (a * __builtin_amdgcn_rcpf(1.0f + e)) * b;
 }
 
+// The epilogues.  The values are the template argument EPI of the kernels and the `epilogue` argument of gemm_dispatch.
+enum Epi : int {
+  EPI_NONE = 0,         // y <- acc
+  EPI_BIAS = 1,         // y <- acc + bias
+  EPI_GELU = 2,         // y <- gelu(acc + bias)
+  EPI_GELU_SAVE = 3,    // aux <- acc + bias, y <- gelu(aux)
+  EPI_GELU_BWD = 4,     // y <- acc * gelu'(aux)
+  EPI_F32 = 5,          // fp32 output of the bf16x3 product: persistent kernel only
+  EPI_QUICK_GELU = 6,   // y <- QuickGELU(acc + bias)
+  EPI_TANH_GELU = 7,    // y <- tanh-GELU(acc + bias)
+  EPI_SWIGLU = 8,       // SwiGLU gate over a packed w12 (ring and persistent ring kernels only; N = 2 H, output [M, H])
+};
+constexpr bool epi_has_bias(int e) {
+  return e == EPI_BIAS || e == EPI_GELU || e == EPI_GELU_SAVE || e == EPI_QUICK_GELU || e == EPI_TANH_GELU;
+}
+constexpr bool epi_has_act(int e) { return e == EPI_GELU || e == EPI_QUICK_GELU || e == EPI_TANH_GELU; }
+constexpr bool epi_saves_pre(int e) { return e == EPI_GELU_SAVE; }
+constexpr bool epi_reads_pre(int e) { return e == EPI_GELU_BWD; }
+constexpr bool epi_f32_out(int e) { return e == EPI_F32; }
+constexpr bool epi_gated(int e) { return e == EPI_SWIGLU; }
+
 template <int EPI>
 __device__ __forceinline__ float gemm_act(float v) {      // the forward activation of an epilogue without a saved tile
-  if (EPI == 2) return gelu_fwd(v);
-  if (EPI == 6) return quick_gelu_fwd(v);
-  if (EPI == 7) return gelu_tanh_fwd(v);
+  if (EPI == EPI_GELU) return gelu_fwd(v);
+  if (EPI == EPI_QUICK_GELU) return quick_gelu_fwd(v);
+  if (EPI == EPI_TANH_GELU) return gelu_tanh_fwd(v);
   return v;
 }
+
 
 // Epilogue shared by both kernels.  The accumulator tile of a wave is [n][m] with 4 consecutive n per lane: stored
 // straight from registers that is an 8-byte store per (lane, tile), 16 rows x 32 B per wave instruction -- partial
@@ -146,7 +169,7 @@ __device__ __forceinline__ void gemm_epilogue(f32x4 (&acc)[NT][8], unsigned char
     }
   };
   __builtin_amdgcn_s_barrier();                    // every wave is done with the operand ring
-  if (EPI == 4) {                                  // the saved pre-activation tile comes in the way the result goes out
+  if (epi_reads_pre(EPI)) {                        // the saved pre-activation tile comes in the way the result goes out
 #pragma unroll
     for (int it = 0; it < 2 * CH; ++it) {
       const int item = it * 64 + lane;
@@ -161,7 +184,7 @@ __device__ __forceinline__ void gemm_epilogue(f32x4 (&acc)[NT][8], unsigned char
   for (int i = 0; i < NT; ++i) {
     const int nl = i * 16 + 4 * (lane >> 4);       // local column of this lane's 4 values
     float bv[4] = {0.f, 0.f, 0.f, 0.f};
-    if ((EPI == 1 || EPI == 2 || EPI == 3 || EPI == 6 || EPI == 7) && bias != nullptr) {
+    if (epi_has_bias(EPI) && bias != nullptr) {
       const u16x4 b4 = *reinterpret_cast<const u16x4*>(bias + n0 + wn * WN + nl);
 #pragma unroll
       for (int r = 0; r < 4; ++r) bv[r] = bf16_bits_to_f32(b4[r]);
@@ -170,18 +193,18 @@ __device__ __forceinline__ void gemm_epilogue(f32x4 (&acc)[NT][8], unsigned char
     for (int j = 0; j < 8; ++j) {
       u16x4* cell = reinterpret_cast<u16x4*>(region + (j * 16 + (lane & 15)) * ROWB + nl * 2);
       u16x4 o, pre;
-      if (EPI == 4) pre = *cell;
+      if (epi_reads_pre(EPI)) pre = *cell;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float v = acc[i][j][r] + bv[r];
-        if (EPI == 2 || EPI == 6 || EPI == 7) v = gemm_act<EPI>(v);
-        if (EPI == 4) v *= gelu_erf_grad(bf16_bits_to_f32(pre[r]));
+        if (epi_has_act(EPI)) v = gemm_act<EPI>(v);
+        if (epi_reads_pre(EPI)) v *= gelu_erf_grad(bf16_bits_to_f32(pre[r]));
         o[r] = f32_to_bf16_bits(v);
       }
       *cell = o;
     }
   }
-  if (EPI == 3) {                                  // pre-activation out (saved for backward), then GELU of the ROUNDED
+  if (epi_saves_pre(EPI)) {                        // pre-activation out (saved for backward), then GELU of the ROUNDED
     flush(aux);                                    // value in place (what nn.GELU sees after a bf16 nn.Linear)
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
@@ -242,9 +265,9 @@ __device__ __forceinline__ void gemm_epilogue_swiglu(f32x4 (&acc)[4][8], unsigne
   }
 }
 
-// EPI: 0 = none, 1 = + bias, 2 = gelu(+ bias), 3 = aux <- (+ bias), y <- gelu(aux), 4 = y <- acc * gelu'(aux)
-// (5 = fp32 output of the bf16x3 product: persistent kernel only), 6 = QuickGELU(+ bias), 7 = tanh-GELU(+ bias),
-// 8 = SwiGLU gate over a packed w12 (ring and persistent ring kernels only; N = 2 H, output [M, H])
+// fragment read offset inside a sub-tile: row lane & 15, 16-byte k chunk lane >> 4
+__device__ __forceinline__ int gemm_frag_off(int lane) { return gemm_swz((lane & 15) * 64 + (lane >> 4) * 16); }
+
 template <int BN, int EPI>
 __global__ __launch_bounds__(512) void gemm_bf16_nt_kernel(const unsigned short* __restrict__ X,
                                                            const unsigned short* __restrict__ W,
@@ -299,9 +322,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_nt_kernel(const unsigned short*
   for (int i = 0; i < NT; ++i)
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  // fragment read offset inside a sub-tile: row lane & 15, 16-byte k chunk lane >> 4
-  const int frag_off = gemm_swz((lane & 15) * 64 + (lane >> 4) * 16);
+  const int frag_off = gemm_frag_off(lane);
   const int a_sub0 = (wm * 8) * 2;                 // first sub-tile of this wave's activation rows
   const int b_sub0 = NSUB_A + (wn * NT) * 2;       // first sub-tile of this wave's weight rows
   constexpr int NPIECE = NSUB / 8;                 // LDS-DMA pieces per wave and K step (8, 7 or 6)
@@ -406,7 +427,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_ring_kernel(const unsigned shor
   for (int i = 0; i < NT; ++i)
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const int frag_off = gemm_swz((lane & 15) * 64 + (lane >> 4) * 16);
+  const int frag_off = gemm_frag_off(lane);
   const int a_sub0 = (wm * 8) * 2, b_sub0 = (wn * NT) * 2;
 
   const int nk = K / GBK;
@@ -465,7 +486,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_ring_kernel(const unsigned shor
     k_step(t, std::false_type{});
   }
 
-  if constexpr (EPI == 8) gemm_epilogue_swiglu(acc, g_lds, bias, Y, M, N >> 1, m0, n0, wm, wn, lane, wave);
+  if constexpr (epi_gated(EPI)) gemm_epilogue_swiglu(acc, g_lds, bias, Y, M, N >> 1, m0, n0, wm, wn, lane, wave);
   else gemm_epilogue<BN, NT, EPI>(acc, g_lds, bias, aux, Y, M, N, m0, n0, wm, wn, lane, wave);
 }
 
@@ -479,27 +500,39 @@ __global__ __launch_bounds__(512) void gemm_bf16_ring_kernel(const unsigned shor
 // in that final layout (16-byte loads).  Leaves the LDS ring alone, so the operands of the NEXT tile keep streaming in.
 // EPI 5: fp32 output of pitch N, columns >= N are not stored (the weight matrix is padded to the tile width, the output
 // is not): two 16-byte stores per 8 columns.
+// the butterfly pair on one pair of values: (the value of tile i, of tile i ^ 1) -> the lane-exchanged pair
+__device__ __forceinline__ f32x2 gemm_butterfly(float a, float b) {
+  typedef unsigned int eu32x2 __attribute__((ext_vector_type(2)));
+  const eu32x2 s1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+  const eu32x2 s2 = __builtin_amdgcn_permlane16_swap(s1[0], s1[1], false, false);
+  return (f32x2){__uint_as_float(s2[0]), __uint_as_float(s2[1])};
+}
+// row block j of the four tiles: v[2 h + k][r] is column h * 32 + q * 8 + 4 k + r of this lane's row
+__device__ __forceinline__ void gemm_butterfly_block(const f32x4 (&acc)[4][8], int j, float (&v)[4][4]) {
+#pragma unroll
+  for (int p = 0; p < 2; ++p)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const f32x2 s = gemm_butterfly(acc[2 * p][j][r], acc[2 * p + 1][j][r]);
+      v[2 * p][r] = s[0];
+      v[2 * p + 1][r] = s[1];
+    }
+}
+__device__ __forceinline__ void gemm_store_nt(const uint4& o, void* dst) {       // 16 bytes, non-temporal
+  __builtin_nontemporal_store((u32x4){o.x, o.y, o.z, o.w}, reinterpret_cast<u32x4*>(dst));
+}
+
 template <int EPI>
 __device__ __forceinline__ void gemm_epilogue_direct(f32x4 (&acc)[4][8], const unsigned short* bias,
                                                      unsigned short* aux, unsigned short* Y, int M, int N, int row0,
                                                      int col0, int lane) {
-  typedef unsigned int eu32x2 __attribute__((ext_vector_type(2)));
   const int q = lane >> 4, r16 = lane & 15;
-  if constexpr (EPI == 5) {
+  if constexpr (epi_f32_out(EPI)) {
     float* Y32 = reinterpret_cast<float*>(Y);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       float v[4][4];
-#pragma unroll
-      for (int p = 0; p < 2; ++p)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          eu32x2 s1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[2 * p][j][r]),
-                                                       __float_as_uint(acc[2 * p + 1][j][r]), false, false);
-          eu32x2 s2 = __builtin_amdgcn_permlane16_swap(s1[0], s1[1], false, false);
-          v[2 * p][r] = __uint_as_float(s2[0]);
-          v[2 * p + 1][r] = __uint_as_float(s2[1]);
-        }
+      gemm_butterfly_block(acc, j, v);
       const int row = row0 + j * 16 + r16;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
@@ -521,44 +554,29 @@ __device__ __forceinline__ void gemm_epilogue_direct(f32x4 (&acc)[4][8], const u
   for (int h = 0; h < 2; ++h)
 #pragma unroll
     for (int k = 0; k < 8; ++k) bv[h][k] = 0.f;
-  if ((EPI == 1 || EPI == 2 || EPI == 3 || EPI == 6 || EPI == 7) && bias != nullptr) {
+  if (epi_has_bias(EPI) && bias != nullptr) {
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const uint4 b8 = *reinterpret_cast<const uint4*>(bias + col0 + h * 32 + q * 8);
-      const unsigned int w4[4] = {b8.x, b8.y, b8.z, b8.w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        bv[h][2 * k] = __uint_as_float(w4[k] << 16);
-        bv[h][2 * k + 1] = __uint_as_float(w4[k] & 0xffff0000u);
-      }
-    }
+    for (int h = 0; h < 2; ++h) unpack8(*reinterpret_cast<const uint4*>(bias + col0 + h * 32 + q * 8), bv[h]);
   }
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     float v[4][4];
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        eu32x2 s1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[2 * p][j][r]),
-                                                     __float_as_uint(acc[2 * p + 1][j][r]), false, false);
-        eu32x2 s2 = __builtin_amdgcn_permlane16_swap(s1[0], s1[1], false, false);
-        v[2 * p][r] = __uint_as_float(s2[0]);
-        v[2 * p + 1][r] = __uint_as_float(s2[1]);
-      }
+    gemm_butterfly_block(acc, j, v);
     const int row = row0 + j * 16 + r16;
     if (row < M) {
       const size_t off = (size_t)row * N + col0 + q * 8;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        float f[8];
+        float f[8], pre[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) f[k] = v[2 * h + (k >> 2)][k & 3] + bv[h][k];
-        if (EPI == 2 || EPI == 6 || EPI == 7) {
+        if (epi_has_act(EPI)) {
 #pragma unroll
           for (int k = 0; k < 8; ++k) f[k] = gemm_act<EPI>(f[k]);
         }
-        if (EPI == 4) {
+        if (epi_reads_pre(EPI)) {
+          // unpacked pair by pair in front of its products: with unpack8 ahead of the eight products the persistent
+          // kernel's instruction schedule changes
           const uint4 p8 = *reinterpret_cast<const uint4*>(aux + off + h * 32);
           const unsigned int w4[4] = {p8.x, p8.y, p8.z, p8.w};
 #pragma unroll
@@ -567,18 +585,15 @@ __device__ __forceinline__ void gemm_epilogue_direct(f32x4 (&acc)[4][8], const u
             f[2 * k + 1] *= gelu_erf_grad(__uint_as_float(w4[k] & 0xffff0000u));
           }
         }
-        uint4 o = make_uint4(pack_bf16_bits(f[0], f[1]), pack_bf16_bits(f[2], f[3]), pack_bf16_bits(f[4], f[5]),
-                             pack_bf16_bits(f[6], f[7]));
-        if (EPI == 3) {
-          __builtin_nontemporal_store((u32x4){o.x, o.y, o.z, o.w}, reinterpret_cast<u32x4*>(aux + off + h * 32));   // pre-activation, rounded
-          const unsigned int w4[4] = {o.x, o.y, o.z, o.w};
-          unsigned int g4[4];
+        uint4 o = pack8(f);
+        if (epi_saves_pre(EPI)) {
+          gemm_store_nt(o, aux + off + h * 32);     // pre-activation, rounded
+          unpack8(o, pre);
 #pragma unroll
-          for (int k = 0; k < 4; ++k)
-            g4[k] = pack_bf16_bits(gelu_fwd(__uint_as_float(w4[k] << 16)), gelu_fwd(__uint_as_float(w4[k] & 0xffff0000u)));
-          o = make_uint4(g4[0], g4[1], g4[2], g4[3]);
+          for (int k = 0; k < 8; ++k) f[k] = gelu_fwd(pre[k]);
+          o = pack8(f);
         }
-        __builtin_nontemporal_store((u32x4){o.x, o.y, o.z, o.w}, reinterpret_cast<u32x4*>(Y + off + h * 32));
+        gemm_store_nt(o, Y + off + h * 32);
       }
     }
   }
@@ -592,7 +607,6 @@ __device__ __forceinline__ void gemm_epilogue_direct(f32x4 (&acc)[4][8], const u
 __device__ __forceinline__ void gemm_epilogue_direct_swiglu(f32x4 (&acc)[4][8], const unsigned short* bias,
                                                             unsigned short* Y, int M, int H, int row0, int col0,
                                                             int lane) {
-  typedef unsigned int eu32x2 __attribute__((ext_vector_type(2)));
   const int q = lane >> 4, r16 = lane & 15;
   float b1[2][4], b2[2][4];
 #pragma unroll
@@ -615,17 +629,14 @@ __device__ __forceinline__ void gemm_epilogue_direct_swiglu(f32x4 (&acc)[4][8], 
     for (int r = 0; r < 4; ++r) {
       const float g0 = swiglu_gate(acc[0][j][r] + b1[0][r], acc[2][j][r] + b2[0][r]);
       const float g1 = swiglu_gate(acc[1][j][r] + b1[1][r], acc[3][j][r] + b2[1][r]);
-      eu32x2 s1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(g0), __float_as_uint(g1), false, false);
-      eu32x2 s2 = __builtin_amdgcn_permlane16_swap(s1[0], s1[1], false, false);
-      f[r] = __uint_as_float(s2[0]);
-      f[4 + r] = __uint_as_float(s2[1]);
+      const f32x2 s = gemm_butterfly(g0, g1);
+      f[r] = s[0];
+      f[4 + r] = s[1];
     }
     const int row = row0 + j * 16 + r16;
     if (row < M) {
       const size_t off = (size_t)row * H + (col0 >> 1) + q * 8;
-      const uint4 o = make_uint4(pack_bf16_bits(f[0], f[1]), pack_bf16_bits(f[2], f[3]), pack_bf16_bits(f[4], f[5]),
-                                 pack_bf16_bits(f[6], f[7]));
-      __builtin_nontemporal_store((u32x4){o.x, o.y, o.z, o.w}, reinterpret_cast<u32x4*>(Y + off));
+      gemm_store_nt(pack8(f), Y + off);
     }
   }
 }
@@ -681,8 +692,9 @@ __global__ __launch_bounds__(512) void gemm_bf16_pring_kernel(const unsigned sho
   // split of the weights, whose rows hold the splits side by side: pitch K = 3 ka); N = columns stored = output pitch.
   extern __shared__ __align__(16) unsigned char g_lds[];
   constexpr int NT = 4, UNIT = 32768, NSLOT = 5;
-  constexpr int NST = (EPI == 3) ? 32 : (EPI == 8) ? 8 : 16;   // global stores of a wave per epilogue
-  const int KA = EPI == 5 ? ka : K;                         // row pitch of the activation panel
+  constexpr int NST = epi_saves_pre(EPI) ? 32 : epi_gated(EPI) ? 8 : 16;   // global stores of a wave per epilogue
+  constexpr bool F32_OUT = epi_f32_out(EPI);                // (a constant: a call inside a run-time condition changes the code)
+  const int KA = F32_OUT ? ka : K;                         // row pitch of the activation panel
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
@@ -742,7 +754,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pring_kernel(const unsigned sho
   auto wrap = [](int s) { return s >= NSLOT ? s - NSLOT : s; };
 
   f32x4 acc[NT][8];
-  const int frag_off = gemm_swz((lane & 15) * 64 + (lane >> 4) * 16);
+  const int frag_off = gemm_frag_off(lane);
   const int a_sub0 = (wm * 8) * 2, b_sub0 = (wn * NT) * 2;
 
   // ---- one K step (64 deep = two k-blocks of 32), software-pipelined through registers so that no MFMA group waits
@@ -824,7 +836,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pring_kernel(const unsigned sho
     for (int t = 0; t < nk; ++t) {
       if (t == nk - 2) set_off_a(m0n);                      // every A unit of this tile has been issued
       int ta = t + 2;                                       // K step of the activation panel (EPI 5: modulo its depth)
-      if (EPI == 5 && ta < nk) {
+      if (F32_OUT && ta < nk) {
         const int nka = KA / GBK;
         ta -= ta >= nka ? nka : 0;
         ta -= ta >= nka ? nka : 0;
@@ -856,10 +868,10 @@ __global__ __launch_bounds__(512) void gemm_bf16_pring_kernel(const unsigned sho
       slot = s_a1;
     }
     const bool full_rows = m0 + GBM <= M;                   // every store of the epilogue is issued by every wave
-    if constexpr (EPI == 8) gemm_epilogue_direct_swiglu(acc, bias, Y, M, N >> 1, m0 + wm * 128, n0 + wn * 64, lane);
+    if constexpr (epi_gated(EPI)) gemm_epilogue_direct_swiglu(acc, bias, Y, M, N >> 1, m0 + wm * 128, n0 + wn * 64, lane);
     else gemm_epilogue_direct<EPI>(acc, bias, aux, Y, M, N, m0 + wm * 128, n0 + wn * 64, lane);
-    st_pending = (full_rows && EPI != 5) ? NST : 0;
-    if (!full_rows || EPI == 5) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // ragged rows (EPI 5: columns): not every wave issues every store
+    st_pending = (full_rows && !F32_OUT) ? NST : 0;
+    if (!full_rows || F32_OUT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // ragged rows (EPI 5: columns): not every wave issues every store
     if (!has_next) break;
     ++o;
     m0 = m0n;
@@ -883,16 +895,22 @@ static int gemm_column_group(int tiles_n, int bn, int K) {
   return best;
 }
 
-template <int EPI>
-static void launch_gemm_ring(const void* x, const void* w, const void* bias, void* aux, void* y, int M, int N, int K,
-                             hipStream_t st) {
-  const int tiles_n = N / 256, mblocks = (M + GBM - 1) / GBM;
+// the two non-persistent kernels: the ring kernel at BN = 256 (five 32 KiB units), the two-stage kernel at 192 / 128
+template <int BN, int EPI>
+static void launch_gemm(const void* x, const void* w, const void* bias, void* aux, void* y, int M, int N, int K,
+                        hipStream_t st) {
+  const int tiles_n = N / BN, mblocks = (M + GBM - 1) / GBM;
   const int groups = (mblocks + 7) / 8;
-  const int ngroup = gemm_column_group(tiles_n, 256, K);
-  allow_full_lds((const void*)gemm_bf16_ring_kernel<EPI>);
-  hipLaunchKernelGGL((gemm_bf16_ring_kernel<EPI>), dim3(groups * tiles_n * 8), dim3(512), 5 * 32768, st,
-                     (const unsigned short*)x, (const unsigned short*)w, (const unsigned short*)bias,
-                     (unsigned short*)aux, (unsigned short*)y, M, N, K, tiles_n, mblocks, ngroup);
+  const int ngroup = gemm_column_group(tiles_n, BN, K);
+  auto kernel = [] {
+    if constexpr (BN == 256) return gemm_bf16_ring_kernel<EPI>;
+    else return gemm_bf16_nt_kernel<BN, EPI>;
+  }();
+  const size_t lds = BN == 256 ? 5 * 32768 : 2 * (size_t)(GBM * GBK * 2 + BN * GBK * 2);
+  allow_full_lds((const void*)kernel);
+  hipLaunchKernelGGL(kernel, dim3(groups * tiles_n * 8), dim3(512), lds, st, (const unsigned short*)x,
+                     (const unsigned short*)w, (const unsigned short*)bias, (unsigned short*)aux, (unsigned short*)y, M,
+                     N, K, tiles_n, mblocks, ngroup);
 }
 
 // grid of the persistent kernel: 8 P workgroups, P <= 32 per XCD, every XCD's stream at least P tiles long
@@ -921,46 +939,18 @@ static void launch_gemm_pring(const void* x, const void* w, const void* bias, vo
                      (unsigned short*)aux, (unsigned short*)y, M, N, K, tiles_n, mblocks, ngroup, chunk_tiles, ka, P);
 }
 
-template <int BN, int EPI>
-static void launch_gemm(const void* x, const void* w, const void* bias, void* aux, void* y, int M, int N, int K,
-                        hipStream_t st) {
-  const int tiles_n = N / BN, mblocks = (M + GBM - 1) / GBM;
-  const int groups = (mblocks + 7) / 8;
-  const int ngroup = gemm_column_group(tiles_n, BN, K);
-  const size_t lds = 2 * (size_t)(GBM * GBK * 2 + BN * GBK * 2);
-  allow_full_lds((const void*)gemm_bf16_nt_kernel<BN, EPI>);
-  hipLaunchKernelGGL((gemm_bf16_nt_kernel<BN, EPI>), dim3(groups * tiles_n * 8), dim3(512), lds, st,
-                     (const unsigned short*)x, (const unsigned short*)w, (const unsigned short*)bias,
-                     (unsigned short*)aux, (unsigned short*)y, M, N, K, tiles_n, mblocks, ngroup);
-}
+// Which kernel a shape takes.  wide_only: the caller's epilogue exists in the 256-column kernels only.
+enum GemmRoute { GEMM_PRING, GEMM_RING, GEMM_NT192, GEMM_NT128 };
 
-}  // namespace basd
-
-static int gemm_dispatch(const void* x, const void* w, const void* bias, void* aux, void* y, int64_t M, int N, int K,
-                         int epilogue, int tile_run, void* stream, const char* what) {
-  using namespace basd;
-  if (M <= 0) return BASD_OK;
-  if (M > 0x7fffff00LL) return fail(BASD_ERR_SHAPE, "%s: M = %lld too large", what, (long long)M);
-  if (K % GBK || K < GBK || (N % 256 && N % 192 && N % 128) || N < 128)
-    return fail(BASD_ERR_SHAPE, "%s: need K %% 64 == 0 and N a multiple of 256, 192 or 128 (got N=%d K=%d)", what, N, K);
-  hipStream_t st = (hipStream_t)stream;
-  const int m = (int)M;
-#define BASD_GEMM_EPI(LAUNCH)                                          \
-  do {                                                                 \
-    switch (epilogue) {                                                \
-      case 0: LAUNCH(0); break;                                        \
-      case 1: LAUNCH(1); break;                                        \
-      case 2: LAUNCH(2); break;                                        \
-      case 3: LAUNCH(3); break;                                        \
-      case 6: LAUNCH(6); break;                                        \
-      case 7: LAUNCH(7); break;                                        \
-      default: LAUNCH(4); break;                                       \
-    }                                                                  \
-  } while (0)
+static GemmRoute gemm_route(int M, int N, int K, bool wide_only) {
+  // the persistent kernel where every XCD has at least one tile per CU of a full grid and K >= 3 steps (measured on one
+  // MI355X, M = 50 432: fc1 + GELU 288 vs 327 us, fc2 220 vs 237, qkv 181 vs 207, proj 68 vs 76, student fc1 51 vs 66)
+  if (pring_cus_per_xcd(M, N) == 32 && K >= 192) return GEMM_PRING;
+  if (wide_only) return GEMM_RING;
   // tile width: among the widths that divide N, the one whose tile count fills the 256 CUs best in whole rounds
   // (fc2 of ViT-B: 197 x 3 tiles of 256 columns = 2.3 rounds -> 3; 197 x 6 tiles of 128 = 4.6 -> 5: 77 % -> 92 %);
   // ties go to the wider tile (fewer re-reads of the activation rows)
-  const int mblocks = (m + GBM - 1) / GBM;
+  const int mblocks = (M + GBM - 1) / GBM;
   int best_bn = 0;
   double best_eff = -1.0;
   for (int bn : {256, 192, 128}) {
@@ -971,24 +961,48 @@ static int gemm_dispatch(const void* x, const void* w, const void* bias, void* a
                                                        // two-stage tiles run at 0.6 - 0.8 of the ring kernel's rate
     if (eff > best_eff + 1e-9) { best_eff = eff; best_bn = bn; }
   }
-  // the persistent kernel where every XCD has at least one tile per CU of a full grid and K >= 3 steps (measured on one
-  // MI355X, M = 50 432: fc1 + GELU 288 vs 327 us, fc2 220 vs 237, qkv 181 vs 207, proj 68 vs 76, student fc1 51 vs 66)
-  if (pring_cus_per_xcd(m, N) == 32 && K >= 192) {
-#define BASD_PRING(E) launch_gemm_pring<E>(x, w, bias, aux, y, m, N, K, tile_run, st)
-    BASD_GEMM_EPI(BASD_PRING);
-#undef BASD_PRING
-    return check_launch(what);
-  }
-#define BASD_RING(E) launch_gemm_ring<E>(x, w, bias, aux, y, m, N, K, st)
-#define BASD_NT192(E) launch_gemm<192, E>(x, w, bias, aux, y, m, N, K, st)
-#define BASD_NT128(E) launch_gemm<128, E>(x, w, bias, aux, y, m, N, K, st)
-  if (best_bn == 256) BASD_GEMM_EPI(BASD_RING);
-  else if (best_bn == 192) BASD_GEMM_EPI(BASD_NT192);
-  else BASD_GEMM_EPI(BASD_NT128);
-#undef BASD_RING
-#undef BASD_NT192
-#undef BASD_NT128
-#undef BASD_GEMM_EPI
+  return best_bn == 256 ? GEMM_RING : best_bn == 192 ? GEMM_NT192 : GEMM_NT128;
+}
+
+// Runtime epilogue code -> template argument: f(std::integral_constant<int, E>) for the one E of the list that equals
+// `epilogue`; false, and nothing launched, if none does.
+template <int... E, class F>
+static bool gemm_with_epi(std::integer_sequence<int, E...>, int epilogue, F&& f) {
+  return ((epilogue == E && (f(std::integral_constant<int, E>{}), true)) || ...);
+}
+// the epilogues gemm_dispatch serves (EPI_F32 and EPI_SWIGLU have entries and launches of their own)
+using GemmDispatchEpis = std::integer_sequence<int, EPI_NONE, EPI_BIAS, EPI_GELU, EPI_GELU_SAVE, EPI_GELU_BWD,
+                                               EPI_QUICK_GELU, EPI_TANH_GELU>;
+
+// The M / K / column-count refusals of every entry.  n_ok: the entry's own rule on its column count n_name = n.
+static int gemm_check_shape(const char* what, int64_t M, int K, bool n_ok, const char* n_rule, const char* n_name, int n) {
+  if (M > 0x7fffff00LL) return fail(BASD_ERR_SHAPE, "%s: M = %lld too large", what, (long long)M);
+  if (K % GBK || K < GBK || !n_ok)
+    return fail(BASD_ERR_SHAPE, "%s: need K %% 64 == 0 and %s (got %s=%d K=%d)", what, n_rule, n_name, n, K);
+  return BASD_OK;
+}
+
+}  // namespace basd
+
+static int gemm_dispatch(const void* x, const void* w, const void* bias, void* aux, void* y, int64_t M, int N, int K,
+                         int epilogue, int tile_run, void* stream, const char* what) {
+  using namespace basd;
+  if (M <= 0) return BASD_OK;
+  const bool n_ok = N >= 128 && !(N % 256 && N % 192 && N % 128);
+  if (const int rc = gemm_check_shape(what, M, K, n_ok, "N a multiple of 256, 192 or 128", "N", N)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int m = (int)M;
+  const GemmRoute route = gemm_route(m, N, K, false);
+  const bool known = gemm_with_epi(GemmDispatchEpis{}, epilogue, [&](auto epi) {
+    constexpr int E = decltype(epi)::value;
+    switch (route) {
+      case GEMM_PRING: launch_gemm_pring<E>(x, w, bias, aux, y, m, N, K, tile_run, st); break;
+      case GEMM_RING: launch_gemm<256, E>(x, w, bias, aux, y, m, N, K, st); break;
+      case GEMM_NT192: launch_gemm<192, E>(x, w, bias, aux, y, m, N, K, st); break;
+      case GEMM_NT128: launch_gemm<128, E>(x, w, bias, aux, y, m, N, K, st); break;
+    }
+  });
+  if (!known) return fail(BASD_ERR_SHAPE, "%s: unknown epilogue %d", what, epilogue);
   return check_launch(what);
 }
 
@@ -996,7 +1010,7 @@ extern "C" int basd_gemm_bf16(const void* x, const void* w, const void* bias, vo
                               int epilogue, int tile_run, void* stream) {
   using namespace basd;
   if (epilogue < 0 || epilogue > 2) return fail(BASD_ERR_SHAPE, "gemm_bf16: epilogue %d not in {0, 1, 2}", epilogue);
-  if (epilogue == 1 && bias == nullptr) epilogue = 0;
+  if (epilogue == EPI_BIAS && bias == nullptr) epilogue = EPI_NONE;
   return gemm_dispatch(x, w, bias, nullptr, y, M, N, K, epilogue, tile_run, stream, "gemm_bf16");
 }
 
@@ -1004,37 +1018,35 @@ extern "C" int basd_gemm_bf16_act(const void* x, const void* w, const void* bias
                                   int act, int tile_run, void* stream) {
   using namespace basd;
   if (act < 0 || act > 3) return fail(BASD_ERR_SHAPE, "gemm_bf16_act: act %d not in {0, 1, 2, 3}", act);
-  // act -> EPI: none = + bias (or nothing), erf-GELU = the epilogue basd_gemm_bf16 runs, QuickGELU, tanh-GELU
-  const int epilogue = act == 0 ? (bias != nullptr ? 1 : 0) : act == 1 ? 2 : act == 2 ? 6 : 7;
+  // act: none = + bias (or nothing), erf-GELU = the epilogue basd_gemm_bf16 runs, QuickGELU, tanh-GELU
+  const int epilogue = act == 0 ? (bias != nullptr ? EPI_BIAS : EPI_NONE)
+                       : act == 1 ? EPI_GELU : act == 2 ? EPI_QUICK_GELU : EPI_TANH_GELU;
   return gemm_dispatch(x, w, bias, nullptr, y, M, N, K, epilogue, tile_run, stream, "gemm_bf16_act");
 }
 
 extern "C" int basd_gemm_bf16_swiglu(const void* x, const void* w12p, const void* bias12p, void* y, int64_t M, int H,
                                      int K, int tile_run, void* stream) {
   using namespace basd;
-  // only the 256-column kernels carry the gated epilogue (the 192-column tile has three 16-column tiles per wave and
-  // cannot pair them): persistent ring where basd_gemm_bf16 would take it for N = 2 H, else the ring kernel
-  if (H < 128 || H % 128 || H > (1 << 29) || K % GBK || K < GBK)
-    return fail(BASD_ERR_SHAPE, "gemm_bf16_swiglu: need H %% 128 == 0 and K %% 64 == 0 (got H=%d K=%d)", H, K);
-  if (M > 0x7fffff00LL) return fail(BASD_ERR_SHAPE, "gemm_bf16_swiglu: M = %lld too large", (long long)M);
+  const bool h_ok = H >= 128 && H % 128 == 0 && H <= (1 << 29);
+  if (const int rc = gemm_check_shape("gemm_bf16_swiglu", M, K, h_ok, "H a multiple of 128", "H", H)) return rc;
   if (M <= 0) return BASD_OK;
   if (x == nullptr || w12p == nullptr || y == nullptr) return fail(BASD_ERR_SHAPE, "gemm_bf16_swiglu: null x / w12p / y");
   const int m = (int)M, N = 2 * H;
   hipStream_t st = (hipStream_t)stream;
-  if (pring_cus_per_xcd(m, N) == 32 && K >= 192) launch_gemm_pring<8>(x, w12p, bias12p, nullptr, y, m, N, K, tile_run, st);
-  else launch_gemm_ring<8>(x, w12p, bias12p, nullptr, y, m, N, K, st);
+  // only the 256-column kernels carry the gated epilogue (the 192-column tile has three 16-column tiles per wave and
+  // cannot pair them): persistent ring where basd_gemm_bf16 would take it for N = 2 H, else the ring kernel
+  if (gemm_route(m, N, K, true) == GEMM_PRING) launch_gemm_pring<EPI_SWIGLU>(x, w12p, bias12p, nullptr, y, m, N, K, tile_run, st);
+  else launch_gemm<256, EPI_SWIGLU>(x, w12p, bias12p, nullptr, y, m, N, K, st);
   return check_launch("gemm_bf16_swiglu");
 }
 
 extern "C" int basd_gemm_bf16x3_f32(const void* x, const void* w3, float* y, int64_t M, int N, int K, void* stream) {
   using namespace basd;
   if (M <= 0) return BASD_OK;
-  if (M > 0x7fffff00LL) return fail(BASD_ERR_SHAPE, "gemm_bf16x3_f32: M = %lld too large", (long long)M);
-  if (K % GBK || K < GBK || N < 1 || N % 8)
-    return fail(BASD_ERR_SHAPE, "gemm_bf16x3_f32: need K %% 64 == 0 and N %% 8 == 0 (got N=%d K=%d)", N, K);
+  if (const int rc = gemm_check_shape("gemm_bf16x3_f32", M, K, N >= 1 && N % 8 == 0, "N a multiple of 8", "N", N)) return rc;
   if ((M + GBM - 1) / GBM < 8) return fail(BASD_ERR_SHAPE, "gemm_bf16x3_f32: needs M > 1792 rows (got %lld)", (long long)M);
   if (K < 2 * GBK) return fail(BASD_ERR_SHAPE, "gemm_bf16x3_f32: K >= 128 required (got %d)", K);
-  launch_gemm_pring<5>(x, w3, nullptr, nullptr, y, (int)M, N, 3 * K, 0, (hipStream_t)stream, K);
+  launch_gemm_pring<EPI_F32>(x, w3, nullptr, nullptr, y, (int)M, N, 3 * K, 0, (hipStream_t)stream, K);
   return check_launch("gemm_bf16x3_f32");
 }
 
@@ -1042,7 +1054,7 @@ extern "C" int basd_gemm_bf16_gelu_fwd(const void* x, const void* w, const void*
                                        int N, int K, int tile_run, void* stream) {
   using namespace basd;
   if (M > 0 && (pre == nullptr || y == nullptr)) return fail(BASD_ERR_SHAPE, "gemm_bf16_gelu_fwd: pre and y are required");
-  return gemm_dispatch(x, w, bias, pre, y, M, N, K, 3, tile_run, stream, "gemm_bf16_gelu_fwd");
+  return gemm_dispatch(x, w, bias, pre, y, M, N, K, EPI_GELU_SAVE, tile_run, stream, "gemm_bf16_gelu_fwd");
 }
 
 extern "C" int basd_gemm_bf16_gelu_bwd(const void* dy, const void* wt, const void* pre, void* dpre, int64_t M, int N,
@@ -1050,5 +1062,6 @@ extern "C" int basd_gemm_bf16_gelu_bwd(const void* dy, const void* wt, const voi
   using namespace basd;
   if (M > 0 && (pre == nullptr || dpre == nullptr))
     return fail(BASD_ERR_SHAPE, "gemm_bf16_gelu_bwd: pre and dpre are required");
-  return gemm_dispatch(dy, wt, nullptr, const_cast<void*>(pre), dpre, M, N, K, 4, tile_run, stream, "gemm_bf16_gelu_bwd");
+  return gemm_dispatch(dy, wt, nullptr, const_cast<void*>(pre), dpre, M, N, K, EPI_GELU_BWD, tile_run, stream,
+                       "gemm_bf16_gelu_bwd");
 }
