@@ -65,6 +65,9 @@
  *   basd_attention_fwd_relbias_bf16
  *                          timm Beit Attention.forward of a frozen BEiT / BEiT-v2 teacher (learned relative-position
  *                          bias on the logits, teacher.py:118 creates it) with the CLS-row tap
+ *   basd_attention_fwd_rope_bf16
+ *                          timm Eva EvaAttention.forward of a frozen EVA-02 teacher (rotary position embedding on q and
+ *                          k, teacher.py:118 creates it) with the CLS-row tap
  *   basd_layernorm_fwd_bf16 / _bwd_bf16, basd_add_layernorm_fwd_bf16
  *                          timm nn.LayerNorm of the ViT blocks (student: with backward; frozen teacher: fused with
  *                          the residual add in front of it)
@@ -525,6 +528,23 @@ int basd_attention_fwd_qmean_bf16(const void* qkv, int B, int T, int H, int hd, 
  * BASD_ERR_SHAPE without a launch.  No allocation, no synchronisation. */
 int basd_attention_fwd_relbias_bf16(const void* qkv, const float* table, int B, int gh, int gw, int H, int hd,
                                     float scale, void* out, float* importance, void* stream);
+
+/* The same forward for a frozen block whose attention rotates q and k with a rotary position embedding (timm Eva
+ * EvaAttention.forward with RotaryEmbeddingCat: EVA-02): qkv [B, T, 3, H, hd] bf16 -> out [B, T, H * hd] bf16 =
+ * softmax(Q' K'^T * scale) V per head, where for every head, token t and channel pair i
+ *   x'[2i]     = x[2i] c - x[2i + 1] s
+ *   x'[2i + 1] = x[2i + 1] c + x[2i] s,      (c, s) = rope[t][i],      x = q and x = k;  v is untouched.
+ * rope: fp32 [T, hd / 2, 2], 16-byte aligned -- (cos, sin) of pair i of token t.  Row t applies to token t whatever it
+ * is: the kernel knows no grid, frequency bands or prefix tokens, and a token that is not rotated (the CLS token) has
+ * the row (1, 0).  The rotation happens in registers, between the global loads of the K chunks / Q fragments and their
+ * use: fp32 arithmetic on the bf16 inputs, ONE rounding back to bf16, so the matrix cores see bf16 operands as in
+ * basd_attention_fwd_bf16; no rotated copy of q or k and nothing [T, T] is read or written.  importance (nullable):
+ * [B, H, T-1] fp32; receives per head the CLS row of that softmax (fp32 logits) without the CLS column, divided by H
+ * (the tap is the sum over the H axis) -- layout and meaning of basd_attention_fwd_relbias_bf16's.  Arithmetic otherwise
+ * as basd_attention_fwd_bf16.  hd == 64, 2 <= T <= 272, B >= 1, H >= 1, rope != NULL; anything else is BASD_ERR_SHAPE
+ * without a launch.  No allocation, no synchronisation. */
+int basd_attention_fwd_rope_bf16(const void* qkv, const float* rope, int B, int T, int H, int hd, float scale, void* out,
+                                 float* importance, void* stream);
 
 /* Fused attention backward of a trained block (the student; reference src/training/trainer.py:157 through timm
  * Attention.forward): qkv [B, T, 3, H, hd] bf16, out / dout [B, T, H * hd] bf16 (forward output and its gradient),

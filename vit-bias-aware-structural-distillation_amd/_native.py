@@ -41,6 +41,7 @@ EXPORTS = (
     "basd_sym_tridiag_f64_workspace_bytes", "basd_sym_tridiag_f64", "basd_tridiag_mp_rank",
     "basd_window_attention_fwd_bf16", "basd_patch_merge_ln_bf16", "basd_gemm_bf16_act", "basd_vit_embed_bf16",
     "basd_attention_fwd_relbias_bf16", "basd_gemm_bf16_swiglu", "basd_vit_embed_reg_bf16",
+    "basd_attention_fwd_rope_bf16",
 )
 
 
@@ -97,6 +98,7 @@ _SIGNATURES = {
     "basd_attention_fwd_bf16": (_P, _I, _I, _I, _I, _F, _P, _P, _P, _P),
     "basd_attention_fwd_qmean_bf16": (_P, _I, _I, _I, _I, _F, _P, _P, _P),
     "basd_attention_fwd_relbias_bf16": (_P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P),
+    "basd_attention_fwd_rope_bf16": (_P, _P, _I, _I, _I, _I, _F, _P, _P, _P),
     "basd_attention_bwd_bf16": (_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P),
     "basd_attention_fwd_long_bf16": (_P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P),
     "basd_attention_bwd_long_workspace_bytes": (_I, _I, _I, _I),
@@ -1188,6 +1190,54 @@ def attention_fwd_relbias(qkv: torch.Tensor, table: torch.Tensor, gh: int, gw: i
     _check(lib().basd_attention_fwd_relbias_bf16(_ptr(qkv), _ptr(table), b, gh, gw, heads, head_dim,
                                                  ctypes.c_float(scale), _ptr(out), _ptr(imp), _stream()),
            "basd_attention_fwd_relbias_bf16")
+    return out, (imp.sum(dim=1) if want_importance else None)
+
+
+def rope_table(gh: int, gw: int, head_dim: int, *, ref_grid=None, temperature: float = 10000.0,
+               prefix_tokens: int = 1) -> torch.Tensor:
+    """fp32 [prefix_tokens + gh * gw, head_dim / 2, 2] on the CPU: (cos, sin) of the angle that rotates channel pair
+    (2i, 2i + 1) of every token -- the table ``attention_fwd_rope`` reads; angles in fp64.  The rule is timm's
+    ``RotaryEmbeddingCat`` with ``in_pixels=False`` (EVA-02), written from memory of timm 1.0.x ``pos_embed_sincos.py``
+    without timm at hand: bands b_j = temperature^(-j / (hd / 4)), j = 0 .. hd / 4 - 1; coordinates y = arange(gh) *
+    (ref_gh / gh), x likewise (plain arange when ``ref_grid`` is None or the grid itself); the hd / 2 angles of patch
+    (y, x) are [y b_0 .. y b_last, x b_0 .. x b_last].  The prefix rows (CLS) are (1, 0): not rotated.  Check against
+    the ``rope`` buffers of the installed timm before loading real weights."""
+    if head_dim % 4 != 0 or gh < 1 or gw < 1 or prefix_tokens < 0:
+        raise ValueError(f"rope_table: grid {gh} x {gw}, head_dim {head_dim} (a multiple of 4), prefix {prefix_tokens}")
+    nb = head_dim // 4
+    bands = float(temperature) ** (-torch.arange(nb, dtype=torch.float64) / nb)
+    ref_gh, ref_gw = (gh, gw) if ref_grid is None else (int(ref_grid[0]), int(ref_grid[1]))
+    y = torch.arange(gh, dtype=torch.float64) * (ref_gh / gh)
+    x = torch.arange(gw, dtype=torch.float64) * (ref_gw / gw)
+    ang = torch.cat([(y[:, None, None] * bands).expand(gh, gw, nb), (x[None, :, None] * bands).expand(gh, gw, nb)], dim=-1)
+    table = torch.zeros(prefix_tokens + gh * gw, 2 * nb, 2, dtype=torch.float64)
+    table[:prefix_tokens, :, 0] = 1.0
+    table[prefix_tokens:, :, 0] = ang.reshape(gh * gw, 2 * nb).cos()
+    table[prefix_tokens:, :, 1] = ang.reshape(gh * gw, 2 * nb).sin()
+    return table.float()
+
+
+def attention_fwd_rope_supported(t: int, hd: int) -> bool:
+    """the range of ``basd_attention_fwd_rope_bf16``: the short kernel's token count from 2 up, head dim 64"""
+    return hd == 64 and 2 <= t <= 272
+
+
+def attention_fwd_rope(qkv: torch.Tensor, rope: torch.Tensor, heads: int, head_dim: int, scale: float,
+                       want_importance: bool = False):
+    """qkv [B, T, 3 * heads * head_dim] bf16, rope [T, head_dim / 2, 2] fp32 ((cos, sin) per token and channel pair:
+    ``rope_table``) -> (out [B, T, heads * head_dim] bf16, importance | None) with softmax(q' k'^T * scale) v per head,
+    q' / k' the pairwise rotations of q / k (fp32 arithmetic, one rounding to bf16) done inside the kernel; importance:
+    the CLS row of the head-averaged map of that softmax without its first entry, [B, T-1] fp32."""
+    _need_cuda(qkv, rope)
+    b, t = qkv.shape[0], qkv.shape[1]
+    assert qkv.dtype == torch.bfloat16 and qkv.shape[-1] == 3 * heads * head_dim
+    assert rope.dtype == torch.float32 and tuple(rope.shape) == (t, head_dim // 2, 2), (tuple(rope.shape), t, head_dim)
+    qkv, rope = qkv.contiguous(), rope.contiguous()
+    assert rope.data_ptr() % 16 == 0
+    out = torch.empty(b, t, heads * head_dim, dtype=torch.bfloat16, device=qkv.device)
+    imp = torch.empty(b, heads, t - 1, dtype=torch.float32, device=qkv.device) if want_importance else None
+    _check(lib().basd_attention_fwd_rope_bf16(_ptr(qkv), _ptr(rope), b, t, heads, head_dim, ctypes.c_float(scale),
+                                              _ptr(out), _ptr(imp), _stream()), "basd_attention_fwd_rope_bf16")
     return out, (imp.sum(dim=1) if want_importance else None)
 
 

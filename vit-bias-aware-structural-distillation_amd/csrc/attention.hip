@@ -43,17 +43,38 @@ template <int CTRL> __device__ __forceinline__ float at_dpp_add(float v) {
 // a lane forms idx = (y_q + gh - 1)(2 gw - 1) + x_q + gw - 1 - koff[key] per logit (one division per lane and query
 // tile); a CLS query reads row R - 3 (R - 1 against the CLS key), a patch query row R - 2 against the CLS key.  The tap is
 // row 0 of the main softmax (fp32 logits, bias included), not the bf16-rounded side computation of the plain kernel.
+//
+// ROPE: EVA-02's rotary position embedding (basd_attention_fwd_rope_bf16): q and k of token t are rotated pairwise,
+// (x[2i], x[2i+1]) -> (x[2i] c - x[2i+1] s, x[2i+1] c + x[2i] s) with (c, s) = rope[t][i], before the logits are formed;
+// v is untouched.  A 16-byte chunk holds four whole pairs, so a K chunk is rotated in registers between its global load
+// and its LDS store, and a Q fragment between its (prefetched) global load and the MFMA: fp32 arithmetic on the bf16
+// inputs, one rounding back to bf16.  The eight table floats of a chunk are loaded next to it (two 16-byte loads issued
+// with the K / V / Q loads).  The kernel knows no grid: row t of the table belongs to token t (the host writes (1, 0)
+// into the rows of tokens that are not rotated).  The table pointer travels in RelBias::table (gh = gw = 0): the
+// kernel's argument list stays the one of the other instantiations.  The tap is row 0 of the main softmax as for RELBIAS.
 struct RelBias {
-  const float* table;                                // [R, H] fp32, heads on the fast axis
+  const float* table;                                // [R, H] fp32, heads on the fast axis (ROPE: [T, hd / 2, 2] fp32)
   int gh, gw;                                        // patch grid: T = gh * gw + 1, CLS token first
 };
 
-template <int NKT, int AT_HD, bool QMEAN = false, bool RELBIAS = false>   // key tiles of 16: T <= 16 * NKT; head dim 64 or 80
+// one word = the channel pair (2i, 2i + 1) in bf16 -> the rotated pair, rounded once
+__device__ __forceinline__ unsigned int rope_pair(unsigned int w, float c, float s) {
+  const float a = __uint_as_float(w << 16), b = __uint_as_float(w & 0xffff0000u);
+  return pack_bf16(fmaf(-b, s, a * c), fmaf(a, s, b * c));
+}
+// eight channels = four pairs; cs0 = (c, s) of the first two pairs, cs1 of the last two
+__device__ __forceinline__ uint4 rope_chunk(const uint4& v, const float4& cs0, const float4& cs1) {
+  return make_uint4(rope_pair(v.x, cs0.x, cs0.y), rope_pair(v.y, cs0.z, cs0.w), rope_pair(v.z, cs1.x, cs1.y),
+                    rope_pair(v.w, cs1.z, cs1.w));
+}
+
+template <int NKT, int AT_HD, bool QMEAN = false, bool RELBIAS = false, bool ROPE = false>   // key tiles of 16: T <= 16 * NKT; head dim 64 or 80
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void attention_fwd_kernel(const unsigned short* __restrict__ qkv, int T, int H,
                                                             float scale, unsigned short* __restrict__ out,
                                                             float* __restrict__ importance, float* __restrict__ lse,
                                                             RelBias rb) {
   static_assert(!(QMEAN && RELBIAS), "the relative-position bias comes with the CLS tap only");
+  static_assert(!ROPE || (!QMEAN && !RELBIAS && AT_HD == 64), "the rotary embedding: CLS tap, no bias, whole 32-deep steps");
   constexpr int NKS = (NKT + 1) / 2;                 // 32-key steps of the P V product
   constexpr int KROWS = 32 * NKS;                    // LDS rows (zero padded)
   constexpr int NDS = (AT_HD + 31) / 32;             // 32-deep steps of the Q K^T contraction
@@ -78,16 +99,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   //      them: 14 us of a 24 us workgroup in the first version of this kernel).
   constexpr int NLD = (KROWS * NCHP + 255) / 256;
   uint4 kreg[NLD], vreg[NLD];
+  float4 kcs[ROPE ? NLD : 1][2];                     // ROPE: (cos, sin) of the four pairs of every K chunk
 #pragma unroll
   for (int i = 0; i < NLD; ++i) {
     const int idx = tid + 256 * i;
     const int r = idx / NCHP, c8 = idx - r * NCHP;
     kreg[i] = make_uint4(0, 0, 0, 0);
     vreg[i] = make_uint4(0, 0, 0, 0);
+    if constexpr (ROPE) kcs[i][0] = kcs[i][1] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (r < T && c8 < NCH) {
       const unsigned short* p = base + (size_t)r * row + c8 * 8;
       kreg[i] = *reinterpret_cast<const uint4*>(p + (size_t)H * AT_HD);
       vreg[i] = *reinterpret_cast<const uint4*>(p + (size_t)2 * H * AT_HD);
+      if constexpr (ROPE) {
+        const float4* cs = reinterpret_cast<const float4*>(rb.table + (size_t)r * AT_HD + c8 * 8);
+        kcs[i][0] = cs[0];
+        kcs[i][1] = cs[1];
+      }
     }
   }
   const int R = RELBIAS ? (2 * rb.gh - 1) * (2 * rb.gw - 1) + 3 : 0;
@@ -109,6 +137,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   for (int i = 0; i < NLD; ++i) {
     const int idx = tid + 256 * i;
     const int r = idx / NCHP, c8 = idx - r * NCHP;
+    if constexpr (ROPE) kreg[i] = rope_chunk(kreg[i], kcs[i][0], kcs[i][1]);    // padding rows: zeros stay zeros
     if (idx < KROWS * NCHP) {
       *reinterpret_cast<uint4*>(Ks + r * AT_LD + c8 * 8) = kreg[i];
       *reinterpret_cast<uint4*>(Vs + r * AT_LD + c8 * 8) = vreg[i];
@@ -121,16 +150,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int nqt = (T + 15) >> 4;
   const int full_tiles = T >> 4;                     // key tiles without padding
   unsigned short* Ow = Os + wave * 16 * AT_LD;
-  auto load_q = [&](int qt_, uint4 (&dst)[NDS]) {
+  // ROPE: the fragment's table rows are fetched with it; the rotation itself waits until the fragment is taken out of
+  // the prefetch registers (below), so the loads stay in flight over a whole query tile as they do without it
+  auto load_q = [&](int qt_, uint4 (&dst)[NDS], float4 (&cs)[ROPE ? NDS : 1][2]) {
 #pragma unroll
     for (int ks = 0; ks < NDS; ++ks) {
       dst[ks] = make_uint4(0, 0, 0, 0);
-      if (qt_ < nqt && qt_ * 16 + li < T && 32 * ks + 8 * g < AT_HD)
+      if constexpr (ROPE) cs[ks][0] = cs[ks][1] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (qt_ < nqt && qt_ * 16 + li < T && 32 * ks + 8 * g < AT_HD) {
         dst[ks] = *reinterpret_cast<const uint4*>(base + (size_t)(qt_ * 16 + li) * row + 32 * ks + 8 * g);
+        if constexpr (ROPE) {
+          const float4* p = reinterpret_cast<const float4*>(rb.table + (size_t)(qt_ * 16 + li) * AT_HD + 32 * ks + 8 * g);
+          cs[ks][0] = p[0];
+          cs[ks][1] = p[1];
+        }
+      }
     }
   };
   uint4 qnext[NDS];
-  load_q(wave, qnext);
+  float4 qcs[ROPE ? NDS : 1][2];
+  load_q(wave, qnext, qcs);
   float csum[QMEAN ? NKT : 1][4];                    // QMEAN: this lane's query column summed over the wave's tiles
 #pragma unroll
   for (int kt = 0; kt < (QMEAN ? NKT : 1); ++kt)
@@ -141,8 +180,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // Q fragments of this tile: query q0 + li, d = 32 ks + 8 g .. + 7 (fetched one tile ahead)
     bf16x8 qf[NDS];
 #pragma unroll
-    for (int ks = 0; ks < NDS; ++ks) qf[ks] = *reinterpret_cast<bf16x8*>(&qnext[ks]);
-    load_q(qt + 4, qnext);
+    for (int ks = 0; ks < NDS; ++ks) {
+      if constexpr (ROPE) qnext[ks] = rope_chunk(qnext[ks], qcs[ks][0], qcs[ks][1]);
+      qf[ks] = *reinterpret_cast<bf16x8*>(&qnext[ks]);
+    }
+    load_q(qt + 4, qnext, qcs);
     // ---- S^T tiles
     f32x4 s[NKT];
 #pragma unroll
@@ -176,7 +218,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       }
     }
     // ---- the attention tap: CLS query (column 0 of tile 0) with bf16-rounded logits, head-averaged
-    if (!QMEAN && !RELBIAS && importance != nullptr && qt == 0) {
+    if (!QMEAN && !RELBIAS && !ROPE && importance != nullptr && qt == 0) {
       float lr[NKT][4];                              // transient: dead before the P V product needs registers
       float tmx = -3.0e38f;
 #pragma unroll
@@ -239,7 +281,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     sum += __shfl_xor(sum, 16, 64);
     sum += __shfl_xor(sum, 32, 64);
     const float inv = 1.f / sum;
-    if constexpr (RELBIAS) {
+    if constexpr (RELBIAS || ROPE) {
       // the tap: the CLS row (query 0 = column li 0 of tile 0) of this softmax without the CLS column, divided by H
       if (importance != nullptr && qt == 0 && li == 0) {
         const float tinv = inv / (float)H;
@@ -333,7 +375,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
 }
 
-template <int NKT, int HD, bool QMEAN = false, bool RELBIAS = false>
+template <int NKT, int HD, bool QMEAN = false, bool RELBIAS = false, bool ROPE = false>
 static void launch_attention(const void* qkv, int B, int T, int H, float scale, void* out, float* importance,
                              float* lse, hipStream_t st, RelBias rb = RelBias{nullptr, 0, 0}) {
   constexpr int KROWS = 32 * ((NKT + 1) / 2);
@@ -342,8 +384,8 @@ static void launch_attention(const void* qkv, int B, int T, int H, float scale, 
   static_assert(8 * LD >= KROWS, "the output staging tile of a wave holds its query-mean column sums");
   static_assert((2 * KROWS * LD + 4 * 16 * LD) % 8 == 0, "the key offsets behind the tiles are read 16 bytes at a time");
   if (RELBIAS) lds += ((size_t)KROWS + (size_t)(2 * rb.gh - 1) * (2 * rb.gw - 1) + 3) * sizeof(float);
-  allow_full_lds((const void*)attention_fwd_kernel<NKT, HD, QMEAN, RELBIAS>);
-  hipLaunchKernelGGL((attention_fwd_kernel<NKT, HD, QMEAN, RELBIAS>), dim3(B * H), dim3(256), lds, st,
+  allow_full_lds((const void*)attention_fwd_kernel<NKT, HD, QMEAN, RELBIAS, ROPE>);
+  hipLaunchKernelGGL((attention_fwd_kernel<NKT, HD, QMEAN, RELBIAS, ROPE>), dim3(B * H), dim3(256), lds, st,
                      (const unsigned short*)qkv, T, H, scale, (unsigned short*)out, importance, lse, rb);
 }
 
@@ -401,4 +443,18 @@ extern "C" int basd_attention_fwd_relbias_bf16(const void* qkv, const float* tab
   else if (T <= 208) launch_attention<13, 64, false, true>(qkv, B, T, H, scale, out, importance, nullptr, st, rb);
   else launch_attention<17, 64, false, true>(qkv, B, T, H, scale, out, importance, nullptr, st, rb);
   return check_launch("attention_fwd_relbias");
+}
+
+extern "C" int basd_attention_fwd_rope_bf16(const void* qkv, const float* rope, int B, int T, int H, int hd, float scale,
+                                            void* out, float* importance, void* stream) {
+  using namespace basd;
+  if (hd != 64 || T < 2 || T > 272 || H < 1 || B < 1 || rope == nullptr)
+    return fail(BASD_ERR_SHAPE, "attention_fwd_rope: B=%d T=%d H=%d hd=%d rope=%s unsupported (hd 64, 2 <= T <= 272, B, H >= 1, "
+                                "a table)", B, T, H, hd, rope == nullptr ? "NULL" : "given");
+  const RelBias rb{rope, 0, 0};                      // the table pointer in the bias slot of the kernel's arguments
+  hipStream_t st = (hipStream_t)stream;
+  if (T <= 64) launch_attention<4, 64, false, false, true>(qkv, B, T, H, scale, out, importance, nullptr, st, rb);
+  else if (T <= 208) launch_attention<13, 64, false, false, true>(qkv, B, T, H, scale, out, importance, nullptr, st, rb);
+  else launch_attention<17, 64, false, false, true>(qkv, B, T, H, scale, out, importance, nullptr, st, rb);
+  return check_launch("attention_fwd_rope");
 }

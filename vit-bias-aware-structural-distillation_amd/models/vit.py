@@ -394,7 +394,7 @@ class SwiGLU(nn.Module):
 
 class Block(nn.Module):
     def __init__(self, dim, num_heads, mlp_ratio=4.0, drop_path=0.0, init_values=None, eps=1e-6, act="gelu",
-                 attn_cls=None, mlp="mlp", mlp_hidden=None):
+                 attn_cls=None, mlp="mlp", mlp_hidden=None, mlp_cls=None):
         super().__init__()
         self.norm1 = MixedLayerNorm(dim, eps=eps)
         # attn_cls(dim, num_heads): the attention of another model family (models/beit.py); default: Attention
@@ -405,7 +405,8 @@ class Block(nn.Module):
         if mlp not in MLP_KINDS:
             raise ValueError(f"Block: unknown MLP {mlp!r}; known: {MLP_KINDS}")
         hidden = int(mlp_hidden) if mlp_hidden else int(dim * mlp_ratio)
-        self.mlp = SwiGLU(dim, hidden) if mlp == "swiglu" else Mlp(dim, hidden, act)
+        # mlp_cls(dim, hidden): the MLP of another model family (models/eva.py); default: SwiGLU / Mlp by name
+        self.mlp = mlp_cls(dim, hidden) if mlp_cls else SwiGLU(dim, hidden) if mlp == "swiglu" else Mlp(dim, hidden, act)
         self.ls2 = LayerScale(dim, init_values) if init_values else nn.Identity()
         self.drop_path2 = DropPath(drop_path)
 
