@@ -68,6 +68,9 @@
  *   basd_attention_fwd_rope_bf16
  *                          timm Eva EvaAttention.forward of a frozen EVA-02 teacher (rotary position embedding on q and
  *                          k, teacher.py:118 creates it) with the CLS-row tap
+ *   basd_attention_fwd_long_rope_bf16
+ *                          the same rotary forward for 273 .. 1024 tokens (DINOv3 and EVA-02 teachers at 384 px) on
+ *                          the tiled kernels; DINOv3's half-split pairs are interleaved in the weights at load time
  *   basd_layernorm_fwd_bf16 / _bwd_bf16, basd_add_layernorm_fwd_bf16
  *                          timm nn.LayerNorm of the ViT blocks (student: with backward; frozen teacher: fused with
  *                          the residual add in front of it)
@@ -545,6 +548,18 @@ int basd_attention_fwd_relbias_bf16(const void* qkv, const float* table, int B, 
  * without a launch.  No allocation, no synchronisation. */
 int basd_attention_fwd_rope_bf16(const void* qkv, const float* rope, int B, int T, int H, int hd, float scale, void* out,
                                  float* importance, void* stream);
+
+/* The rotary forward on the tiled kernels of basd_attention_fwd_long_bf16, for the token counts the entry above refuses
+ * (a rotary teacher at 384 px: DINOv3 /16 has 581 tokens, EVA-02 /14 has 730): same qkv, rope, rotation rule (fp32
+ * arithmetic, ONE rounding to bf16, before the logits; v untouched) and out.  cls_importance (nullable): [B, H, T-1]
+ * fp32, the CLS tap of basd_attention_fwd_long_bf16 computed on the rotated operands: q_0 and every k row are rotated
+ * and rounded to bf16, then fp32 dot, logit rounded to bf16, scale, expf, softmax without the CLS column, divided by H.
+ * (The short entry taps its main softmax with fp32 logits instead; both are within bf16 rounding of the exact row.)
+ * No LSE and no query-mean output: only frozen teachers with a CLS token use this entry.  hd == 64, 2 <= T <= 1024,
+ * B >= 1, H >= 1, rope != NULL; anything else is BASD_ERR_SHAPE without a launch.  No allocation, no
+ * synchronisation. */
+int basd_attention_fwd_long_rope_bf16(const void* qkv, const float* rope, int B, int T, int H, int hd, float scale,
+                                      void* out, float* cls_importance, void* stream);
 
 /* Fused attention backward of a trained block (the student; reference src/training/trainer.py:157 through timm
  * Attention.forward): qkv [B, T, 3, H, hd] bf16, out / dout [B, T, H * hd] bf16 (forward output and its gradient),

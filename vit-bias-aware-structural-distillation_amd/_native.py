@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import math
 import os
 import subprocess
 
@@ -41,7 +42,7 @@ EXPORTS = (
     "basd_sym_tridiag_f64_workspace_bytes", "basd_sym_tridiag_f64", "basd_tridiag_mp_rank",
     "basd_window_attention_fwd_bf16", "basd_patch_merge_ln_bf16", "basd_gemm_bf16_act", "basd_vit_embed_bf16",
     "basd_attention_fwd_relbias_bf16", "basd_gemm_bf16_swiglu", "basd_vit_embed_reg_bf16",
-    "basd_attention_fwd_rope_bf16",
+    "basd_attention_fwd_rope_bf16", "basd_attention_fwd_long_rope_bf16",
 )
 
 
@@ -99,6 +100,7 @@ _SIGNATURES = {
     "basd_attention_fwd_qmean_bf16": (_P, _I, _I, _I, _I, _F, _P, _P, _P),
     "basd_attention_fwd_relbias_bf16": (_P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P),
     "basd_attention_fwd_rope_bf16": (_P, _P, _I, _I, _I, _I, _F, _P, _P, _P),
+    "basd_attention_fwd_long_rope_bf16": (_P, _P, _I, _I, _I, _I, _F, _P, _P, _P),
     "basd_attention_bwd_bf16": (_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P),
     "basd_attention_fwd_long_bf16": (_P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P),
     "basd_attention_bwd_long_workspace_bytes": (_I, _I, _I, _I),
@@ -1239,6 +1241,58 @@ def attention_fwd_rope(qkv: torch.Tensor, rope: torch.Tensor, heads: int, head_d
     _check(lib().basd_attention_fwd_rope_bf16(_ptr(qkv), _ptr(rope), b, t, heads, head_dim, ctypes.c_float(scale),
                                               _ptr(out), _ptr(imp), _stream()), "basd_attention_fwd_rope_bf16")
     return out, (imp.sum(dim=1) if want_importance else None)
+
+
+def attention_fwd_long_rope_supported(t: int, hd: int) -> bool:
+    """the range of ``basd_attention_fwd_long_rope_bf16``: the tiled kernel's token count from 2 up, head dim 64"""
+    return hd == 64 and 2 <= t <= LONG_ATTENTION_MAX_T
+
+
+def attention_fwd_long_rope(qkv: torch.Tensor, rope: torch.Tensor, heads: int, head_dim: int, scale: float,
+                            want_importance: bool = False):
+    """``attention_fwd_rope`` on the tiled kernels (csrc/attention_long.hip, ROPE), for the token counts the short entry
+    refuses; arguments and results are the same.  The importance is the CLS tap of ``attention_fwd``'s long kernel
+    (bf16-rounded logits) on the rotated operands."""
+    _need_cuda(qkv, rope)
+    b, t = qkv.shape[0], qkv.shape[1]
+    assert qkv.dtype == torch.bfloat16 and qkv.shape[-1] == 3 * heads * head_dim
+    assert rope.dtype == torch.float32 and tuple(rope.shape) == (t, head_dim // 2, 2), (tuple(rope.shape), t, head_dim)
+    qkv, rope = qkv.contiguous(), rope.contiguous()
+    assert rope.data_ptr() % 16 == 0
+    out = torch.empty(b, t, heads * head_dim, dtype=torch.bfloat16, device=qkv.device)
+    imp = torch.empty(b, heads, t - 1, dtype=torch.float32, device=qkv.device) if want_importance else None
+    _check(lib().basd_attention_fwd_long_rope_bf16(_ptr(qkv), _ptr(rope), b, t, heads, head_dim, ctypes.c_float(scale),
+                                                   _ptr(out), _ptr(imp), _stream()),
+           "basd_attention_fwd_long_rope_bf16")
+    return out, (imp.sum(dim=1) if want_importance else None)
+
+
+def dinov3_rope_table(gh: int, gw: int, head_dim: int, base: float = 100.0, prefix_tokens: int = 5) -> torch.Tensor:
+    """fp32 [prefix_tokens + gh * gw, head_dim / 2, 2] on the CPU: (cos, sin) of DINOv3's rotary angles, one per channel
+    pair, in the layout ``attention_fwd_rope`` / ``attention_fwd_long_rope`` read; angles in fp64.  The rule is
+    ``RopePositionEmbedding`` of facebookresearch/dinov3 (``base`` given, coordinates normalised "separate", no
+    augmentation), written from memory without the hub code or timm at hand: periods p_j = base^(2 j / (hd / 2)),
+    j = 0 .. hd / 4 - 1; coordinates y = (arange(gh) + 0.5) / gh * 2 - 1 in [-1, 1], x likewise; the hd / 2 angles of
+    patch (y, x) are [2 pi y / p_0 .. 2 pi y / p_last, 2 pi x / p_0 .. 2 pi x / p_last].  DINOv3 tiles these hd / 2
+    angles twice over the hd channels and rotates the half-split pairs (i, i + hd / 2): angle i belongs to that pair,
+    which ``models/dinov3.py`` moves to the channels (2 i, 2 i + 1) in the weights.  The prefix rows (CLS and the
+    registers) are (1, 0): not rotated.  Check against the checkpoint's ``rope_embed.periods`` before loading real
+    weights."""
+    if head_dim % 4 != 0 or gh < 1 or gw < 1 or prefix_tokens < 0:
+        raise ValueError(f"dinov3_rope_table: grid {gh} x {gw}, head_dim {head_dim} (a multiple of 4), prefix "
+                         f"{prefix_tokens}")
+    nb = head_dim // 4
+    periods = float(base) ** (2.0 * torch.arange(nb, dtype=torch.float64) / (head_dim // 2))
+    y = (torch.arange(gh, dtype=torch.float64) + 0.5) / gh * 2.0 - 1.0
+    x = (torch.arange(gw, dtype=torch.float64) + 0.5) / gw * 2.0 - 1.0
+    two_pi = 2.0 * math.pi
+    ang = torch.cat([(two_pi * y[:, None, None] / periods).expand(gh, gw, nb),
+                     (two_pi * x[None, :, None] / periods).expand(gh, gw, nb)], dim=-1).reshape(gh * gw, 2 * nb)
+    table = torch.zeros(prefix_tokens + gh * gw, 2 * nb, 2, dtype=torch.float64)
+    table[:prefix_tokens, :, 0] = 1.0
+    table[prefix_tokens:, :, 0] = ang.cos()
+    table[prefix_tokens:, :, 1] = ang.sin()
+    return table.float()
 
 
 def _short_attention_bwd_ok(t: int, hd: int) -> bool:

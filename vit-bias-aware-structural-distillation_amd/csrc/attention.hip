@@ -57,16 +57,7 @@ struct RelBias {
   int gh, gw;                                        // patch grid: T = gh * gw + 1, CLS token first
 };
 
-// one word = the channel pair (2i, 2i + 1) in bf16 -> the rotated pair, rounded once
-__device__ __forceinline__ unsigned int rope_pair(unsigned int w, float c, float s) {
-  const float a = __uint_as_float(w << 16), b = __uint_as_float(w & 0xffff0000u);
-  return pack_bf16(fmaf(-b, s, a * c), fmaf(a, s, b * c));
-}
-// eight channels = four pairs; cs0 = (c, s) of the first two pairs, cs1 of the last two
-__device__ __forceinline__ uint4 rope_chunk(const uint4& v, const float4& cs0, const float4& cs1) {
-  return make_uint4(rope_pair(v.x, cs0.x, cs0.y), rope_pair(v.y, cs0.z, cs0.w), rope_pair(v.z, cs1.x, cs1.y),
-                    rope_pair(v.w, cs1.z, cs1.w));
-}
+// rope_pair / rope_chunk (basd_frag.h) rotate one word / one 16-byte chunk
 
 template <int NKT, int AT_HD, bool QMEAN = false, bool RELBIAS = false, bool ROPE = false>   // key tiles of 16: T <= 16 * NKT; head dim 64 or 80
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void attention_fwd_kernel(const unsigned short* __restrict__ qkv, int T, int H,

@@ -19,6 +19,12 @@
 //   query mean   attn_long_qmean_kernel: one wave per 16-key tile walks every query tile, recomputes P from the LSE of
 //                the main pass and sums it down the column in a fixed order -- no partials, no atomics, bitwise
 //                reproducible.
+// ROPE (basd_attention_fwd_long_rope_bf16; frozen teachers with a rotary embedding past the 272 tokens of attention.hip):
+//   q and k of token t are rotated pairwise by the (cos, sin) rows of an fp32 table [T, hd / 2, 2] (rope_chunk,
+//   basd_frag.h: fp32 arithmetic, one rounding to bf16) before the logits are formed; v is untouched.  A K chunk is
+//   rotated in registers between its global load and its LDS store -- its eight table floats travel with it through the
+//   prefetch registers -- and the Q fragments once in front of the key loop.  The CLS tap rotates q_0 and every k row
+//   the same way before its dot: it is the tap above on the rotated, bf16-rounded operands.  No LSE, no query mean.
 //
 // Backward (FA2): attn_long_delta_kernel computes delta = rowsum(dO * O); attn_long_bwd_kernel runs one workgroup per
 // (image, head, 128-key block), wave w owning 32 keys whose K / V fragments and dK^T / dV^T accumulators stay in
@@ -26,6 +32,8 @@
 // dQ: the four waves' 32 x hd contributions meet in LDS and are added in wave order; the block's sum goes to a
 // per-key-block fp32 partial in the workspace (vector stores), and attn_long_dq_kernel adds the partials in key-block
 // order and writes the bf16 dQ slice of dqkv.  No atomics: the gradient is bitwise reproducible.
+#include <type_traits>
+
 #include "basd_frag.h"
 
 namespace basd {
@@ -33,11 +41,19 @@ namespace basd {
 constexpr int AL_MAXT = 1024;
 constexpr float AL_LOG2E = 1.4426950408889634f;
 
+// The ROPE instantiations take the table where the plain ones take the LSE pointer (forward) or next to the importance
+// pointer (tap): the argument lists, and with them the device code, of the plain instantiations stay what they were.
+struct AlRopeTap {
+  float* importance;
+  const float* rope;                                 // [T, HD / 2, 2] fp32 (cos, sin)
+};
+
 // ------------------------------------------------------------------------------------------------------ forward ----
-template <int HD>
-__global__ __launch_bounds__(256) void attn_long_fwd_kernel(const unsigned short* __restrict__ qkv, int T, int H,
-                                                            float scale, unsigned short* __restrict__ out,
-                                                            float* __restrict__ lse) {
+template <int HD, bool ROPE = false>
+__global__ __launch_bounds__(256) void attn_long_fwd_kernel(
+    const unsigned short* __restrict__ qkv, int T, int H, float scale, unsigned short* __restrict__ out,
+    typename std::conditional<ROPE, const float*, float*>::type __restrict__ lse_or_rope) {
+  static_assert(!ROPE || HD == 64, "the rotary embedding: head dim 64 (whole 32-deep steps)");
   constexpr int KB = 64;                             // keys per LDS tile
   constexpr int NDS = (HD + 31) / 32;                // 32-deep steps of the Q K^T contraction
   constexpr int NDT = HD / 16;                       // 16-column tiles of the output
@@ -55,7 +71,13 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(const unsigned short
   const size_t row = (size_t)3 * H * HD;
   const unsigned short* base = qkv + (size_t)b * T * row + (size_t)h * HD;
 
+  float* lse = nullptr;
+  const float* rope = nullptr;
+  if constexpr (ROPE) rope = lse_or_rope;
+  else lse = lse_or_rope;
+
   uint4 kreg[NLD], vreg[NLD];
+  float4 kcs[ROPE ? NLD : 1][2];                     // ROPE: (cos, sin) of the four pairs of every K chunk
   auto load_kv = [&](int k0) {
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
@@ -63,10 +85,16 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(const unsigned short
       const int r = idx / NCHP, c8 = idx - r * NCHP;
       kreg[i] = make_uint4(0, 0, 0, 0);
       vreg[i] = make_uint4(0, 0, 0, 0);
+      if constexpr (ROPE) kcs[i][0] = kcs[i][1] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (idx < KB * NCHP && k0 + r < T && c8 < NCH) {
         const unsigned short* p = base + (size_t)(k0 + r) * row + c8 * 8;
         kreg[i] = *reinterpret_cast<const uint4*>(p + (size_t)H * HD);
         vreg[i] = *reinterpret_cast<const uint4*>(p + (size_t)2 * H * HD);
+        if constexpr (ROPE) {                        // the table row of the GLOBAL key index, inside the same guard
+          const float4* cs = reinterpret_cast<const float4*>(rope + (size_t)(k0 + r) * HD + c8 * 8);
+          kcs[i][0] = cs[0];
+          kcs[i][1] = cs[1];
+        }
       }
     }
   };
@@ -78,6 +106,12 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(const unsigned short
     uint4 v = make_uint4(0, 0, 0, 0);
     if (q0 + li < T && 32 * ks + 8 * g < HD)
       v = *reinterpret_cast<const uint4*>(base + (size_t)(q0 + li) * row + 32 * ks + 8 * g);
+    if constexpr (ROPE) {                            // rotated once: the fragments stay in registers for the whole loop
+      if (q0 + li < T) {
+        const float4* cs = reinterpret_cast<const float4*>(rope + (size_t)(q0 + li) * HD + 32 * ks + 8 * g);
+        v = rope_chunk(v, cs[0], cs[1]);
+      }
+    }
     qf[ks] = *reinterpret_cast<const bf16x8*>(&v);
   }
   const float sl2 = scale * AL_LOG2E;
@@ -93,6 +127,7 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(const unsigned short
     for (int i = 0; i < NLD; ++i) {
       const int idx = tid + 256 * i;
       const int r = idx / NCHP, c8 = idx - r * NCHP;
+      if constexpr (ROPE) kreg[i] = rope_chunk(kreg[i], kcs[i][0], kcs[i][1]);    // padding rows: zeros stay zeros
       if (idx < KB * NCHP) {
         *reinterpret_cast<uint4*>(Ks + r * LD + c8 * 8) = kreg[i];
         *reinterpret_cast<uint4*>(Vs + r * LD + c8 * 8) = vreg[i];
@@ -188,26 +223,54 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(const unsigned short
 }
 
 // CLS-row tap, per head: importance[b, h, t-1] = softmax_t(bf16(q_0 . k_t) * scale) / H, the arithmetic of
-// attn_tap.hip (fp32 dot in d order, round to bf16, scale, expf).  One workgroup per (image, head).
-template <int HD>
-__global__ __launch_bounds__(256) void attn_long_cls_kernel(const unsigned short* __restrict__ qkv, int T, int H,
-                                                            float scale, float* __restrict__ importance) {
+// attn_tap.hip (fp32 dot in d order, round to bf16, scale, expf).  One workgroup per (image, head).  ROPE: q_0 and
+// every k row are rotated by their table rows and rounded to bf16 in front of that dot.
+template <int HD, bool ROPE = false>
+__global__ __launch_bounds__(256) void attn_long_cls_kernel(
+    const unsigned short* __restrict__ qkv, int T, int H, float scale,
+    typename std::conditional<ROPE, AlRopeTap, float* __restrict__>::type tap) {
   __shared__ float logit[AL_MAXT];
   __shared__ float red[8];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
   const size_t row = (size_t)3 * H * HD;
   const unsigned short* base = qkv + (size_t)b * T * row;
+  float* __restrict__ importance;
+  const float* rope = nullptr;
+  if constexpr (ROPE) {
+    importance = tap.importance;
+    rope = tap.rope;
+  } else {
+    importance = tap;
+  }
   float q[HD];
+  if constexpr (ROPE) {
 #pragma unroll
-  for (int d = 0; d < HD; ++d) q[d] = bf16_bits_to_f32(base[(size_t)h * HD + d]);
+    for (int v = 0; v < HD / 8; ++v) {               // token 0's table row
+      const float4* cs = reinterpret_cast<const float4*>(rope + 8 * v);
+      const uint4 w = rope_chunk(*reinterpret_cast<const uint4*>(base + (size_t)h * HD + 8 * v), cs[0], cs[1]);
+      const unsigned int ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        q[8 * v + 2 * e] = __uint_as_float(ww[e] << 16);
+        q[8 * v + 2 * e + 1] = __uint_as_float(ww[e] & 0xffff0000u);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int d = 0; d < HD; ++d) q[d] = bf16_bits_to_f32(base[(size_t)h * HD + d]);
+  }
   float mx = -3.0e38f;
   for (int t = tid; t < T; t += 256) {
     const uint4* kp = reinterpret_cast<const uint4*>(base + (size_t)t * row + (size_t)(H + h) * HD);
     float dot = 0.f;
 #pragma unroll
     for (int v = 0; v < HD / 8; ++v) {
-      const uint4 w = kp[v];
+      uint4 w = kp[v];
+      if constexpr (ROPE) {
+        const float4* cs = reinterpret_cast<const float4*>(rope + (size_t)t * HD + 8 * v);
+        w = rope_chunk(w, cs[0], cs[1]);
+      }
       const unsigned int ww[4] = {w.x, w.y, w.z, w.w};
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -664,6 +727,23 @@ extern "C" int basd_attention_fwd_long_bf16(const void* qkv, int B, int T, int H
   if (hd == 64) launch_fwd_long<64>(qkv, B, T, H, scale, out, cls_importance, qmean_importance, lse, st);
   else launch_fwd_long<80>(qkv, B, T, H, scale, out, cls_importance, qmean_importance, lse, st);
   return check_launch("attention_fwd_long");
+}
+
+extern "C" int basd_attention_fwd_long_rope_bf16(const void* qkv, const float* rope, int B, int T, int H, int hd,
+                                                 float scale, void* out, float* cls_importance, void* stream) {
+  using namespace basd;
+  if (hd != 64 || T < 2 || T > AL_MAXT || H < 1 || B < 1 || rope == nullptr)
+    return fail(BASD_ERR_SHAPE, "attention_fwd_long_rope: B=%d T=%d H=%d hd=%d rope=%s unsupported (hd 64, 2 <= T <= %d, "
+                                "B, H >= 1, a table)", B, T, H, hd, rope == nullptr ? "NULL" : "given", AL_MAXT);
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned short* p = (const unsigned short*)qkv;
+  if (out != nullptr)
+    hipLaunchKernelGGL((attn_long_fwd_kernel<64, true>), dim3(B * H, (T + 63) / 64), dim3(256), 0, st, p, T, H, scale,
+                       (unsigned short*)out, rope);
+  if (cls_importance != nullptr)
+    hipLaunchKernelGGL((attn_long_cls_kernel<64, true>), dim3(B * H), dim3(256), 0, st, p, T, H, scale,
+                       AlRopeTap{cls_importance, rope});
+  return check_launch("attention_fwd_long_rope");
 }
 
 extern "C" int64_t basd_attention_bwd_long_workspace_bytes(int B, int T, int H, int hd) {

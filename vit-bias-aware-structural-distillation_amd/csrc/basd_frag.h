@@ -31,6 +31,18 @@ __device__ __forceinline__ unsigned int pack_bf16_bits(float lo, float hi) {
   return (unsigned int)f32_to_bf16_bits(lo) | ((unsigned int)f32_to_bf16_bits(hi) << 16);
 }
 
+// Rotary embedding of the attention kernels (attention.hip, attention_long.hip; ROPE): one word = the channel pair
+// (2i, 2i + 1) in bf16 -> the pair rotated by (c, s) = (cos, sin) in fp32, rounded to bf16 once
+__device__ __forceinline__ unsigned int rope_pair(unsigned int w, float c, float s) {
+  const float a = __uint_as_float(w << 16), b = __uint_as_float(w & 0xffff0000u);
+  return pack_bf16(fmaf(-b, s, a * c), fmaf(a, s, b * c));
+}
+// eight channels = four pairs; cs0 = (c, s) of the first two pairs, cs1 of the last two
+__device__ __forceinline__ uint4 rope_chunk(const uint4& v, const float4& cs0, const float4& cs1) {
+  return make_uint4(rope_pair(v.x, cs0.x, cs0.y), rope_pair(v.y, cs0.z, cs0.w), rope_pair(v.z, cs1.x, cs1.y),
+                    rope_pair(v.w, cs1.z, cs1.w));
+}
+
 // 8 bf16 of a 16-byte word <-> fp32; the packing goes through __float2bfloat16
 __device__ __forceinline__ void unpack8(const uint4& v, float (&f)[8]) {
   const unsigned int w[4] = {v.x, v.y, v.z, v.w};

@@ -7,9 +7,10 @@ rotation of q and k by per-token angles; the CLS token is not rotated), ``EvaMlp
 layers ``fc1_g`` / ``fc1_x`` and, for the base model, a LayerNorm between the gate and ``fc2``: "sub-LN") and both an
 absolute position embedding and the rotary one.  On the device a frozen bf16 block runs
 ``basd_attention_fwd_rope_bf16``: q and k are rotated in registers inside the attention kernel from an fp32 (cos, sin)
-table, the CLS-row tap is a by-product, and no rotated copy of q or k exists in memory.  The MLP runs
-``basd_gemm_bf16_swiglu`` on a packed [fc1_g; fc1_x] image built once, the LayerNorm kernel and the fc2 GEMM.
-Everywhere else (CPU, fp32, gradients, T > 272, head dim != 64) torch ops rotate q and k in front of SDPA and the MLP
+table, the CLS-row tap is a by-product, and no rotated copy of q or k exists in memory; past that kernel's 272 tokens
+(336 and 384 px inputs) ``basd_attention_fwd_long_rope_bf16`` does the same on the tiled kernels, up to 1024 tokens.  The
+MLP runs ``basd_gemm_bf16_swiglu`` on a packed [fc1_g; fc1_x] image built once, the LayerNorm kernel and the fc2 GEMM.
+Everywhere else (CPU, fp32, gradients, T > 1024, head dim != 64) torch ops rotate q and k in front of SDPA and the MLP
 is the unfused composition; on the device both are counted library fallbacks.
 
 WRITTEN WITHOUT timm AT HAND, from memory of timm 1.0.x ``eva.py`` and ``pos_embed_sincos.py``: the angle rule
@@ -92,11 +93,14 @@ class RopeAttention(Attention):
         on_device = ops.handles(qkv_flat)
         has_cls = self.tap is None or bool(self.tap["has_cls"])
         if (_FUSED_EVA_DISPATCH and on_device and not torch.is_grad_enabled() and qkv_flat.dtype == torch.bfloat16
-                and rope.dtype == torch.float32 and has_cls and ops.attention_fwd_rope_supported(t, self.head_dim)):
+                and rope.dtype == torch.float32 and has_cls
+                and (ops.attention_fwd_rope_supported(t, self.head_dim)
+                     or ops.attention_fwd_long_rope_supported(t, self.head_dim))):
             # frozen block: fused attention with q and k rotated in the kernel, the tap as a by-product
-            # (csrc/attention.hip, ROPE)
-            out_flat, imp = ops.attention_fwd_rope(qkv_flat, rope, self.num_heads, self.head_dim, self.scale,
-                                                   self.tap is not None)
+            # (csrc/attention.hip, ROPE; past its 272 tokens the tiled kernel of csrc/attention_long.hip, ROPE)
+            fwd = (ops.attention_fwd_rope if ops.attention_fwd_rope_supported(t, self.head_dim)
+                   else ops.attention_fwd_long_rope)
+            out_flat, imp = fwd(qkv_flat, rope, self.num_heads, self.head_dim, self.scale, self.tap is not None)
             if self.tap is not None:
                 self.tap["out"] = imp
             return self.proj(out_flat)

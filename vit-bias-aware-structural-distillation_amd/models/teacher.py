@@ -154,7 +154,8 @@ def load_teacher(model_name: str, img_size: int, *, weights: str | None = None, 
                  seed: int = 42, patch_size: int | None = None, dtype=torch.bfloat16, act: str | None = None,
                  norm_eps: float | None = None) -> TeacherModel:
     """Build (not download: reference teacher.py:113-148 fetches from the network) the named teacher -- a ViT preset of
-    ``models/vit.py``, a BEiT / BEiT-v2 preset of ``models/beit.py``, an EVA-02 preset of ``models/eva.py`` or a
+    ``models/vit.py``, a BEiT / BEiT-v2 preset of ``models/beit.py``, an EVA-02 preset of ``models/eva.py``, a DINOv3
+    preset of ``models/dinov3.py`` or a
     feature-map preset of ``models/cnn.py``
     (ResNet, ConvNeXt-V2 and the Swin family of ``models/swin.py``) -- frozen, in eval mode, weights pre-cast to bf16;
     ``weights`` = a local state dict (timm / torchvision parameter names).  The returned ``mean`` / ``std`` are the preset's (the reference reads them from
@@ -162,9 +163,10 @@ def load_teacher(model_name: str, img_size: int, *, weights: str | None = None, 
     ``act`` / ``norm_eps`` override a ViT preset's MLP activation and LayerNorm epsilon."""
     from .beit import BEIT_PRESETS, create_beit, load_timm_state_dict
     from .cnn import CNN_PRESETS, create_cnn
+    from .dinov3 import DINOV3_PRESETS, create_dinov3, load_dinov3_state_dict
     from .eva import EVA_PRESETS, create_eva, load_eva_state_dict
     base = model_name.split(".", 1)[0]
-    known = (VIT_PRESETS, CNN_PRESETS, BEIT_PRESETS, EVA_PRESETS)
+    known = (VIT_PRESETS, CNN_PRESETS, BEIT_PRESETS, EVA_PRESETS, DINOV3_PRESETS)
     if not any(model_name in k for k in known) and any(base in k for k in known):
         model_name = base      # timm's pretrained tag ("convnextv2_tiny.fcmae", "..._clip_224.openai"): weights are local
     gen_state = torch.random.get_rng_state()
@@ -182,9 +184,12 @@ def load_teacher(model_name: str, img_size: int, *, weights: str | None = None, 
     elif model_name in EVA_PRESETS:
         model = create_eva(model_name, img_size=img_size, patch_size=patch_size)
         mean, std = EVA_PRESETS[model_name][7:9]
+    elif model_name in DINOV3_PRESETS:
+        model = create_dinov3(model_name, img_size=img_size, patch_size=patch_size)
+        mean, std = DINOV3_PRESETS[model_name][4:6]
     else:
         raise ValueError(f"teacher {model_name!r}: not a known preset "
-                         f"({sorted(VIT_PRESETS) + sorted(CNN_PRESETS) + sorted(BEIT_PRESETS) + sorted(EVA_PRESETS)}); "
+                         f"({sorted(VIT_PRESETS) + sorted(CNN_PRESETS) + sorted(BEIT_PRESETS) + sorted(EVA_PRESETS) + sorted(DINOV3_PRESETS)}); "
                          "wrap your own module in TeacherModel(...) with the fields probe_model() returns")
     torch.random.set_rng_state(gen_state)
     if weights:
@@ -194,12 +199,16 @@ def load_teacher(model_name: str, img_size: int, *, weights: str | None = None, 
             load_timm_state_dict(model, state)       # timm's gamma_1 / gamma_2 names, a checked bias-table size
         elif model_name in EVA_PRESETS:
             load_eva_state_dict(model, state)        # q_proj / k_proj / v_proj of the base checkpoint, a checked pos_embed
+        elif model_name in DINOV3_PRESETS:
+            load_dinov3_state_dict(model, state)     # hub / timm names; q / k rows interleaved for the rotation kernels
         elif model_name in VIT_PRESETS:
             model.load_state_dict(dinov2_state_dict(model, state), strict=False)    # hub / timm names of the DINOv2 family
         else:
             model.load_state_dict(state, strict=False)
     if model_name in BEIT_PRESETS or model_name in EVA_PRESETS:
         model.materialize_qkv_bias()                 # cat(q_bias, 0, v_bias) as the qkv layer's bias: one fused GEMM
+    if model_name in DINOV3_PRESETS:
+        model.interleave_rope_pairs()                # k bias zeroed; a no-op after load_dinov3_state_dict
     model = model.to(device).eval()
     for p in model.parameters():
         p.requires_grad = False
