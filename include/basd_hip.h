@@ -71,6 +71,8 @@
  *   basd_attention_fwd_long_rope_bf16
  *                          the same rotary forward for 273 .. 1024 tokens (DINOv3 and EVA-02 teachers at 384 px) on
  *                          the tiled kernels; DINOv3's half-split pairs are interleaved in the weights at load time
+ *   basd_attention_fwd_long_relbias_bf16
+ *                          the same biased forward for 273 .. 1024 tokens (BEiT teachers at 384 px) on the tiled kernels
  *   basd_layernorm_fwd_bf16 / _bwd_bf16, basd_add_layernorm_fwd_bf16
  *                          timm nn.LayerNorm of the ViT blocks (student: with backward; frozen teacher: fused with
  *                          the residual add in front of it)
@@ -560,6 +562,22 @@ int basd_attention_fwd_rope_bf16(const void* qkv, const float* rope, int B, int 
  * synchronisation. */
 int basd_attention_fwd_long_rope_bf16(const void* qkv, const float* rope, int B, int T, int H, int hd, float scale,
                                       void* out, float* cls_importance, void* stream);
+
+/* BEiT's relative-position bias on the tiled kernels of basd_attention_fwd_long_bf16, for the token counts
+ * basd_attention_fwd_relbias_bf16 refuses (BEiT at 384 px: 577 tokens): same qkv ([B, T, 3, H, hd] bf16, CLS token
+ * first, T = gh * gw + 1), table (fp32 [R, H], R = (2 gh - 1)(2 gw - 1) + 3), index rule and out ([B, T, H * hd] bf16).
+ * Logit of query i and key j: fp32(q_i . k_j) * scale + table[idx(i, j)][h]; the kernel stages the head's column
+ * divided by scale in LDS and adds it to the raw fp32 dot in front of the online softmax's running maximum, so with an
+ * all-zero table out and cls_importance are basd_attention_fwd_long_bf16's bit for bit.  No [T, T] or [H, T, T] array is
+ * read or written.  cls_importance (nullable): [B, H, T-1] fp32, the CLS tap of basd_attention_fwd_long_bf16 plus the
+ * bias: fp32 dot in d order, rounded to bf16, times scale, + table[R - 1][h] for key 0 and table[R - 3][h] for every
+ * patch key, expf, softmax without the CLS column, divided by H.  (The short entry taps its main softmax with fp32
+ * logits instead; both are within bf16 rounding of the exact row.)  No LSE and no query-mean output: BEiT always has a
+ * CLS token.  hd == 64, gh, gw >= 1, 2 <= T <= 1024 (the short entry's range included), B, H >= 1, qkv, table and out
+ * != NULL, scale finite and > 0; anything else is BASD_ERR_SHAPE without a launch and nothing is written.  No
+ * allocation, no synchronisation. */
+int basd_attention_fwd_long_relbias_bf16(const void* qkv, const float* table, int B, int gh, int gw, int H, int hd,
+                                         float scale, void* out, float* cls_importance, void* stream);
 
 /* Fused attention backward of a trained block (the student; reference src/training/trainer.py:157 through timm
  * Attention.forward): qkv [B, T, 3, H, hd] bf16, out / dout [B, T, H * hd] bf16 (forward output and its gradient),

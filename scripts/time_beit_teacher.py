@@ -8,9 +8,13 @@ Every round is a FRESH child process with its own time limit; inside a child the
 ``--kernel`` adds one more child: the attention call alone at ViT-B shape (B x 12 heads x 197 tokens) -- the new kernel,
 the existing unbiased kernel on the same qkv (what the in-kernel gather costs) and the library form.
 
+``--img-size 384`` times the beit_base_patch16_384 teacher instead (a 24 x 24 grid, 577 tokens: the tiled kernels,
+basd_attention_fwd_long_relbias_bf16) at the same batch, and ``--kernel`` then runs the attention call alone at
+B x 12 heads x 577 tokens.
+
 Device events, warm-up, medians of N timed calls.
 
-    python scripts/time_beit_teacher.py [--batch 256] [--iters 10] [--rounds 3] [--kernel] [--limit 300]"""
+    python scripts/time_beit_teacher.py [--img-size 224] [--batch 256] [--iters 10] [--rounds 3] [--kernel] [--limit 300]"""
 import argparse
 import json
 import os
@@ -19,7 +23,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MODEL = "beitv2_base_patch16_224"
+MODELS = {224: "beitv2_base_patch16_224", 384: "beit_base_patch16_384"}
 
 
 def median_ms(fn, iters, warmup=3):
@@ -43,13 +47,14 @@ def child_forward(args):
     import basd_amd.losses._ops as O
     import basd_amd.models.beit as B
     from basd_amd.models import extract_intermediates, load_teacher
-    teacher = load_teacher(MODEL, 224, device="cuda")
+    model = MODELS[args.img_size]
+    teacher = load_teacher(model, args.img_size, device="cuda")
     g = torch.Generator().manual_seed(1)
     with torch.no_grad():      # a fresh BEiT has zero-mean 0.02 tables: give the bias the spread of a trained one
         for blk in teacher.model.blocks:
             t = blk.attn.relative_position_bias_table
             t.copy_(1.5 * torch.randn(t.shape, generator=g))
-    x = torch.randn(args.batch, 3, 224, 224, device="cuda").to(torch.bfloat16)
+    x = torch.randn(args.batch, 3, args.img_size, args.img_size, device="cuda").to(torch.bfloat16)
 
     def run(fused):
         B._FUSED_RELBIAS_ATTENTION = fused
@@ -64,7 +69,7 @@ def child_forward(args):
     rel = float((ta[last].float() - tb[last].float()).norm() / tb[last].float().norm())
     tap = float((ia[last] - ib[last]).abs().max() / ib[last].abs().max())
     del ta, ia, tb, ib
-    out = {"model": MODEL, "batch": args.batch, "iters": args.iters, "round": args.round,
+    out = {"model": model, "img_size": args.img_size, "batch": args.batch, "iters": args.iters, "round": args.round,
            "own_vs_library_rel_l2_last_layer": rel, "own_vs_library_tap_max_rel": tap}
     for name in (("own", "library") if args.round % 2 == 0 else ("library", "own")):
         out[f"{name}_ms"] = median_ms(sides[name], args.iters)
@@ -78,7 +83,7 @@ def child_kernel(args):
     import torch.nn.functional as F
     import basd_amd._native as native
     from basd_amd.models.beit import relative_position_index
-    b, heads, hd, gh, gw = args.batch, 12, 64, 14, 14
+    b, heads, hd, gh, gw = args.batch, 12, 64, args.img_size // 16, args.img_size // 16
     t, scale = gh * gw + 1, 64 ** -0.5
     g = torch.Generator(device="cuda").manual_seed(0)
     qkv = torch.randn(b, t, 3 * heads * hd, device="cuda", generator=g).bfloat16()
@@ -92,7 +97,10 @@ def child_kernel(args):
         tap = logits.softmax(dim=-1)[:, :, 0, 1:].mean(dim=1)
         return F.scaled_dot_product_attention(q, k, v, attn_mask=bias.unsqueeze(0).to(q.dtype)), tap
 
-    cases = [("relbias_kernel", lambda: native.attention_fwd_relbias(qkv, table, gh, gw, heads, hd, scale, True)),
+    # the entry RelPosAttention.forward takes at this grid; attention_fwd dispatches the unbiased call the same way
+    relbias = (native.attention_fwd_relbias if native.attention_fwd_relbias_supported(gh, gw, hd)
+               else native.attention_fwd_long_relbias)
+    cases = [("relbias_kernel", lambda: relbias(qkv, table, gh, gw, heads, hd, scale, True)),
              ("unbiased_kernel", lambda: native.attention_fwd(qkv, heads, hd, scale, want_importance=True)),
              ("library_mask_sdpa_tap", library)]
     out = {"what": "attention call alone", "B": b, "H": heads, "T": t, "hd": hd, "iters": args.iters}
@@ -105,6 +113,7 @@ def child_kernel(args):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--img-size", type=int, default=224, choices=sorted(MODELS))
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=3)
@@ -122,7 +131,8 @@ def main():
         return
     # the parent never touches the GPU: every measurement is a fresh child under its own time limit, and the first
     # child that fails, faults or runs out of time ends the run
-    base = [sys.executable, os.path.abspath(__file__), "--batch", str(args.batch), "--iters", str(args.iters)]
+    base = [sys.executable, os.path.abspath(__file__), "--img-size", str(args.img_size), "--batch", str(args.batch),
+            "--iters", str(args.iters)]
     jobs = [base + ["--child", "forward", "--round", str(r)] for r in range(max(args.rounds, 3))]
     if args.kernel:
         jobs.append(base + ["--child", "kernel"])

@@ -42,7 +42,7 @@ EXPORTS = (
     "basd_sym_tridiag_f64_workspace_bytes", "basd_sym_tridiag_f64", "basd_tridiag_mp_rank",
     "basd_window_attention_fwd_bf16", "basd_patch_merge_ln_bf16", "basd_gemm_bf16_act", "basd_vit_embed_bf16",
     "basd_attention_fwd_relbias_bf16", "basd_gemm_bf16_swiglu", "basd_vit_embed_reg_bf16",
-    "basd_attention_fwd_rope_bf16", "basd_attention_fwd_long_rope_bf16",
+    "basd_attention_fwd_rope_bf16", "basd_attention_fwd_long_rope_bf16", "basd_attention_fwd_long_relbias_bf16",
 )
 
 
@@ -101,6 +101,7 @@ _SIGNATURES = {
     "basd_attention_fwd_relbias_bf16": (_P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P),
     "basd_attention_fwd_rope_bf16": (_P, _P, _I, _I, _I, _I, _F, _P, _P, _P),
     "basd_attention_fwd_long_rope_bf16": (_P, _P, _I, _I, _I, _I, _F, _P, _P, _P),
+    "basd_attention_fwd_long_relbias_bf16": (_P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P),
     "basd_attention_bwd_bf16": (_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P),
     "basd_attention_fwd_long_bf16": (_P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P),
     "basd_attention_bwd_long_workspace_bytes": (_I, _I, _I, _I),
@@ -1192,6 +1193,29 @@ def attention_fwd_relbias(qkv: torch.Tensor, table: torch.Tensor, gh: int, gw: i
     _check(lib().basd_attention_fwd_relbias_bf16(_ptr(qkv), _ptr(table), b, gh, gw, heads, head_dim,
                                                  ctypes.c_float(scale), _ptr(out), _ptr(imp), _stream()),
            "basd_attention_fwd_relbias_bf16")
+    return out, (imp.sum(dim=1) if want_importance else None)
+
+
+def attention_fwd_long_relbias_supported(gh: int, gw: int, hd: int) -> bool:
+    """the range of ``basd_attention_fwd_long_relbias_bf16``: the tiled kernel's token count from 2 up, head dim 64"""
+    return hd == 64 and gh >= 1 and gw >= 1 and gh * gw + 1 <= LONG_ATTENTION_MAX_T
+
+
+def attention_fwd_long_relbias(qkv: torch.Tensor, table: torch.Tensor, gh: int, gw: int, heads: int, head_dim: int,
+                               scale: float, want_importance: bool = False):
+    """``attention_fwd_relbias`` on the tiled kernels (csrc/attention_long.hip, RELBIAS), for the token counts the short
+    entry refuses; arguments and results are the same.  The importance is the CLS tap of ``attention_fwd``'s long kernel
+    (bf16-rounded logits) with the CLS row's bias added to the scaled logits."""
+    _need_cuda(qkv, table)
+    b, t = qkv.shape[0], qkv.shape[1]
+    assert qkv.dtype == torch.bfloat16 and qkv.shape[-1] == 3 * heads * head_dim and t == gh * gw + 1
+    assert table.dtype == torch.float32 and tuple(table.shape) == ((2 * gh - 1) * (2 * gw - 1) + 3, heads)
+    qkv, table = qkv.contiguous(), table.contiguous()
+    out = torch.empty(b, t, heads * head_dim, dtype=torch.bfloat16, device=qkv.device)
+    imp = torch.empty(b, heads, t - 1, dtype=torch.float32, device=qkv.device) if want_importance else None
+    _check(lib().basd_attention_fwd_long_relbias_bf16(_ptr(qkv), _ptr(table), b, gh, gw, heads, head_dim,
+                                                      ctypes.c_float(scale), _ptr(out), _ptr(imp), _stream()),
+           "basd_attention_fwd_long_relbias_bf16")
     return out, (imp.sum(dim=1) if want_importance else None)
 
 

@@ -25,6 +25,14 @@
 //   rotated in registers between its global load and its LDS store -- its eight table floats travel with it through the
 //   prefetch registers -- and the Q fragments once in front of the key loop.  The CLS tap rotates q_0 and every k row
 //   the same way before its dot: it is the tap above on the rotated, bf16-rounded operands.  No LSE, no query mean.
+// RELBIAS (basd_attention_fwd_long_relbias_bf16; frozen BEiT / BEiT-v2 teachers past the 272 tokens of attention.hip):
+//   the logit of query i and key j is fp32(q_i . k_j) * scale + table[idx(i, j)][h], the index rule of attention.hip.
+//   Every workgroup stages the head's column of the table, divided by scale, in LDS (R <= 4095 floats for T <= 1024)
+//   next to koff[key] = y_k (2 gw - 1) + x_k of every patch key; a lane -- one query column for the whole loop -- adds
+//   tab[qb - koff[key]] to the raw accumulator of each of its keys in front of the tile's maximum, so the online softmax
+//   below it is the plain kernel's to the instruction (an all-zero table gives the plain kernel's bits) and a masked
+//   tail key stays masked.  The CLS row's bias is two constants per head: the tap adds them to its scaled, bf16-rounded
+//   logits.  Nothing [T, T] is read or written.  No LSE, no query mean.
 //
 // Backward (FA2): attn_long_delta_kernel computes delta = rowsum(dO * O); attn_long_bwd_kernel runs one workgroup per
 // (image, head, 128-key block), wave w owning 32 keys whose K / V fragments and dK^T / dV^T accumulators stay in
@@ -48,12 +56,27 @@ struct AlRopeTap {
   const float* rope;                                 // [T, HD / 2, 2] fp32 (cos, sin)
 };
 
+// The RELBIAS instantiations take these in the same two slots.
+struct AlRelBias {
+  const float* table;                                // [R, H] fp32, heads on the fast axis
+  int gh, gw;                                        // patch grid: T = gh * gw + 1, CLS token first
+};
+struct AlRelTap {
+  float* importance;
+  const float* table;
+  int R;                                             // (2 gh - 1)(2 gw - 1) + 3
+};
+constexpr int AL_MAXR = 4096;                        // R <= 4 gh gw + 3 <= 4095 for T <= AL_MAXT
+
 // ------------------------------------------------------------------------------------------------------ forward ----
-template <int HD, bool ROPE = false>
+template <int HD, bool ROPE = false, bool RELBIAS = false>
 __global__ __launch_bounds__(256) void attn_long_fwd_kernel(
     const unsigned short* __restrict__ qkv, int T, int H, float scale, unsigned short* __restrict__ out,
-    typename std::conditional<ROPE, const float*, float*>::type __restrict__ lse_or_rope) {
+    typename std::conditional<RELBIAS, AlRelBias,
+                              typename std::conditional<ROPE, const float* __restrict__, float* __restrict__>::type>::type
+        lse_or_rope) {
   static_assert(!ROPE || HD == 64, "the rotary embedding: head dim 64 (whole 32-deep steps)");
+  static_assert(!RELBIAS || (!ROPE && HD == 64), "the relative-position bias: head dim 64, no rotary embedding");
   constexpr int KB = 64;                             // keys per LDS tile
   constexpr int NDS = (HD + 31) / 32;                // 32-deep steps of the Q K^T contraction
   constexpr int NDT = HD / 16;                       // 16-column tiles of the output
@@ -73,8 +96,18 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(
 
   float* lse = nullptr;
   const float* rope = nullptr;
-  if constexpr (ROPE) rope = lse_or_rope;
-  else lse = lse_or_rope;
+  float* tab = nullptr;                              // RELBIAS: the head's column of the table / scale, [R]
+  int* koff = nullptr;                               // RELBIAS: y_k (2 gw - 1) + x_k of patch key k, [AL_MAXT]
+  if constexpr (RELBIAS) {
+    __shared__ float tab_s[AL_MAXR];
+    __shared__ __align__(16) int koff_s[AL_MAXT];
+    tab = tab_s;
+    koff = koff_s;
+  } else if constexpr (ROPE) {
+    rope = lse_or_rope;
+  } else {
+    lse = lse_or_rope;
+  }
 
   uint4 kreg[NLD], vreg[NLD];
   float4 kcs[ROPE ? NLD : 1][2];                     // ROPE: (cos, sin) of the four pairs of every K chunk
@@ -114,6 +147,37 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(
     }
     qf[ks] = *reinterpret_cast<const bf16x8*>(&v);
   }
+  // RELBIAS: this lane's query q0 + li reads tab[qb - koff[k]] against patch key k; a CLS (or padding) query reads the
+  // constant row R - 3; against the CLS key it is row c0.  The first barrier of the key loop publishes tab and koff.
+  int qb = 0, c0 = 0;
+  bool qpatch = false;
+  if constexpr (RELBIAS) {
+    const int gh = lse_or_rope.gh, gw = lse_or_rope.gw;
+    const int rl = 2 * gw - 1;                       // table rows per step in y
+    const int R = (2 * gh - 1) * rl + 3;
+    for (int i0 = 0; i0 < R; i0 += 1024) {
+      float tv[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int idx = i0 + tid + 256 * i;
+        tv[i] = (idx < R) ? lse_or_rope.table[(size_t)idx * H + h] / scale : 0.f;
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int idx = i0 + tid + 256 * i;
+        if (idx < R) tab[idx] = tv[i];
+      }
+    }
+    for (int key = tid; key < AL_MAXT; key += 256) {   // CLS and padding keys: 0 (overridden below / masked)
+      const int yk = (key >= 1 && key < T) ? (key - 1) / gw : 0;
+      koff[key] = (key >= 1 && key < T) ? yk * rl + (key - 1 - yk * gw) : 0;
+    }
+    const int qi = q0 + li;
+    qpatch = qi >= 1 && qi < T;
+    const int yq = qpatch ? (qi - 1) / gw : 0;
+    qb = qpatch ? (yq + gh - 1) * rl + (qi - 1 - yq * gw) + gw - 1 : R - 3;
+    c0 = qpatch ? R - 2 : R - 1;
+  }
   const float sl2 = scale * AL_LOG2E;
   float m_run = -3.0e38f, l_run = 0.f;               // per query column li (same value in the four lane groups)
   f32x4 o[NDT];
@@ -146,6 +210,19 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kk, qf[ks], acc, 0, 0, 0);
       }
       s[kt] = acc;
+    }
+    if constexpr (RELBIAS) {                         // s += table[idx(query, key)] / scale: keys k0 + 16 kt + 4 g + r
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt) {
+        const int4 ko = *reinterpret_cast<const int4*>(koff + k0 + 16 * kt + 4 * g);
+        const int kk[4] = {ko.x, ko.y, ko.z, ko.w};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          int idx = qpatch ? qb - kk[r] : qb;
+          if (kt == 0 && r == 0 && k0 == 0 && g == 0) idx = c0;       // the CLS key
+          s[kt][r] += tab[idx];
+        }
+      }
     }
     // ---- online softmax of this tile
     float mx = -3.0e38f;
@@ -224,11 +301,14 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(
 
 // CLS-row tap, per head: importance[b, h, t-1] = softmax_t(bf16(q_0 . k_t) * scale) / H, the arithmetic of
 // attn_tap.hip (fp32 dot in d order, round to bf16, scale, expf).  One workgroup per (image, head).  ROPE: q_0 and
-// every k row are rotated by their table rows and rounded to bf16 in front of that dot.
-template <int HD, bool ROPE = false>
+// every k row are rotated by their table rows and rounded to bf16 in front of that dot.  RELBIAS: the CLS row's bias,
+// table[R - 1][h] for key 0 and table[R - 3][h] for every patch key, is added to the scaled logit.
+template <int HD, bool ROPE = false, bool RELBIAS = false>
 __global__ __launch_bounds__(256) void attn_long_cls_kernel(
     const unsigned short* __restrict__ qkv, int T, int H, float scale,
-    typename std::conditional<ROPE, AlRopeTap, float* __restrict__>::type tap) {
+    typename std::conditional<RELBIAS, AlRelTap,
+                              typename std::conditional<ROPE, AlRopeTap, float* __restrict__>::type>::type tap) {
+  static_assert(!RELBIAS || (!ROPE && HD == 64), "the relative-position bias: head dim 64, no rotary embedding");
   __shared__ float logit[AL_MAXT];
   __shared__ float red[8];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -237,7 +317,12 @@ __global__ __launch_bounds__(256) void attn_long_cls_kernel(
   const unsigned short* base = qkv + (size_t)b * T * row;
   float* __restrict__ importance;
   const float* rope = nullptr;
-  if constexpr (ROPE) {
+  float bias_cls = 0.f, bias_patch = 0.f;            // RELBIAS: the CLS query against the CLS key / against a patch key
+  if constexpr (RELBIAS) {
+    importance = tap.importance;
+    bias_cls = tap.table[(size_t)(tap.R - 1) * H + h];
+    bias_patch = tap.table[(size_t)(tap.R - 3) * H + h];
+  } else if constexpr (ROPE) {
     importance = tap.importance;
     rope = tap.rope;
   } else {
@@ -280,7 +365,8 @@ __global__ __launch_bounds__(256) void attn_long_cls_kernel(
     }
     unsigned int bits = __float_as_uint(dot);
     bits += 0x7fffu + ((bits >> 16) & 1u);
-    const float l = __uint_as_float(bits & 0xffff0000u) * scale;
+    float l = __uint_as_float(bits & 0xffff0000u) * scale;
+    if constexpr (RELBIAS) l += (t == 0) ? bias_cls : bias_patch;
     logit[t] = l;
     mx = fmaxf(mx, l);
   }
@@ -744,6 +830,28 @@ extern "C" int basd_attention_fwd_long_rope_bf16(const void* qkv, const float* r
     hipLaunchKernelGGL((attn_long_cls_kernel<64, true>), dim3(B * H), dim3(256), 0, st, p, T, H, scale,
                        AlRopeTap{cls_importance, rope});
   return check_launch("attention_fwd_long_rope");
+}
+
+extern "C" int basd_attention_fwd_long_relbias_bf16(const void* qkv, const float* table, int B, int gh, int gw, int H,
+                                                    int hd, float scale, void* out, float* cls_importance,
+                                                    void* stream) {
+  using namespace basd;
+  const int64_t T64 = (gh >= 1 && gw >= 1) ? (int64_t)gh * gw + 1 : 0;
+  if (hd != 64 || T64 < 2 || T64 > AL_MAXT || H < 1 || B < 1 || qkv == nullptr || table == nullptr || out == nullptr ||
+      !(scale > 0.f) || !(scale <= 3.0e38f))
+    return fail(BASD_ERR_SHAPE, "attention_fwd_long_relbias: B=%d grid %d x %d H=%d hd=%d scale=%g qkv / table / out=%s unsupported "
+                                "(hd 64, 2 <= gh * gw + 1 <= %d, B, H >= 1, the three pointers, a finite scale > 0)",
+                B, gh, gw, H, hd, (double)scale,
+                (qkv == nullptr || table == nullptr || out == nullptr) ? "a NULL" : "given", AL_MAXT);
+  const int T = (int)T64;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned short* p = (const unsigned short*)qkv;
+  hipLaunchKernelGGL((attn_long_fwd_kernel<64, false, true>), dim3(B * H, (T + 63) / 64), dim3(256), 0, st, p, T, H,
+                     scale, (unsigned short*)out, AlRelBias{table, gh, gw});
+  if (cls_importance != nullptr)
+    hipLaunchKernelGGL((attn_long_cls_kernel<64, false, true>), dim3(B * H), dim3(256), 0, st, p, T, H, scale,
+                       AlRelTap{cls_importance, table, (2 * gh - 1) * (2 * gw - 1) + 3});
+  return check_launch("attention_fwd_long_relbias");
 }
 
 extern "C" int64_t basd_attention_bwd_long_workspace_bytes(int B, int T, int H, int hd) {

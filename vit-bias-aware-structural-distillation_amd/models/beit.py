@@ -5,10 +5,11 @@ The model is the plain ViT of ``models/vit.py`` -- the same ``Block``, ``Mlp``, 
 ``BasdLinear`` -- with three differences: no ``pos_embed``; LayerScale on both branches (timm's ``gamma_1`` /
 ``gamma_2``, here ``ls1.gamma`` / ``ls2.gamma`` so that ``fold_layerscale`` folds them and the frozen blocks take the
 fused inference path); and ``RelPosAttention``, which adds ``relative_position_bias_table[index(i, j)][head]`` to the
-logit of query i and key j.  On the device a frozen bf16 block runs ``basd_attention_fwd_relbias_bf16``: the bias is
-gathered inside the attention kernel from the head's column of the table, the CLS-row tap is a by-product, and no
-[T, T] or [H, T, T] bias exists in memory.  Everywhere else (CPU, fp32, gradients, T > 272, head dim != 64) the torch
-path builds the dense bias from an index buffer; on the device that is a counted library fallback.
+logit of query i and key j.  On the device a frozen bf16 block runs ``basd_attention_fwd_relbias_bf16`` up to 272 tokens
+and ``basd_attention_fwd_long_relbias_bf16`` (the tiled kernels) from there to 1024 tokens -- 384 px at patch 16 has
+577: the bias is gathered inside the attention kernel from the head's column of the table, the CLS-row tap is a
+by-product, and no [T, T] or [H, T, T] bias exists in memory.  Everywhere else (CPU, fp32, gradients, T > 1024, head dim
+!= 64) the torch path builds the dense bias from an index buffer; on the device that is a counted library fallback.
 
 WRITTEN WITHOUT timm AT HAND, from memory of timm 1.0.x ``beit.py``: the index rule (``relbias_index`` in
 ``_native.py``: pairwise coordinate differences shifted to be non-negative, row-major over (2 gh - 1) x (2 gw - 1), then
@@ -105,15 +106,20 @@ class RelPosAttention(Attention):
         on_device = ops.handles(qkv_flat)
         has_cls = self.tap is None or bool(self.tap["has_cls"])
         if (_FUSED_RELBIAS_ATTENTION and on_device and not torch.is_grad_enabled() and qkv_flat.dtype == torch.bfloat16
-                and table.dtype == torch.float32 and has_cls
-                and ops.attention_fwd_relbias_supported(gh, gw, self.head_dim)):
+                and table.dtype == torch.float32 and has_cls):
             # frozen block: fused attention with the bias gathered in the kernel, the tap as a by-product
-            # (csrc/attention.hip, RELBIAS)
-            out_flat, imp = ops.attention_fwd_relbias(qkv_flat, table, gh, gw, self.num_heads, self.head_dim, self.scale,
-                                                      self.tap is not None)
-            if self.tap is not None:
-                self.tap["out"] = imp
-            return self.proj(out_flat)
+            # (csrc/attention.hip, RELBIAS; past its 272 tokens the tiled kernels of csrc/attention_long.hip, RELBIAS)
+            fused = None
+            if ops.attention_fwd_relbias_supported(gh, gw, self.head_dim):
+                fused = ops.attention_fwd_relbias
+            elif ops.attention_fwd_long_relbias_supported(gh, gw, self.head_dim):
+                fused = ops.attention_fwd_long_relbias
+            if fused is not None:
+                out_flat, imp = fused(qkv_flat, table, gh, gw, self.num_heads, self.head_dim, self.scale,
+                                      self.tap is not None)
+                if self.tap is not None:
+                    self.tap["out"] = imp
+                return self.proj(out_flat)
         if on_device:
             library_fallback("attention (relative bias)", f"grid={gh}x{gw} head_dim={self.head_dim} "
                                                           f"dtype={qkv_flat.dtype} grad={torch.is_grad_enabled()}")
@@ -175,6 +181,11 @@ BEIT_PRESETS = {
     "beit_large_patch16_224": (1024, 24, 16, 16, 1e-5, HALF_MEAN, HALF_STD),
     "beitv2_base_patch16_224": (768, 12, 12, 16, 1e-5, IMAGENET_MEAN, IMAGENET_STD),
     "beitv2_large_patch16_224": (1024, 24, 16, 16, 1e-5, IMAGENET_MEAN, IMAGENET_STD),
+    # the 384 px fine-tunes of BEiT v1 (24 x 24 grid, 577 tokens: the tiled attention), from memory of timm like the
+    # rest: the architecture and the 0.5 / 0.5 statistics of their 224 px namesakes.  A checkpoint must arrive with the
+    # 47 x 47 + 3 row table of that grid (tables are not resampled).  beit_large_patch16_512 (1025 tokens) is not here.
+    "beit_base_patch16_384": (768, 12, 12, 16, 0.1, HALF_MEAN, HALF_STD),
+    "beit_large_patch16_384": (1024, 24, 16, 16, 1e-5, HALF_MEAN, HALF_STD),
 }
 
 # keys of a timm checkpoint that have no counterpart here: the index is rebuilt from the grid, the head is not built
