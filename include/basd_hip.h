@@ -92,6 +92,8 @@
  *   basd_window_attention_fwd_bf16, basd_patch_merge_ln_bf16
  *                          the frozen Swin teacher trunk (src/models/teacher.py through timm: the `layers` container and
  *                          the nhwc feature map its probe understands)
+ *   basd_window_attention_fwd_wide_bf16
+ *                          the window attention of that trunk for windows 9 .. 16 (the window-12 checkpoints at 384 px)
  *   basd_resample_u8, basd_ta_normalize_u8
  *                          the torchvision v2 transforms of both training views (src/data/datasets.py:80-94 clean /
  *                          evaluation view, :137-149 augmented view), which the reference runs in its loader workers
@@ -832,6 +834,19 @@ int basd_add_relu_bf16(void* y, const void* r, int64_t rows, int C, int ld_y, in
  * must not alias qkv.  Anything else is BASD_ERR_SHAPE without a launch. */
 int basd_window_attention_fwd_bf16(const void* qkv, const float* bias, int B, int H, int W, int heads, int C, int ws,
                                    int shift, int ld_qkv, int ld_out, float scale, void* out, void* stream);
+
+/* The same attention for windows of 9 x 9 to 16 x 16 slots (window 12 of the 384 px Swin checkpoints), which the entry
+ * above refuses: rows, roll / partition index arithmetic, label mask (-100.0 in fp32), rounding points (fp32 logits
+ * fmaf(q . k, scale, bias) + mask, fp32 softmax over the whole row, probabilities rounded to bf16, one rounding at the
+ * store) and the zero pad columns of out are exactly those of basd_window_attention_fwd_bf16.
+ * table: timm's relative_position_bias_table itself, fp32 [(2 ws - 1)^2, heads] (NOT an expanded image); the logit of
+ * query slot (iy_q, ix_q) and key slot (iy_k, ix_k) reads row (iy_q - iy_k + ws - 1)(2 ws - 1) + (ix_q - ix_k + ws - 1).
+ * One workgroup of four waves per (window, head); no atomics: the same input gives the same bits.
+ * 9 <= ws <= 16, 0 <= shift < ws, H % ws == 0, W % ws == 0, C == 32 heads, ld % 8 == 0, 3 C <= ld_qkv, C <= ld_out,
+ * 16-byte aligned buffers, B (H / ws)(W / ws) heads < 2^31; out must not alias qkv.  Anything else is BASD_ERR_SHAPE
+ * without a launch. */
+int basd_window_attention_fwd_wide_bf16(const void* qkv, const float* table, int B, int H, int W, int heads, int C,
+                                        int ws, int shift, int ld_qkv, int ld_out, float scale, void* out, void* stream);
 
 /* Patch merging + LayerNorm: x [B, H, W, ld_in] bf16 with C channels -> y [B, H/2, W/2, 4 C] bf16 (contiguous),
  *   y[b, r, c, :] = LayerNorm_{4 C}(concat(x[b, 2r, 2c], x[b, 2r+1, 2c], x[b, 2r, 2c+1], x[b, 2r+1, 2c+1])),

@@ -1,12 +1,13 @@
-"""forward_features of the frozen swin_tiny_patch4_window7_224 teacher at 224 px, bf16: the fused trunk (csrc/swin.hip +
-basd_gemm_bf16 + the LayerNorm kernels) against the plain-torch path of the same module (library GEMMs, torch softmax
-and index gathers), in one process.  The parent of this model does not exist, so the library path of the same box is
+"""forward_features of a frozen Swin teacher (default swin_tiny_patch4_window7_224 at 224 px), bf16: the fused trunk
+(csrc/swin.hip, csrc/swin_wide.hip for the window-12 presets + basd_gemm_bf16 + the LayerNorm kernels) against the
+plain-torch path of the same module (library GEMMs, torch softmax and index gathers), in one process.  The parent of this model does not exist, so the library path of the same box is
 the only baseline.
 
 Device events, warm-up, medians of N timed forwards per side; the two sides alternate for ``--rounds`` rounds and every
-round prints one JSON line (the raw lines of profiles/swin_trunk_ab.txt).
+round prints one JSON line (the raw lines of profiles/swin_trunk_ab.txt and profiles/swin_384_teacher_ab.txt).
 
-    python scripts/time_swin.py [--batch 256] [--iters 10] [--rounds 3] [--once fused|library]
+    python scripts/time_swin.py [--model NAME] [--img-size 224] [--batch 256] [--iters 10] [--rounds 3] [--once fused|library]
+    python scripts/time_swin.py --model swin_base_patch4_window12_384 --img-size 384
 
 ``--once`` runs a few forwards of one side only (for a kernel trace: rocprofv3 --kernel-trace --stats -- python ...)."""
 import argparse
@@ -41,15 +42,16 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--model", default="swin_tiny_patch4_window7_224")
+    ap.add_argument("--img-size", type=int, default=224)
     ap.add_argument("--once", choices=("fused", "library"), default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("time_swin.py needs the GPU: a CPU run says nothing about it")
     from basd_amd.models import load_teacher
-    teacher = load_teacher(args.model, 224, device="cuda")
+    teacher = load_teacher(args.model, args.img_size, device="cuda")
     model = teacher.model
     assert model._fused is not None, model.fused_refusal()
-    x = torch.randn(args.batch, 3, 224, 224, device="cuda").to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+    x = torch.randn(args.batch, 3, args.img_size, args.img_size, device="cuda").to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
 
     def fused():
         with torch.no_grad():
@@ -69,7 +71,7 @@ def main():
     rel = float((a - b).norm() / b.norm())
     del a, b
     for r in range(max(args.rounds, 3)):
-        out = {"model": args.model, "batch": args.batch, "iters": args.iters, "round": r, "fused_vs_library_rel_l2": rel}
+        out = {"model": args.model, "img_size": args.img_size, "batch": args.batch, "iters": args.iters, "round": r, "fused_vs_library_rel_l2": rel}
         for name in (("fused", "library") if r % 2 == 0 else ("library", "fused")):
             out[f"{name}_ms"] = median_ms(fused if name == "fused" else library, args.iters)
         out["library_over_fused"] = out["library_ms"]["median"] / out["fused_ms"]["median"]

@@ -43,6 +43,7 @@ EXPORTS = (
     "basd_window_attention_fwd_bf16", "basd_patch_merge_ln_bf16", "basd_gemm_bf16_act", "basd_vit_embed_bf16",
     "basd_attention_fwd_relbias_bf16", "basd_gemm_bf16_swiglu", "basd_vit_embed_reg_bf16",
     "basd_attention_fwd_rope_bf16", "basd_attention_fwd_long_rope_bf16", "basd_attention_fwd_long_relbias_bf16",
+    "basd_window_attention_fwd_wide_bf16",
 )
 
 
@@ -137,6 +138,7 @@ _SIGNATURES = {
     "basd_sym_tridiag_f64": (_P, _I, _P, _P, _P, _P),
     "basd_tridiag_mp_rank": (_P, _P, _I, _I64, _I, _I, _P, _P, _P),
     "basd_window_attention_fwd_bf16": (_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P),
+    "basd_window_attention_fwd_wide_bf16": (_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P),
     "basd_patch_merge_ln_bf16": (_P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P),
 }
 
@@ -1714,7 +1716,7 @@ def add_relu_(y: torch.Tensor, r: torch.Tensor, c: int | None = None) -> torch.T
     return y
 
 
-# --------------------------------------------------------------------------- Swin teacher trunk (csrc/swin.hip)
+# --------------------------------------------------------------------------- Swin teacher trunk (csrc/swin.hip, csrc/swin_wide.hip)
 WINDOW_SLOTS = 64          # slots of a window tile: ws <= 8; also the row / column count of a bias image
 
 
@@ -1754,6 +1756,39 @@ def window_attention(qkv: torch.Tensor, bias_img: torch.Tensor, ws: int, shift: 
     _check(lib().basd_window_attention_fwd_bf16(_ptr(qkv), _ptr(bias_img), b, h, w, heads, c, ws, shift, ld_qkv, ld_out,
                                                 ctypes.c_float(scale), _ptr(out), _stream()),
            "basd_window_attention_fwd_bf16")
+    return out
+
+
+WINDOW_WIDE_MIN, WINDOW_WIDE_MAX = 9, 16      # windows of basd_window_attention_fwd_wide_bf16 (csrc/swin_wide.hip)
+
+
+def window_attention_wide_supported(h: int, w: int, ws: int, shift: int, heads: int, c: int, ld_qkv: int,
+                                    ld_out: int) -> bool:
+    return (WINDOW_WIDE_MIN <= ws <= WINDOW_WIDE_MAX and 0 <= shift < ws and h >= ws and w >= ws and h % ws == 0
+            and w % ws == 0 and heads >= 1 and c == 32 * heads and ld_qkv % 8 == 0 and ld_out % 8 == 0
+            and ld_qkv >= 3 * c and ld_out >= c)
+
+
+def window_attention_wide(qkv: torch.Tensor, table: torch.Tensor, ws: int, shift: int, heads: int, scale: float,
+                          ld_out: int | None = None) -> torch.Tensor:
+    """``window_attention`` for windows 9 .. 16 (81 .. 256 slots; window 12 of the 384 px Swin checkpoints): the same
+    rows, roll / partition arithmetic, mask and rounding points.  ``table`` is timm's ``relative_position_bias_table``
+    itself, fp32 [(2 ws - 1)^2, heads]; the kernel computes the index per logit, no [N, N] image is built."""
+    _need_cuda(qkv, table)
+    assert qkv.dtype == torch.bfloat16 and qkv.dim() == 4 and qkv.is_contiguous()
+    assert table.dtype == torch.float32 and table.is_contiguous()
+    b, h, w, ld_qkv = qkv.shape
+    c = 32 * heads
+    ld_out = c if ld_out is None else ld_out
+    if not (window_attention_wide_supported(h, w, ws, shift, heads, c, ld_qkv, ld_out)
+            and table.shape == ((2 * ws - 1) ** 2, heads)):
+        raise BasdNativeError(f"window_attention_wide: grid {h}x{w} ws={ws} shift={shift} heads={heads} ld_qkv={ld_qkv} "
+                              f"ld_out={ld_out} table={tuple(table.shape)} is not tiled (9 <= ws <= 16, head dim 32, grid "
+                              "a multiple of ws, bias table [(2 ws - 1)^2, heads])")
+    out = torch.empty(b, h, w, ld_out, dtype=torch.bfloat16, device=qkv.device)
+    _check(lib().basd_window_attention_fwd_wide_bf16(_ptr(qkv), _ptr(table), b, h, w, heads, c, ws, shift, ld_qkv, ld_out,
+                                                     ctypes.c_float(scale), _ptr(out), _stream()),
+           "basd_window_attention_fwd_wide_bf16")
     return out
 
 

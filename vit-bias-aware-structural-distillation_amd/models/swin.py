@@ -28,7 +28,10 @@ Two forwards of the same parameters, under the protocol and with the image helpe
   and after ``probe_model``, whose hook needs the stage modules' forward): activations are rows ``[B H W, ld]`` (96
   channels in rows of 128, pad columns zero), every linear layer is ``basd_gemm_bf16`` (GELU in fc1's epilogue, the qkv
   width padded to one the GEMM tiles), window attention and patch merging + LayerNorm are ``csrc/swin.hip``, the other
-  LayerNorms the existing kernels.  It enqueues no library GEMM, no convolution and no SDPA.
+  LayerNorms the existing kernels.  It enqueues no library GEMM, no convolution and no SDPA.  Windows up to 8 take
+  ``basd_window_attention_fwd_bf16`` with the bias expanded to a [heads, 64, 64] image; windows 9 .. 16 (window 12 of
+  the 384 px checkpoints) take ``basd_window_attention_fwd_wide_bf16`` (``csrc/swin_wide.hip``) with the fp32 bias
+  table itself.  A window above 16 is refused.
 """
 from __future__ import annotations
 
@@ -41,6 +44,7 @@ from .fused_trunk import FusedTrunk, centre_tap_identity, norm_params, padded_im
 
 HEAD_DIM = 32
 MASK_VALUE = -100.0
+WINDOW_TILE = 8            # the largest window of basd_window_attention_fwd_bf16; 9 .. 16 is the wide entry's
 
 
 def relative_position_index(ws: int) -> torch.Tensor:
@@ -205,6 +209,11 @@ class SwinTransformer(FusedTrunk, nn.Module):
         for key in [k for k in state_dict if k.startswith(prefix) and
                     (k.endswith("attn_mask") or k.endswith("relative_position_index"))]:
             del state_dict[key]
+        rows = (2 * self.window_size - 1) ** 2
+        for key, table in state_dict.items():       # tables are not resampled: a checkpoint of another window is refused
+            if key.startswith(prefix) and key.endswith("relative_position_bias_table") and table.shape[0] != rows:
+                raise ValueError(f"Swin: {key} has {table.shape[0]} rows, window {self.window_size} needs "
+                                 f"(2 ws - 1)^2 = {rows}; bias tables of another window size are not resampled")
         if prefix + "layers.0.downsample.reduction.weight" in state_dict:
             head = prefix + "layers."
             moved = {}
@@ -224,6 +233,11 @@ class SwinTransformer(FusedTrunk, nn.Module):
         ops = get_ops()
         return next((n for n in range((3 * c + 127) // 128 * 128, 3 * c + 513, 128) if ops.gemm_supported(n, ld)), None)
 
+    def _wide_window(self) -> bool:
+        """which attention entry the blocks take: windows up to 8 fill the 64-slot tile of ``window_attention`` (bias as
+        a [heads, 64, 64] image), larger ones go to ``window_attention_wide`` (the fp32 bias table itself)"""
+        return self.window_size > WINDOW_TILE
+
     def fused_refusal(self) -> str | None:
         """Why the kernels do not take this architecture (None: they do)."""
         ops = get_ops()
@@ -231,13 +245,17 @@ class SwinTransformer(FusedTrunk, nn.Module):
             return "the kernel provider has no Swin trunk entries"
         if self.patch_embed.proj.weight.shape[1] != 3:
             return f"the patch embedding takes 3 input channels (got {self.patch_embed.proj.weight.shape[1]})"
-        ws = self.window_size
+        ws = self.window_size                     # the window every block uses on any grid (``_stage_window``)
+        wide = self._wide_window()
+        if wide and not hasattr(ops, "window_attention_wide"):
+            return f"stage 0: window {ws} needs the wide window attention entry, which the kernel provider does not have"
+        supported = ops.window_attention_wide_supported if wide else ops.window_attention_supported
         for i, (c, nh) in enumerate(zip(self.dims, self.heads)):
             ld = row_width(c)
             nq = self._qkv_width(c, ld)
             if c != HEAD_DIM * nh:
                 return f"stage {i}: width {c} with {nh} heads is not head dim {HEAD_DIM}"
-            if nq is None or not ops.window_attention_supported(ws, ws, ws, ws // 2, nh, c, nq, ld):
+            if nq is None or not supported(ws, ws, ws, ws // 2, nh, c, nq, ld):
                 return f"stage {i}: window {ws} / width {c} (rows of {ld}) is not tiled by the window attention kernel"
             if not (ops.gemm_supported(ld, ld) and ops.gemm_supported(4 * c, ld) and ops.gemm_supported(ld, 4 * c)
                     and (ops.layernorm_supported(c) if ld == c else ops.dwconv7_ln_supported(c, ld, ld))):
@@ -254,8 +272,11 @@ class SwinTransformer(FusedTrunk, nn.Module):
     def _build_fused(self):
         """The weight images of ``prepare_fused``: zero-padded GEMM images, the patch embedding in the patch order of
         ``basd_patchify_bf16`` (48 columns in rows of 64), fp32 norm parameters, and per block the relative-position
-        bias expanded from the table into the fp32 [heads, 64, 64] image of ``basd_window_attention_fwd_bf16``."""
+        bias: expanded from the table into the fp32 [heads, 64, 64] image of ``basd_window_attention_fwd_bf16`` for
+        windows up to 8, the fp32 table itself for ``basd_window_attention_fwd_wide_bf16`` (an expanded image of a
+        window-12 model would be [heads, 144, 144] per block)."""
         ops = get_ops()
+        wide = self._wide_window()
         proj = self.patch_embed.proj
         lds = [row_width(c) for c in self.dims]
 
@@ -276,7 +297,8 @@ class SwinTransformer(FusedTrunk, nn.Module):
             for blk in stage.blocks:
                 rec["blocks"].append({
                     "norm1": norm_params(blk.norm1), "qkv": linear(blk.attn.qkv, nq, ld),
-                    "bias": ops.window_bias_image(blk.attn.bias()), "scale": blk.attn.scale, "shift": blk.shift,
+                    "bias": (blk.attn.relative_position_bias_table.to(torch.float32).contiguous() if wide
+                             else ops.window_bias_image(blk.attn.bias())), "scale": blk.attn.scale, "shift": blk.shift,
                     "proj": linear(blk.attn.proj, ld, ld), "norm2": norm_params(blk.norm2),
                     "fc1": linear(blk.mlp.fc1, 4 * c, ld), "fc2": linear(blk.mlp.fc2, ld, 4 * c)})
             fused["stages"].append(rec)
@@ -301,8 +323,8 @@ class SwinTransformer(FusedTrunk, nn.Module):
                 win, shift = _stage_window(h, w, ws, blk["shift"])
                 y = self._norm_rows(ops, t, c, *blk["norm1"])
                 qkv = ops.gemm_bf16(y, *blk["qkv"])
-                a = ops.window_attention(qkv.view(b, h, w, qkv.shape[1]), blk["bias"], win, shift, nh, blk["scale"],
-                                         ld_out=ld)
+                attend = ops.window_attention_wide if win > WINDOW_TILE else ops.window_attention
+                a = attend(qkv.view(b, h, w, qkv.shape[1]), blk["bias"], win, shift, nh, blk["scale"], ld_out=ld)
                 p = ops.gemm_bf16(a.view(b * h * w, ld), *blk["proj"])
                 if ld == c:
                     t, y = ops.add_layernorm_fwd(p, t, *blk["norm2"])                    # t <- t + p, y = LayerNorm(t)
@@ -325,6 +347,15 @@ class SwinTransformer(FusedTrunk, nn.Module):
                 return False
         return True
 
+    def check_image_size(self, img_size: int) -> None:
+        """``load_teacher`` calls this before the first forward: a window that does not tile the token grids of the
+        image size (window 12 at 224 px: grids 56, 28, 14, 7) is an error that names both"""
+        grids = [img_size // (4 << i) for i in range(len(self.dims))]
+        if not self._grid_ok(img_size, img_size):
+            raise ValueError(f"Swin: image size {img_size} gives the token grids {grids}, which window "
+                             f"{self.window_size} does not tile (every grid is a multiple of the window, or one window); "
+                             f"window {self.window_size} takes image sizes that are multiples of {32 * self.window_size}")
+
     def _takes_fused(self, x) -> bool:
         return (self._fused is not None and not torch.is_grad_enabled() and x.dtype == torch.bfloat16 and x.dim() == 4
                 and x.shape[1] == 3 and self.patch_embed.proj.weight.dtype == torch.bfloat16
@@ -338,4 +369,11 @@ SWIN_PRESETS = {
     "swin_tiny_patch4_window7_224": lambda: SwinTransformer((2, 2, 6, 2), (96, 192, 384, 768), (3, 6, 12, 24)),
     "swin_small_patch4_window7_224": lambda: SwinTransformer((2, 2, 18, 2), (96, 192, 384, 768), (3, 6, 12, 24)),
     "swin_base_patch4_window7_224": lambda: SwinTransformer((2, 2, 18, 2), (128, 256, 512, 1024), (4, 8, 16, 32)),
+    # Swin-L and the window-12 checkpoints of 384 px: depths, widths and heads written from memory of timm's model
+    # table, without timm at hand (as the presets above; DESIGN sections 19 and 26)
+    "swin_large_patch4_window7_224": lambda: SwinTransformer((2, 2, 18, 2), (192, 384, 768, 1536), (6, 12, 24, 48)),
+    "swin_base_patch4_window12_384": lambda: SwinTransformer((2, 2, 18, 2), (128, 256, 512, 1024), (4, 8, 16, 32),
+                                                             window_size=12),
+    "swin_large_patch4_window12_384": lambda: SwinTransformer((2, 2, 18, 2), (192, 384, 768, 1536), (6, 12, 24, 48),
+                                                              window_size=12),
 }

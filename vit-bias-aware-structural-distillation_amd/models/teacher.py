@@ -177,6 +177,8 @@ def load_teacher(model_name: str, img_size: int, *, weights: str | None = None, 
         mean, std = vit_preset(model_name).mean, vit_preset(model_name).std
     elif model_name in CNN_PRESETS:
         model = create_cnn(model_name)
+        if hasattr(model, "check_image_size"):
+            model.check_image_size(img_size)         # Swin: a window that does not tile the grids of this image size
         mean, std = _IMAGENET_MEAN, _IMAGENET_STD
     elif model_name in BEIT_PRESETS:
         model = create_beit(model_name, img_size=img_size, patch_size=patch_size)
