@@ -37,10 +37,45 @@ def median_ms(fn, iters, warmup=5):
     return ts[len(ts) // 2]
 
 
+def ab_long(parent, iters, runs):
+    """the long forward entries at B = 256, this build against --parent (time_attention.ab_row)"""
+    from time_attention import P, ab_row
+    B, H, st = 256, 12, nat._stream()
+    for T, hd in ((257, 64), (577, 64), (257, 80)):
+        qkv = torch.randn(B, T, 3 * H * hd, device="cuda").bfloat16()
+        out = torch.empty(B, T, H * hd, dtype=torch.bfloat16, device="cuda")
+        imp, lse = torch.empty(B, H, T - 1, device="cuda"), torch.empty(B, H, T, device="cuda")
+        ab_row(f"long plain T {T} H {H} hd {hd} with LSE + CLS tap", lambda L: L.basd_attention_fwd_long_bf16(
+            P(qkv), B, T, H, hd, ctypes.c_float(hd ** -0.5), P(out), P(imp), P(None), P(lse), st), parent, iters, runs)
+    hd, scale = 64, ctypes.c_float(0.125)
+    gh = gw = 24
+    T = gh * gw + 1
+    qkv = torch.randn(B, T, 3 * H * hd, device="cuda").bfloat16()
+    out = torch.empty(B, T, H * hd, dtype=torch.bfloat16, device="cuda")
+    imp = torch.empty(B, H, T - 1, device="cuda")
+    table = torch.randn((2 * gh - 1) * (2 * gw - 1) + 3, H, device="cuda")
+    ab_row(f"long relbias T {T} H {H} with tap", lambda L: L.basd_attention_fwd_long_relbias_bf16(
+        P(qkv), P(table), B, gh, gw, H, hd, scale, P(out), P(imp), st), parent, iters, runs)
+    T = 581                                          # DINOv3 at 384 px: 24 x 24 patches + CLS + 4 registers
+    qkv = torch.randn(B, T, 3 * H * hd, device="cuda").bfloat16()
+    out = torch.empty(B, T, H * hd, dtype=torch.bfloat16, device="cuda")
+    imp = torch.empty(B, H, T - 1, device="cuda")
+    rope = nat.dinov3_rope_table(24, 24, hd).cuda()
+    ab_row(f"long rope T {T} H {H} with tap", lambda L: L.basd_attention_fwd_long_rope_bf16(
+        P(qkv), P(rope), B, T, H, hd, scale, P(out), P(imp), st), parent, iters, runs)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--parent", default=None, help="another build of libbasd_hip.so, loaded into the same process: its "
+                    "brackets of the long forward entries and this build's are alternated")
     args = ap.parse_args()
+    if args.parent:
+        from time_attention import load_parent
+        return ab_long(load_parent(args.parent, ("basd_attention_fwd_long_bf16", "basd_attention_fwd_long_relbias_bf16",
+                                                 "basd_attention_fwd_long_rope_bf16")), args.iters, args.runs)
     L = nat.lib()
     print(f"{'shape':<18} {'B':>4} {'T':>5} {'H':>3} {'hd':>3} | {'fwd ms':>8} {'TF/s':>6} {'sdpa ms':>8} {'TF/s':>6} | "
           f"{'bwd ms':>8} {'TF/s':>6} {'sdpa ms':>8} {'TF/s':>6}")

@@ -1174,6 +1174,24 @@ def relbias_index(i: int, j: int, gh: int, gw: int) -> int:
     return (yi - yj + gh - 1) * (2 * gw - 1) + (xi - xj + gw - 1)
 
 
+def _attention_fwd_table(entry: str, qkv, table, rows: tuple, align: int, dims: tuple, heads, head_dim, scale,
+                         want_importance):
+    """The body of the four entries that carry a position table (fp32, shape ``rows``, ``align``-byte aligned): checks,
+    allocation, the call -- ``dims`` are the entry's integers between B and heads, (gh, gw) or (T,) -- and the head sum
+    of the tap.  -> (out [B, T, heads * head_dim] bf16, importance [B, T-1] fp32 | None)"""
+    _need_cuda(qkv, table)
+    b, t = qkv.shape[0], qkv.shape[1]
+    assert qkv.dtype == torch.bfloat16 and qkv.shape[-1] == 3 * heads * head_dim
+    assert table.dtype == torch.float32 and tuple(table.shape) == rows, (tuple(table.shape), rows)
+    qkv, table = qkv.contiguous(), table.contiguous()
+    assert table.data_ptr() % align == 0
+    out = torch.empty(b, t, heads * head_dim, dtype=torch.bfloat16, device=qkv.device)
+    imp = torch.empty(b, heads, t - 1, dtype=torch.float32, device=qkv.device) if want_importance else None
+    _check(getattr(lib(), entry)(_ptr(qkv), _ptr(table), b, *dims, heads, head_dim, ctypes.c_float(scale), _ptr(out),
+                                 _ptr(imp), _stream()), entry)
+    return out, (imp.sum(dim=1) if want_importance else None)
+
+
 def attention_fwd_relbias_supported(gh: int, gw: int, hd: int) -> bool:
     """the range of ``basd_attention_fwd_relbias_bf16``: the short kernel's token count, head dim 64"""
     return hd == 64 and gh >= 1 and gw >= 1 and gh * gw + 1 <= 272
@@ -1185,17 +1203,9 @@ def attention_fwd_relbias(qkv: torch.Tensor, table: torch.Tensor, gh: int, gw: i
     (timm's ``relative_position_bias_table``) -> (out [B, T, heads * head_dim] bf16, importance | None) with
     softmax(q k^T * scale + table[relbias_index(i, j)]) per head; importance: the CLS row of the head-averaged biased
     map without its first entry, [B, T-1] fp32.  The bias is gathered inside the kernel: nothing [T, T] is built."""
-    _need_cuda(qkv, table)
-    b, t = qkv.shape[0], qkv.shape[1]
-    assert qkv.dtype == torch.bfloat16 and qkv.shape[-1] == 3 * heads * head_dim and t == gh * gw + 1
-    assert table.dtype == torch.float32 and tuple(table.shape) == ((2 * gh - 1) * (2 * gw - 1) + 3, heads)
-    qkv, table = qkv.contiguous(), table.contiguous()
-    out = torch.empty(b, t, heads * head_dim, dtype=torch.bfloat16, device=qkv.device)
-    imp = torch.empty(b, heads, t - 1, dtype=torch.float32, device=qkv.device) if want_importance else None
-    _check(lib().basd_attention_fwd_relbias_bf16(_ptr(qkv), _ptr(table), b, gh, gw, heads, head_dim,
-                                                 ctypes.c_float(scale), _ptr(out), _ptr(imp), _stream()),
-           "basd_attention_fwd_relbias_bf16")
-    return out, (imp.sum(dim=1) if want_importance else None)
+    assert qkv.shape[1] == gh * gw + 1
+    return _attention_fwd_table("basd_attention_fwd_relbias_bf16", qkv, table, ((2 * gh - 1) * (2 * gw - 1) + 3, heads), 4,
+                                (gh, gw), heads, head_dim, scale, want_importance)
 
 
 def attention_fwd_long_relbias_supported(gh: int, gw: int, hd: int) -> bool:
@@ -1208,17 +1218,9 @@ def attention_fwd_long_relbias(qkv: torch.Tensor, table: torch.Tensor, gh: int, 
     """``attention_fwd_relbias`` on the tiled kernels (csrc/attention_long.hip, RELBIAS), for the token counts the short
     entry refuses; arguments and results are the same.  The importance is the CLS tap of ``attention_fwd``'s long kernel
     (bf16-rounded logits) with the CLS row's bias added to the scaled logits."""
-    _need_cuda(qkv, table)
-    b, t = qkv.shape[0], qkv.shape[1]
-    assert qkv.dtype == torch.bfloat16 and qkv.shape[-1] == 3 * heads * head_dim and t == gh * gw + 1
-    assert table.dtype == torch.float32 and tuple(table.shape) == ((2 * gh - 1) * (2 * gw - 1) + 3, heads)
-    qkv, table = qkv.contiguous(), table.contiguous()
-    out = torch.empty(b, t, heads * head_dim, dtype=torch.bfloat16, device=qkv.device)
-    imp = torch.empty(b, heads, t - 1, dtype=torch.float32, device=qkv.device) if want_importance else None
-    _check(lib().basd_attention_fwd_long_relbias_bf16(_ptr(qkv), _ptr(table), b, gh, gw, heads, head_dim,
-                                                      ctypes.c_float(scale), _ptr(out), _ptr(imp), _stream()),
-           "basd_attention_fwd_long_relbias_bf16")
-    return out, (imp.sum(dim=1) if want_importance else None)
+    assert qkv.shape[1] == gh * gw + 1
+    return _attention_fwd_table("basd_attention_fwd_long_relbias_bf16", qkv, table, ((2 * gh - 1) * (2 * gw - 1) + 3, heads), 4,
+                                (gh, gw), heads, head_dim, scale, want_importance)
 
 
 def rope_table(gh: int, gw: int, head_dim: int, *, ref_grid=None, temperature: float = 10000.0,
@@ -1256,17 +1258,9 @@ def attention_fwd_rope(qkv: torch.Tensor, rope: torch.Tensor, heads: int, head_d
     ``rope_table``) -> (out [B, T, heads * head_dim] bf16, importance | None) with softmax(q' k'^T * scale) v per head,
     q' / k' the pairwise rotations of q / k (fp32 arithmetic, one rounding to bf16) done inside the kernel; importance:
     the CLS row of the head-averaged map of that softmax without its first entry, [B, T-1] fp32."""
-    _need_cuda(qkv, rope)
-    b, t = qkv.shape[0], qkv.shape[1]
-    assert qkv.dtype == torch.bfloat16 and qkv.shape[-1] == 3 * heads * head_dim
-    assert rope.dtype == torch.float32 and tuple(rope.shape) == (t, head_dim // 2, 2), (tuple(rope.shape), t, head_dim)
-    qkv, rope = qkv.contiguous(), rope.contiguous()
-    assert rope.data_ptr() % 16 == 0
-    out = torch.empty(b, t, heads * head_dim, dtype=torch.bfloat16, device=qkv.device)
-    imp = torch.empty(b, heads, t - 1, dtype=torch.float32, device=qkv.device) if want_importance else None
-    _check(lib().basd_attention_fwd_rope_bf16(_ptr(qkv), _ptr(rope), b, t, heads, head_dim, ctypes.c_float(scale),
-                                              _ptr(out), _ptr(imp), _stream()), "basd_attention_fwd_rope_bf16")
-    return out, (imp.sum(dim=1) if want_importance else None)
+    t = qkv.shape[1]
+    return _attention_fwd_table("basd_attention_fwd_rope_bf16", qkv, rope, (t, head_dim // 2, 2), 16, (t,), heads, head_dim,
+                                scale, want_importance)
 
 
 def attention_fwd_long_rope_supported(t: int, hd: int) -> bool:
@@ -1279,18 +1273,9 @@ def attention_fwd_long_rope(qkv: torch.Tensor, rope: torch.Tensor, heads: int, h
     """``attention_fwd_rope`` on the tiled kernels (csrc/attention_long.hip, ROPE), for the token counts the short entry
     refuses; arguments and results are the same.  The importance is the CLS tap of ``attention_fwd``'s long kernel
     (bf16-rounded logits) on the rotated operands."""
-    _need_cuda(qkv, rope)
-    b, t = qkv.shape[0], qkv.shape[1]
-    assert qkv.dtype == torch.bfloat16 and qkv.shape[-1] == 3 * heads * head_dim
-    assert rope.dtype == torch.float32 and tuple(rope.shape) == (t, head_dim // 2, 2), (tuple(rope.shape), t, head_dim)
-    qkv, rope = qkv.contiguous(), rope.contiguous()
-    assert rope.data_ptr() % 16 == 0
-    out = torch.empty(b, t, heads * head_dim, dtype=torch.bfloat16, device=qkv.device)
-    imp = torch.empty(b, heads, t - 1, dtype=torch.float32, device=qkv.device) if want_importance else None
-    _check(lib().basd_attention_fwd_long_rope_bf16(_ptr(qkv), _ptr(rope), b, t, heads, head_dim, ctypes.c_float(scale),
-                                                   _ptr(out), _ptr(imp), _stream()),
-           "basd_attention_fwd_long_rope_bf16")
-    return out, (imp.sum(dim=1) if want_importance else None)
+    t = qkv.shape[1]
+    return _attention_fwd_table("basd_attention_fwd_long_rope_bf16", qkv, rope, (t, head_dim // 2, 2), 16, (t,), heads, head_dim,
+                                scale, want_importance)
 
 
 def dinov3_rope_table(gh: int, gw: int, head_dim: int, base: float = 100.0, prefix_tokens: int = 5) -> torch.Tensor:

@@ -19,53 +19,32 @@
 //                 transposing LDS read ds_read_b64_tr_b16 on the same eight keys -- no transpose of P or V;
 //   the 16 x 64 output tile is staged through LDS so that every lane stores 16 contiguous bytes.
 // Arithmetic: fp32 logits and probabilities like a flash kernel (P rounded to bf16 for the second MFMA).
-#include "basd_frag.h"
+//
+// Variants (template parameters; the position schemes, their argument and the legal combinations: attn_pos.h):
+//   QMEAN            the tap of a teacher WITHOUT a CLS token (reference src/losses/relational.py:25-27: the attention
+//                    map averaged over heads AND queries): importance[b, h, key] = sum_q P[q][key] / (H T) from the
+//                    probabilities of the main softmax (fp32 logits), [B, H, T]; the caller sums over h as for the CLS tap.
+//   AttnPos::RelBias basd_attention_fwd_relbias_bf16: the raw column of the table is staged behind the tiles and
+//                    s = fmaf(s, scale, bias) is formed per logit, so the softmax below it runs on scaled logits.
+//   AttnPos::Rope    basd_attention_fwd_rope_bf16: a K chunk is rotated between its global load and its LDS store, a Q
+//                    fragment when it is taken out of the prefetch registers.
+//   With a position scheme the tap is row 0 of the main softmax (fp32 logits), not the bf16-rounded side computation
+//   of the plain kernel, and there is no LSE.
+#include "attn_pos.h"
 
 namespace basd {
-
-__device__ __forceinline__ unsigned short f32_to_bf16_rne(float f) {
-  unsigned int u = __float_as_uint(f);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
 
 template <int CTRL> __device__ __forceinline__ float at_dpp_add(float v) {
   return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
 }
 
-// QMEAN: the tap of a teacher WITHOUT a CLS token (reference src/losses/relational.py:25-27: the attention map averaged
-// over heads AND queries): importance[b, h, key] = sum_q P[q][key] / (H T) from the probabilities of the main softmax
-// (fp32 logits, as the torch form of this tap used before), [B, H, T]; the caller sums over h as for the CLS tap.
-//
-// RELBIAS: BEiT's learned relative-position bias (basd_attention_fwd_relbias_bf16): the logit of query i and key j is
-// fp32(q_i . k_j) * scale + table[idx(i, j)][h].  No [T, T] bias exists anywhere: the head's column of the table
-// (R = (2 gh - 1)(2 gw - 1) + 3 floats) is staged in LDS next to koff[key] = y_k (2 gw - 1) + x_k of every patch key, and
-// a lane forms idx = (y_q + gh - 1)(2 gw - 1) + x_q + gw - 1 - koff[key] per logit (one division per lane and query
-// tile); a CLS query reads row R - 3 (R - 1 against the CLS key), a patch query row R - 2 against the CLS key.  The tap is
-// row 0 of the main softmax (fp32 logits, bias included), not the bf16-rounded side computation of the plain kernel.
-//
-// ROPE: EVA-02's rotary position embedding (basd_attention_fwd_rope_bf16): q and k of token t are rotated pairwise,
-// (x[2i], x[2i+1]) -> (x[2i] c - x[2i+1] s, x[2i+1] c + x[2i] s) with (c, s) = rope[t][i], before the logits are formed;
-// v is untouched.  A 16-byte chunk holds four whole pairs, so a K chunk is rotated in registers between its global load
-// and its LDS store, and a Q fragment between its (prefetched) global load and the MFMA: fp32 arithmetic on the bf16
-// inputs, one rounding back to bf16.  The eight table floats of a chunk are loaded next to it (two 16-byte loads issued
-// with the K / V / Q loads).  The kernel knows no grid: row t of the table belongs to token t (the host writes (1, 0)
-// into the rows of tokens that are not rotated).  The table pointer travels in RelBias::table (gh = gw = 0): the
-// kernel's argument list stays the one of the other instantiations.  The tap is row 0 of the main softmax as for RELBIAS.
-struct RelBias {
-  const float* table;                                // [R, H] fp32, heads on the fast axis (ROPE: [T, hd / 2, 2] fp32)
-  int gh, gw;                                        // patch grid: T = gh * gw + 1, CLS token first
-};
-
-// rope_pair / rope_chunk (basd_frag.h) rotate one word / one 16-byte chunk
-
-template <int NKT, int AT_HD, bool QMEAN = false, bool RELBIAS = false, bool ROPE = false>   // key tiles of 16: T <= 16 * NKT; head dim 64 or 80
+template <int NKT, int AT_HD, AttnPos POS = AttnPos::None, bool QMEAN = false>   // key tiles of 16: T <= 16 * NKT; head dim 64 or 80
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void attention_fwd_kernel(const unsigned short* __restrict__ qkv, int T, int H,
                                                             float scale, unsigned short* __restrict__ out,
                                                             float* __restrict__ importance, float* __restrict__ lse,
-                                                            RelBias rb) {
-  static_assert(!(QMEAN && RELBIAS), "the relative-position bias comes with the CLS tap only");
-  static_assert(!ROPE || (!QMEAN && !RELBIAS && AT_HD == 64), "the rotary embedding: CLS tap, no bias, whole 32-deep steps");
+                                                            AttnPosArg pos) {
+  static_assert(attn_pos_ok<POS, AT_HD, QMEAN>, "a position scheme: head dim 64, the CLS tap only");
+  constexpr bool RELBIAS = POS == AttnPos::RelBias, ROPE = POS == AttnPos::Rope;
   constexpr int NKS = (NKT + 1) / 2;                 // 32-key steps of the P V product
   constexpr int KROWS = 32 * NKS;                    // LDS rows (zero padded)
   constexpr int NDS = (AT_HD + 31) / 32;             // 32-deep steps of the Q K^T contraction
@@ -97,32 +76,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int r = idx / NCHP, c8 = idx - r * NCHP;
     kreg[i] = make_uint4(0, 0, 0, 0);
     vreg[i] = make_uint4(0, 0, 0, 0);
-    if constexpr (ROPE) kcs[i][0] = kcs[i][1] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (ROPE) rope_none(kcs[i]);
     if (r < T && c8 < NCH) {
       const unsigned short* p = base + (size_t)r * row + c8 * 8;
       kreg[i] = *reinterpret_cast<const uint4*>(p + (size_t)H * AT_HD);
       vreg[i] = *reinterpret_cast<const uint4*>(p + (size_t)2 * H * AT_HD);
-      if constexpr (ROPE) {
-        const float4* cs = reinterpret_cast<const float4*>(rb.table + (size_t)r * AT_HD + c8 * 8);
-        kcs[i][0] = cs[0];
-        kcs[i][1] = cs[1];
-      }
+      if constexpr (ROPE) rope_rows(pos.table, r, AT_HD, c8 * 8, kcs[i]);
     }
   }
-  const int R = RELBIAS ? (2 * rb.gh - 1) * (2 * rb.gw - 1) + 3 : 0;
-  const int rl = RELBIAS ? 2 * rb.gw - 1 : 0;        // table rows per step in y
-  if constexpr (RELBIAS) {
+  if constexpr (RELBIAS) {                           // the raw column and the key offsets (rule: relbias_koff)
+    const int R = relbias_rows(pos);
     constexpr int NTAB = (1084 + 255) / 256;         // R <= 1084 for gh * gw <= 271
     float tv[NTAB];
 #pragma unroll
-    for (int i = 0; i < NTAB; ++i) tv[i] = (tid + 256 * i < R) ? rb.table[(size_t)(tid + 256 * i) * H + h] : 0.f;
+    for (int i = 0; i < NTAB; ++i) tv[i] = (tid + 256 * i < R) ? pos.table[(size_t)(tid + 256 * i) * H + h] : 0.f;
 #pragma unroll
     for (int i = 0; i < NTAB; ++i)
       if (tid + 256 * i < R) tab[tid + 256 * i] = tv[i];
-    for (int key = tid; key < KROWS; key += 256) {   // CLS and padding keys: 0 (never used / masked)
-      const int yk = (key >= 1 && key < T) ? (key - 1) / rb.gw : 0;
-      koff[key] = (key >= 1 && key < T) ? yk * rl + (key - 1 - yk * rb.gw) : 0;
-    }
+    for (int key = tid; key < KROWS; key += 256) koff[key] = relbias_koff(pos, key, T);
   }
 #pragma unroll
   for (int i = 0; i < NLD; ++i) {
@@ -143,24 +114,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   unsigned short* Ow = Os + wave * 16 * AT_LD;
   // ROPE: the fragment's table rows are fetched with it; the rotation itself waits until the fragment is taken out of
   // the prefetch registers (below), so the loads stay in flight over a whole query tile as they do without it
-  auto load_q = [&](int qt_, uint4 (&dst)[NDS], float4 (&cs)[ROPE ? NDS : 1][2]) {
+  uint4 qnext[NDS];
+  float4 qcs[ROPE ? NDS : 1][2];
+  // Q fragments of tile qt_: query 16 qt_ + li, d = 32 ks + 8 g .. + 7, zero past T and past hd.  Written out here and
+  // in attention_long.hip: through one helper of attn_pos.h the guards of this prefetch are merged and its address
+  // arithmetic hoisted: the plain kernel at T = 197, H = 12 is then 3.5 % slower (profiles/attention_pos_one_copy_ab.txt).
+  auto load_q = [&](int qt_) {
 #pragma unroll
     for (int ks = 0; ks < NDS; ++ks) {
-      dst[ks] = make_uint4(0, 0, 0, 0);
-      if constexpr (ROPE) cs[ks][0] = cs[ks][1] = make_float4(0.f, 0.f, 0.f, 0.f);
+      qnext[ks] = make_uint4(0, 0, 0, 0);
+      if constexpr (ROPE) rope_none(qcs[ks]);
       if (qt_ < nqt && qt_ * 16 + li < T && 32 * ks + 8 * g < AT_HD) {
-        dst[ks] = *reinterpret_cast<const uint4*>(base + (size_t)(qt_ * 16 + li) * row + 32 * ks + 8 * g);
-        if constexpr (ROPE) {
-          const float4* p = reinterpret_cast<const float4*>(rb.table + (size_t)(qt_ * 16 + li) * AT_HD + 32 * ks + 8 * g);
-          cs[ks][0] = p[0];
-          cs[ks][1] = p[1];
-        }
+        qnext[ks] = *reinterpret_cast<const uint4*>(base + (size_t)(qt_ * 16 + li) * row + 32 * ks + 8 * g);
+        if constexpr (ROPE) rope_rows(pos.table, qt_ * 16 + li, AT_HD, 32 * ks + 8 * g, qcs[ks]);
       }
     }
   };
-  uint4 qnext[NDS];
-  float4 qcs[ROPE ? NDS : 1][2];
-  load_q(wave, qnext, qcs);
+  load_q(wave);
   float csum[QMEAN ? NKT : 1][4];                    // QMEAN: this lane's query column summed over the wave's tiles
 #pragma unroll
   for (int kt = 0; kt < (QMEAN ? NKT : 1); ++kt)
@@ -175,7 +145,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       if constexpr (ROPE) qnext[ks] = rope_chunk(qnext[ks], qcs[ks][0], qcs[ks][1]);
       qf[ks] = *reinterpret_cast<bf16x8*>(&qnext[ks]);
     }
-    load_q(qt + 4, qnext, qcs);
+    load_q(qt + 4);
     // ---- S^T tiles
     f32x4 s[NKT];
 #pragma unroll
@@ -191,19 +161,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     if constexpr (RELBIAS) {
       // ---- s = s * scale + table[idx(query, key)]: query q0 + li, keys 16 kt + 4 g + r
-      const int qi = q0 + li;
-      const bool qcls = qi == 0 || qi >= T;          // padding queries read the CLS rows: any valid index will do
-      const int yq = qcls ? 0 : (qi - 1) / rb.gw;
-      const int qb = qcls ? R - 3 : (yq + rb.gh - 1) * rl + (qi - 1 - yq * rb.gw) + rb.gw - 1;
-      const int c0 = qcls ? R - 1 : R - 2;           // against the CLS key
+      const RelBiasQuery rq = relbias_query(pos, q0 + li, T);
 #pragma unroll
       for (int kt = 0; kt < NKT; ++kt) {
+        // relbias_gather of attn_pos.h written out: through the helper (and through a helper for the index alone) the
+        // 17-tile instantiation keeps 35 fewer VGPRs of gathers in flight and T = 257 is 1.6 % slower
+        // (profiles/attention_pos_one_copy_ab.txt)
         const int4 ko = *reinterpret_cast<const int4*>(koff + 16 * kt + 4 * g);
         const int kk[4] = {ko.x, ko.y, ko.z, ko.w};
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          int idx = qcls ? qb : qb - kk[r];
-          if (kt == 0 && r == 0 && g == 0) idx = c0;
+          int idx = rq.patch ? rq.qb - kk[r] : rq.qb;
+          if (kt == 0 && r == 0 && g == 0) idx = rq.c0;
           s[kt][r] = fmaf(s[kt][r], scale, tab[idx]);
         }
       }
@@ -319,7 +288,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa, vb, o[dt], 0, 0, 0);
       }
     }
-    // ---- o[dt][r] = O[query q0 + 4 g + r][d = 16 dt + li]: through LDS, then 16-byte row stores
+    // ---- o[dt][r] = O[query q0 + 4 g + r][d = 16 dt + li]: through LDS, then 16-byte row stores.  Written out here and
+    //      in attention_long.hip: through one helper of attn_pos.h the tile's address arithmetic is hoisted in another
+    //      order and the rotary kernel at T = 197 left the timing band (profiles/attention_pos_one_copy_ab.txt)
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
@@ -366,18 +337,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
 }
 
-template <int NKT, int HD, bool QMEAN = false, bool RELBIAS = false, bool ROPE = false>
+template <int NKT, int HD, AttnPos POS, bool QMEAN>
 static void launch_attention(const void* qkv, int B, int T, int H, float scale, void* out, float* importance,
-                             float* lse, hipStream_t st, RelBias rb = RelBias{nullptr, 0, 0}) {
+                             float* lse, hipStream_t st, AttnPosArg pos) {
   constexpr int KROWS = 32 * ((NKT + 1) / 2);
   constexpr int LD = (HD + 31) / 32 * 32 + 8;
   size_t lds = ((size_t)2 * KROWS * LD + 4 * 16 * LD) * sizeof(unsigned short);
   static_assert(8 * LD >= KROWS, "the output staging tile of a wave holds its query-mean column sums");
   static_assert((2 * KROWS * LD + 4 * 16 * LD) % 8 == 0, "the key offsets behind the tiles are read 16 bytes at a time");
-  if (RELBIAS) lds += ((size_t)KROWS + (size_t)(2 * rb.gh - 1) * (2 * rb.gw - 1) + 3) * sizeof(float);
-  allow_full_lds((const void*)attention_fwd_kernel<NKT, HD, QMEAN, RELBIAS, ROPE>);
-  hipLaunchKernelGGL((attention_fwd_kernel<NKT, HD, QMEAN, RELBIAS, ROPE>), dim3(B * H), dim3(256), lds, st,
-                     (const unsigned short*)qkv, T, H, scale, (unsigned short*)out, importance, lse, rb);
+  if (POS == AttnPos::RelBias) lds += ((size_t)KROWS + (size_t)(2 * pos.gh - 1) * (2 * pos.gw - 1) + 3) * sizeof(float);
+  allow_full_lds((const void*)attention_fwd_kernel<NKT, HD, POS, QMEAN>);
+  hipLaunchKernelGGL((attention_fwd_kernel<NKT, HD, POS, QMEAN>), dim3(B * H), dim3(256), lds, st,
+                     (const unsigned short*)qkv, T, H, scale, (unsigned short*)out, importance, lse, pos);
+}
+
+// the key-tile count of a token count: 4 (T <= 64; head dim 64 only), 13 (T <= 208) or 17 tiles of 16 keys
+template <AttnPos POS = AttnPos::None, bool QMEAN = false>
+static void dispatch_attention(const void* qkv, int B, int T, int H, int hd, float scale, void* out, float* importance,
+                               float* lse, void* stream, AttnPosArg pos = AttnPosArg{nullptr, 0, 0}) {
+  hipStream_t st = (hipStream_t)stream;
+  if (hd == 64) {
+    if (T <= 64) launch_attention<4, 64, POS, QMEAN>(qkv, B, T, H, scale, out, importance, lse, st, pos);
+    else if (T <= 208) launch_attention<13, 64, POS, QMEAN>(qkv, B, T, H, scale, out, importance, lse, st, pos);
+    else launch_attention<17, 64, POS, QMEAN>(qkv, B, T, H, scale, out, importance, lse, st, pos);
+  } else if constexpr (POS == AttnPos::None) {
+    if (T <= 208) launch_attention<13, 80, POS, QMEAN>(qkv, B, T, H, scale, out, importance, lse, st, pos);
+    else launch_attention<17, 80, POS, QMEAN>(qkv, B, T, H, scale, out, importance, lse, st, pos);
+  }
 }
 
 }  // namespace basd
@@ -389,15 +375,7 @@ extern "C" int basd_attention_fwd_bf16(const void* qkv, int B, int T, int H, int
   if ((hd != 64 && hd != 80) || T < 1 || T > 272 || H < 1)
     return fail(BASD_ERR_SHAPE, "attention_fwd: T=%d H=%d hd=%d unsupported (hd 64 | 80, T <= 272)", T, H, hd);
   if (importance != nullptr && T < 2) return fail(BASD_ERR_SHAPE, "attention_fwd: importance needs T >= 2");
-  hipStream_t st = (hipStream_t)stream;
-  if (hd == 64) {
-    if (T <= 64) launch_attention<4, 64>(qkv, B, T, H, scale, out, importance, lse, st);
-    else if (T <= 208) launch_attention<13, 64>(qkv, B, T, H, scale, out, importance, lse, st);
-    else launch_attention<17, 64>(qkv, B, T, H, scale, out, importance, lse, st);
-  } else {
-    if (T <= 208) launch_attention<13, 80>(qkv, B, T, H, scale, out, importance, lse, st);
-    else launch_attention<17, 80>(qkv, B, T, H, scale, out, importance, lse, st);
-  }
+  dispatch_attention(qkv, B, T, H, hd, scale, out, importance, lse, stream);
   return check_launch("attention_fwd");
 }
 
@@ -408,15 +386,7 @@ extern "C" int basd_attention_fwd_qmean_bf16(const void* qkv, int B, int T, int 
   if ((hd != 64 && hd != 80) || T < 1 || T > 272 || H < 1)
     return fail(BASD_ERR_SHAPE, "attention_fwd_qmean: T=%d H=%d hd=%d unsupported (hd 64 | 80, T <= 272)", T, H, hd);
   if (importance == nullptr) return fail(BASD_ERR_SHAPE, "attention_fwd_qmean: importance is required");
-  hipStream_t st = (hipStream_t)stream;
-  if (hd == 64) {
-    if (T <= 64) launch_attention<4, 64, true>(qkv, B, T, H, scale, out, importance, nullptr, st);
-    else if (T <= 208) launch_attention<13, 64, true>(qkv, B, T, H, scale, out, importance, nullptr, st);
-    else launch_attention<17, 64, true>(qkv, B, T, H, scale, out, importance, nullptr, st);
-  } else {
-    if (T <= 208) launch_attention<13, 80, true>(qkv, B, T, H, scale, out, importance, nullptr, st);
-    else launch_attention<17, 80, true>(qkv, B, T, H, scale, out, importance, nullptr, st);
-  }
+  dispatch_attention<AttnPos::None, true>(qkv, B, T, H, hd, scale, out, importance, nullptr, stream);
   return check_launch("attention_fwd_qmean");
 }
 
@@ -427,12 +397,8 @@ extern "C" int basd_attention_fwd_relbias_bf16(const void* qkv, const float* tab
     return fail(BASD_ERR_SHAPE, "attention_fwd_relbias: grid %d x %d H=%d hd=%d unsupported (hd 64, 2 <= gh * gw + 1 <= 272)",
                 gh, gw, H, hd);
   if (B <= 0) return BASD_OK;
-  const int T = gh * gw + 1;
-  const RelBias rb{table, gh, gw};
-  hipStream_t st = (hipStream_t)stream;
-  if (T <= 64) launch_attention<4, 64, false, true>(qkv, B, T, H, scale, out, importance, nullptr, st, rb);
-  else if (T <= 208) launch_attention<13, 64, false, true>(qkv, B, T, H, scale, out, importance, nullptr, st, rb);
-  else launch_attention<17, 64, false, true>(qkv, B, T, H, scale, out, importance, nullptr, st, rb);
+  dispatch_attention<AttnPos::RelBias>(qkv, B, gh * gw + 1, H, hd, scale, out, importance, nullptr, stream,
+                                       AttnPosArg{table, gh, gw});
   return check_launch("attention_fwd_relbias");
 }
 
@@ -442,10 +408,6 @@ extern "C" int basd_attention_fwd_rope_bf16(const void* qkv, const float* rope, 
   if (hd != 64 || T < 2 || T > 272 || H < 1 || B < 1 || rope == nullptr)
     return fail(BASD_ERR_SHAPE, "attention_fwd_rope: B=%d T=%d H=%d hd=%d rope=%s unsupported (hd 64, 2 <= T <= 272, B, H >= 1, "
                                 "a table)", B, T, H, hd, rope == nullptr ? "NULL" : "given");
-  const RelBias rb{rope, 0, 0};                      // the table pointer in the bias slot of the kernel's arguments
-  hipStream_t st = (hipStream_t)stream;
-  if (T <= 64) launch_attention<4, 64, false, false, true>(qkv, B, T, H, scale, out, importance, nullptr, st, rb);
-  else if (T <= 208) launch_attention<13, 64, false, false, true>(qkv, B, T, H, scale, out, importance, nullptr, st, rb);
-  else launch_attention<17, 64, false, false, true>(qkv, B, T, H, scale, out, importance, nullptr, st, rb);
+  dispatch_attention<AttnPos::Rope>(qkv, B, T, H, hd, scale, out, importance, nullptr, stream, AttnPosArg{rope, 0, 0});
   return check_launch("attention_fwd_rope");
 }

@@ -19,20 +19,18 @@
 //   query mean   attn_long_qmean_kernel: one wave per 16-key tile walks every query tile, recomputes P from the LSE of
 //                the main pass and sums it down the column in a fixed order -- no partials, no atomics, bitwise
 //                reproducible.
-// ROPE (basd_attention_fwd_long_rope_bf16; frozen teachers with a rotary embedding past the 272 tokens of attention.hip):
-//   q and k of token t are rotated pairwise by the (cos, sin) rows of an fp32 table [T, hd / 2, 2] (rope_chunk,
-//   basd_frag.h: fp32 arithmetic, one rounding to bf16) before the logits are formed; v is untouched.  A K chunk is
-//   rotated in registers between its global load and its LDS store -- its eight table floats travel with it through the
-//   prefetch registers -- and the Q fragments once in front of the key loop.  The CLS tap rotates q_0 and every k row
-//   the same way before its dot: it is the tap above on the rotated, bf16-rounded operands.  No LSE, no query mean.
-// RELBIAS (basd_attention_fwd_long_relbias_bf16; frozen BEiT / BEiT-v2 teachers past the 272 tokens of attention.hip):
-//   the logit of query i and key j is fp32(q_i . k_j) * scale + table[idx(i, j)][h], the index rule of attention.hip.
-//   Every workgroup stages the head's column of the table, divided by scale, in LDS (R <= 4095 floats for T <= 1024)
-//   next to koff[key] = y_k (2 gw - 1) + x_k of every patch key; a lane -- one query column for the whole loop -- adds
-//   tab[qb - koff[key]] to the raw accumulator of each of its keys in front of the tile's maximum, so the online softmax
-//   below it is the plain kernel's to the instruction (an all-zero table gives the plain kernel's bits) and a masked
-//   tail key stays masked.  The CLS row's bias is two constants per head: the tap adds them to its scaled, bf16-rounded
-//   logits.  Nothing [T, T] is read or written.  No LSE, no query mean.
+// Position schemes (frozen teachers past the 272 tokens of attention.hip; the schemes, their argument and the legal
+// combinations: attn_pos.h).  The forward and the CLS tap take the AttnPosArg behind their plain argument list, which
+// the plain instantiations do not read.  No LSE, no query mean.
+//   AttnPos::Rope    basd_attention_fwd_long_rope_bf16: a K chunk is rotated between its global load and its LDS store --
+//                    its table rows travel with it through the prefetch registers -- and the Q fragments once in front
+//                    of the key loop.  The CLS tap rotates q_0 and every k row the same way before its dot: it is the
+//                    tap above on the rotated, bf16-rounded operands.
+//   AttnPos::RelBias basd_attention_fwd_long_relbias_bf16: the head's column of the table is staged DIVIDED BY scale
+//                    (R <= 4095 floats for T <= 1024) and added to the raw accumulator in front of the tile's maximum,
+//                    so the online softmax below it is the plain kernel's to the instruction (an all-zero table gives
+//                    the plain kernel's bits) and a masked tail key stays masked.  The CLS row's bias is two constants
+//                    per head: the tap adds them to its scaled, bf16-rounded logits.
 //
 // Backward (FA2): attn_long_delta_kernel computes delta = rowsum(dO * O); attn_long_bwd_kernel runs one workgroup per
 // (image, head, 128-key block), wave w owning 32 keys whose K / V fragments and dK^T / dV^T accumulators stay in
@@ -40,43 +38,21 @@
 // dQ: the four waves' 32 x hd contributions meet in LDS and are added in wave order; the block's sum goes to a
 // per-key-block fp32 partial in the workspace (vector stores), and attn_long_dq_kernel adds the partials in key-block
 // order and writes the bf16 dQ slice of dqkv.  No atomics: the gradient is bitwise reproducible.
-#include <type_traits>
-
-#include "basd_frag.h"
+#include "attn_pos.h"
 
 namespace basd {
 
 constexpr int AL_MAXT = 1024;
 constexpr float AL_LOG2E = 1.4426950408889634f;
-
-// The ROPE instantiations take the table where the plain ones take the LSE pointer (forward) or next to the importance
-// pointer (tap): the argument lists, and with them the device code, of the plain instantiations stay what they were.
-struct AlRopeTap {
-  float* importance;
-  const float* rope;                                 // [T, HD / 2, 2] fp32 (cos, sin)
-};
-
-// The RELBIAS instantiations take these in the same two slots.
-struct AlRelBias {
-  const float* table;                                // [R, H] fp32, heads on the fast axis
-  int gh, gw;                                        // patch grid: T = gh * gw + 1, CLS token first
-};
-struct AlRelTap {
-  float* importance;
-  const float* table;
-  int R;                                             // (2 gh - 1)(2 gw - 1) + 3
-};
 constexpr int AL_MAXR = 4096;                        // R <= 4 gh gw + 3 <= 4095 for T <= AL_MAXT
 
 // ------------------------------------------------------------------------------------------------------ forward ----
-template <int HD, bool ROPE = false, bool RELBIAS = false>
+template <int HD, AttnPos POS = AttnPos::None>
 __global__ __launch_bounds__(256) void attn_long_fwd_kernel(
     const unsigned short* __restrict__ qkv, int T, int H, float scale, unsigned short* __restrict__ out,
-    typename std::conditional<RELBIAS, AlRelBias,
-                              typename std::conditional<ROPE, const float* __restrict__, float* __restrict__>::type>::type
-        lse_or_rope) {
-  static_assert(!ROPE || HD == 64, "the rotary embedding: head dim 64 (whole 32-deep steps)");
-  static_assert(!RELBIAS || (!ROPE && HD == 64), "the relative-position bias: head dim 64, no rotary embedding");
+    float* __restrict__ lse, AttnPosArg pos) {
+  static_assert(attn_pos_ok<POS, HD>, "a position scheme: head dim 64");
+  constexpr bool RELBIAS = POS == AttnPos::RelBias, ROPE = POS == AttnPos::Rope;
   constexpr int KB = 64;                             // keys per LDS tile
   constexpr int NDS = (HD + 31) / 32;                // 32-deep steps of the Q K^T contraction
   constexpr int NDT = HD / 16;                       // 16-column tiles of the output
@@ -94,8 +70,6 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(
   const size_t row = (size_t)3 * H * HD;
   const unsigned short* base = qkv + (size_t)b * T * row + (size_t)h * HD;
 
-  float* lse = nullptr;
-  const float* rope = nullptr;
   float* tab = nullptr;                              // RELBIAS: the head's column of the table / scale, [R]
   int* koff = nullptr;                               // RELBIAS: y_k (2 gw - 1) + x_k of patch key k, [AL_MAXT]
   if constexpr (RELBIAS) {
@@ -103,10 +77,6 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(
     __shared__ __align__(16) int koff_s[AL_MAXT];
     tab = tab_s;
     koff = koff_s;
-  } else if constexpr (ROPE) {
-    rope = lse_or_rope;
-  } else {
-    lse = lse_or_rope;
   }
 
   uint4 kreg[NLD], vreg[NLD];
@@ -118,21 +88,18 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(
       const int r = idx / NCHP, c8 = idx - r * NCHP;
       kreg[i] = make_uint4(0, 0, 0, 0);
       vreg[i] = make_uint4(0, 0, 0, 0);
-      if constexpr (ROPE) kcs[i][0] = kcs[i][1] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (ROPE) rope_none(kcs[i]);
       if (idx < KB * NCHP && k0 + r < T && c8 < NCH) {
         const unsigned short* p = base + (size_t)(k0 + r) * row + c8 * 8;
         kreg[i] = *reinterpret_cast<const uint4*>(p + (size_t)H * HD);
         vreg[i] = *reinterpret_cast<const uint4*>(p + (size_t)2 * H * HD);
-        if constexpr (ROPE) {                        // the table row of the GLOBAL key index, inside the same guard
-          const float4* cs = reinterpret_cast<const float4*>(rope + (size_t)(k0 + r) * HD + c8 * 8);
-          kcs[i][0] = cs[0];
-          kcs[i][1] = cs[1];
-        }
+        if constexpr (ROPE) rope_rows(pos.table, k0 + r, HD, c8 * 8, kcs[i]);    // the row of the GLOBAL key index
       }
     }
   };
   load_kv(0);
-  // Q fragments of this wave's tile: query q0 + li, d = 32 ks + 8 g .. + 7 (zero beyond T and beyond hd)
+  // Q fragments of this wave's tile: query q0 + li, d = 32 ks + 8 g .. + 7 (zero beyond T and beyond hd; written out
+  // in both files, see attention.hip)
   bf16x8 qf[NDS];
 #pragma unroll
   for (int ks = 0; ks < NDS; ++ks) {
@@ -141,26 +108,24 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(
       v = *reinterpret_cast<const uint4*>(base + (size_t)(q0 + li) * row + 32 * ks + 8 * g);
     if constexpr (ROPE) {                            // rotated once: the fragments stay in registers for the whole loop
       if (q0 + li < T) {
-        const float4* cs = reinterpret_cast<const float4*>(rope + (size_t)(q0 + li) * HD + 32 * ks + 8 * g);
+        float4 cs[2];
+        rope_rows(pos.table, q0 + li, HD, 32 * ks + 8 * g, cs);
         v = rope_chunk(v, cs[0], cs[1]);
       }
     }
     qf[ks] = *reinterpret_cast<const bf16x8*>(&v);
   }
-  // RELBIAS: this lane's query q0 + li reads tab[qb - koff[k]] against patch key k; a CLS (or padding) query reads the
-  // constant row R - 3; against the CLS key it is row c0.  The first barrier of the key loop publishes tab and koff.
-  int qb = 0, c0 = 0;
-  bool qpatch = false;
+  // RELBIAS: the column divided by scale and the key offsets (rule: relbias_koff); the first barrier of the key loop
+  // publishes tab and koff
+  RelBiasQuery rq = {0, 0, false};
   if constexpr (RELBIAS) {
-    const int gh = lse_or_rope.gh, gw = lse_or_rope.gw;
-    const int rl = 2 * gw - 1;                       // table rows per step in y
-    const int R = (2 * gh - 1) * rl + 3;
+    const int R = relbias_rows(pos);
     for (int i0 = 0; i0 < R; i0 += 1024) {
       float tv[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int idx = i0 + tid + 256 * i;
-        tv[i] = (idx < R) ? lse_or_rope.table[(size_t)idx * H + h] / scale : 0.f;
+        tv[i] = (idx < R) ? pos.table[(size_t)idx * H + h] / scale : 0.f;
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -168,15 +133,8 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(
         if (idx < R) tab[idx] = tv[i];
       }
     }
-    for (int key = tid; key < AL_MAXT; key += 256) {   // CLS and padding keys: 0 (overridden below / masked)
-      const int yk = (key >= 1 && key < T) ? (key - 1) / gw : 0;
-      koff[key] = (key >= 1 && key < T) ? yk * rl + (key - 1 - yk * gw) : 0;
-    }
-    const int qi = q0 + li;
-    qpatch = qi >= 1 && qi < T;
-    const int yq = qpatch ? (qi - 1) / gw : 0;
-    qb = qpatch ? (yq + gh - 1) * rl + (qi - 1 - yq * gw) + gw - 1 : R - 3;
-    c0 = qpatch ? R - 2 : R - 1;
+    for (int key = tid; key < AL_MAXT; key += 256) koff[key] = relbias_koff(pos, key, T);
+    rq = relbias_query(pos, q0 + li, T);
   }
   const float sl2 = scale * AL_LOG2E;
   float m_run = -3.0e38f, l_run = 0.f;               // per query column li (same value in the four lane groups)
@@ -214,14 +172,10 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(
     if constexpr (RELBIAS) {                         // s += table[idx(query, key)] / scale: keys k0 + 16 kt + 4 g + r
 #pragma unroll
       for (int kt = 0; kt < 4; ++kt) {
-        const int4 ko = *reinterpret_cast<const int4*>(koff + k0 + 16 * kt + 4 * g);
-        const int kk[4] = {ko.x, ko.y, ko.z, ko.w};
+        float bias[4];
+        relbias_gather(rq, tab, koff + k0 + 16 * kt, g, kt == 0 && k0 == 0, bias);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          int idx = qpatch ? qb - kk[r] : qb;
-          if (kt == 0 && r == 0 && k0 == 0 && g == 0) idx = c0;       // the CLS key
-          s[kt][r] += tab[idx];
-        }
+        for (int r = 0; r < 4; ++r) s[kt][r] += bias[r];
       }
     }
     // ---- online softmax of this tile
@@ -274,8 +228,10 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(
       }
     }
   }
-  // ---- normalise, LSE, store (rows through the wave's LDS tile: 16-byte row stores)
-  if (lse != nullptr && g == 0 && q0 + li < T) lse[(size_t)bh * T + q0 + li] = fmaf(m_run, scale, __logf(l_run));
+  // ---- normalise, LSE, store (rows through the wave's LDS tile: 16-byte row stores; written out in both files, see
+  //      attention.hip)
+  if (POS == AttnPos::None && lse != nullptr && g == 0 && q0 + li < T)
+    lse[(size_t)bh * T + q0 + li] = fmaf(m_run, scale, __logf(l_run));
   const float inv = 1.f / l_run;
   unsigned short* Ow = Os + wave * 16 * LD;
 #pragma unroll
@@ -303,36 +259,29 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(
 // attn_tap.hip (fp32 dot in d order, round to bf16, scale, expf).  One workgroup per (image, head).  ROPE: q_0 and
 // every k row are rotated by their table rows and rounded to bf16 in front of that dot.  RELBIAS: the CLS row's bias,
 // table[R - 1][h] for key 0 and table[R - 3][h] for every patch key, is added to the scaled logit.
-template <int HD, bool ROPE = false, bool RELBIAS = false>
+template <int HD, AttnPos POS = AttnPos::None>
 __global__ __launch_bounds__(256) void attn_long_cls_kernel(
-    const unsigned short* __restrict__ qkv, int T, int H, float scale,
-    typename std::conditional<RELBIAS, AlRelTap,
-                              typename std::conditional<ROPE, AlRopeTap, float* __restrict__>::type>::type tap) {
-  static_assert(!RELBIAS || (!ROPE && HD == 64), "the relative-position bias: head dim 64, no rotary embedding");
+    const unsigned short* __restrict__ qkv, int T, int H, float scale, float* __restrict__ importance, AttnPosArg pos) {
+  static_assert(attn_pos_ok<POS, HD>, "a position scheme: head dim 64");
+  constexpr bool RELBIAS = POS == AttnPos::RelBias, ROPE = POS == AttnPos::Rope;
   __shared__ float logit[AL_MAXT];
   __shared__ float red[8];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
   const size_t row = (size_t)3 * H * HD;
   const unsigned short* base = qkv + (size_t)b * T * row;
-  float* __restrict__ importance;
-  const float* rope = nullptr;
   float bias_cls = 0.f, bias_patch = 0.f;            // RELBIAS: the CLS query against the CLS key / against a patch key
   if constexpr (RELBIAS) {
-    importance = tap.importance;
-    bias_cls = tap.table[(size_t)(tap.R - 1) * H + h];
-    bias_patch = tap.table[(size_t)(tap.R - 3) * H + h];
-  } else if constexpr (ROPE) {
-    importance = tap.importance;
-    rope = tap.rope;
-  } else {
-    importance = tap;
+    const int R = relbias_rows(pos);
+    bias_cls = pos.table[(size_t)(R - 1) * H + h];
+    bias_patch = pos.table[(size_t)(R - 3) * H + h];
   }
   float q[HD];
   if constexpr (ROPE) {
 #pragma unroll
     for (int v = 0; v < HD / 8; ++v) {               // token 0's table row
-      const float4* cs = reinterpret_cast<const float4*>(rope + 8 * v);
+      float4 cs[2];
+      rope_rows(pos.table, 0, HD, 8 * v, cs);
       const uint4 w = rope_chunk(*reinterpret_cast<const uint4*>(base + (size_t)h * HD + 8 * v), cs[0], cs[1]);
       const unsigned int ww[4] = {w.x, w.y, w.z, w.w};
 #pragma unroll
@@ -353,7 +302,8 @@ __global__ __launch_bounds__(256) void attn_long_cls_kernel(
     for (int v = 0; v < HD / 8; ++v) {
       uint4 w = kp[v];
       if constexpr (ROPE) {
-        const float4* cs = reinterpret_cast<const float4*>(rope + (size_t)t * HD + 8 * v);
+        float4 cs[2];
+        rope_rows(pos.table, t, HD, 8 * v, cs);
         w = rope_chunk(w, cs[0], cs[1]);
       }
       const unsigned int ww[4] = {w.x, w.y, w.z, w.w};
@@ -770,17 +720,21 @@ static inline int al_grid(int64_t n) {
 
 static inline int64_t al_a256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
-template <int HD>
+// the main pass (out given), the CLS tap (cls given) and, without a position scheme, the query-mean tap (qmean given)
+template <int HD, AttnPos POS = AttnPos::None>
 static void launch_fwd_long(const void* qkv, int B, int T, int H, float scale, void* out, float* cls, float* qmean,
-                            float* lse, hipStream_t st) {
+                            float* lse, void* stream, AttnPosArg pos = AttnPosArg{nullptr, 0, 0}) {
+  hipStream_t st = (hipStream_t)stream;
   const unsigned short* p = (const unsigned short*)qkv;
   if (out != nullptr)
-    hipLaunchKernelGGL(attn_long_fwd_kernel<HD>, dim3(B * H, (T + 63) / 64), dim3(256), 0, st, p, T, H, scale,
-                       (unsigned short*)out, lse);
-  if (cls != nullptr) hipLaunchKernelGGL(attn_long_cls_kernel<HD>, dim3(B * H), dim3(256), 0, st, p, T, H, scale, cls);
-  if (qmean != nullptr)
-    hipLaunchKernelGGL(attn_long_qmean_kernel<HD>, dim3(B * H, (T + 63) / 64), dim3(256), 0, st, p, T, H, scale,
-                       (const float*)lse, qmean);
+    hipLaunchKernelGGL((attn_long_fwd_kernel<HD, POS>), dim3(B * H, (T + 63) / 64), dim3(256), 0, st, p, T, H, scale,
+                       (unsigned short*)out, lse, pos);
+  if (cls != nullptr)
+    hipLaunchKernelGGL((attn_long_cls_kernel<HD, POS>), dim3(B * H), dim3(256), 0, st, p, T, H, scale, cls, pos);
+  if constexpr (POS == AttnPos::None)
+    if (qmean != nullptr)
+      hipLaunchKernelGGL(attn_long_qmean_kernel<HD>, dim3(B * H, (T + 63) / 64), dim3(256), 0, st, p, T, H, scale,
+                         (const float*)lse, qmean);
 }
 
 template <int HD>
@@ -809,9 +763,8 @@ extern "C" int basd_attention_fwd_long_bf16(const void* qkv, int B, int T, int H
   if (cls_importance != nullptr && T < 2) return fail(BASD_ERR_SHAPE, "attention_fwd_long: the CLS tap needs T >= 2");
   if (qmean_importance != nullptr && (out == nullptr || lse == nullptr))
     return fail(BASD_ERR_SHAPE, "attention_fwd_long: the query-mean tap needs out and lse");
-  hipStream_t st = (hipStream_t)stream;
-  if (hd == 64) launch_fwd_long<64>(qkv, B, T, H, scale, out, cls_importance, qmean_importance, lse, st);
-  else launch_fwd_long<80>(qkv, B, T, H, scale, out, cls_importance, qmean_importance, lse, st);
+  if (hd == 64) launch_fwd_long<64>(qkv, B, T, H, scale, out, cls_importance, qmean_importance, lse, stream);
+  else launch_fwd_long<80>(qkv, B, T, H, scale, out, cls_importance, qmean_importance, lse, stream);
   return check_launch("attention_fwd_long");
 }
 
@@ -821,14 +774,8 @@ extern "C" int basd_attention_fwd_long_rope_bf16(const void* qkv, const float* r
   if (hd != 64 || T < 2 || T > AL_MAXT || H < 1 || B < 1 || rope == nullptr)
     return fail(BASD_ERR_SHAPE, "attention_fwd_long_rope: B=%d T=%d H=%d hd=%d rope=%s unsupported (hd 64, 2 <= T <= %d, "
                                 "B, H >= 1, a table)", B, T, H, hd, rope == nullptr ? "NULL" : "given", AL_MAXT);
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned short* p = (const unsigned short*)qkv;
-  if (out != nullptr)
-    hipLaunchKernelGGL((attn_long_fwd_kernel<64, true>), dim3(B * H, (T + 63) / 64), dim3(256), 0, st, p, T, H, scale,
-                       (unsigned short*)out, rope);
-  if (cls_importance != nullptr)
-    hipLaunchKernelGGL((attn_long_cls_kernel<64, true>), dim3(B * H), dim3(256), 0, st, p, T, H, scale,
-                       AlRopeTap{cls_importance, rope});
+  launch_fwd_long<64, AttnPos::Rope>(qkv, B, T, H, scale, out, cls_importance, nullptr, nullptr, stream,
+                                     AttnPosArg{rope, 0, 0});
   return check_launch("attention_fwd_long_rope");
 }
 
@@ -843,14 +790,8 @@ extern "C" int basd_attention_fwd_long_relbias_bf16(const void* qkv, const float
                                 "(hd 64, 2 <= gh * gw + 1 <= %d, B, H >= 1, the three pointers, a finite scale > 0)",
                 B, gh, gw, H, hd, (double)scale,
                 (qkv == nullptr || table == nullptr || out == nullptr) ? "a NULL" : "given", AL_MAXT);
-  const int T = (int)T64;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned short* p = (const unsigned short*)qkv;
-  hipLaunchKernelGGL((attn_long_fwd_kernel<64, false, true>), dim3(B * H, (T + 63) / 64), dim3(256), 0, st, p, T, H,
-                     scale, (unsigned short*)out, AlRelBias{table, gh, gw});
-  if (cls_importance != nullptr)
-    hipLaunchKernelGGL((attn_long_cls_kernel<64, false, true>), dim3(B * H), dim3(256), 0, st, p, T, H, scale,
-                       AlRelTap{cls_importance, table, (2 * gh - 1) * (2 * gw - 1) + 3});
+  launch_fwd_long<64, AttnPos::RelBias>(qkv, B, (int)T64, H, scale, out, cls_importance, nullptr, nullptr, stream,
+                                        AttnPosArg{table, gh, gw});
   return check_launch("attention_fwd_long_relbias");
 }
 

@@ -29,7 +29,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..losses._ops import get_ops, library_fallback
-from .vit import HALF_MEAN, HALF_STD, IMAGENET_MEAN, IMAGENET_STD, Attention, Block, MixedLayerNorm, PatchEmbed
+from .vit import HALF_MEAN, HALF_STD, IMAGENET_MEAN, IMAGENET_STD, Block, MixedLayerNorm, PatchEmbed, QVBiasAttention
 
 # 0: dense bias + library SDPA + separate tap on the device too (A/B runs: scripts/time_beit_teacher.py flips it inside
 # one process)
@@ -47,35 +47,16 @@ def relative_position_index(gh: int, gw: int) -> torch.Tensor:
     return index
 
 
-class RelPosAttention(Attention):
-    """timm Beit ``Attention``: ``qkv`` without a bias parameter, ``q_bias`` / ``v_bias`` separate (the k bias is
-    zero), ``relative_position_bias_table`` [(2 gh - 1)(2 gw - 1) + 3, heads] kept in fp32 whatever the model is cast
-    to."""
+class RelPosAttention(QVBiasAttention):
+    """timm Beit ``Attention`` (``QVBiasAttention``) with ``relative_position_bias_table``
+    [(2 gh - 1)(2 gw - 1) + 3, heads], kept in fp32 whatever the model is cast to."""
+    _fp32_name = "relative_position_bias_table"
 
     def __init__(self, dim: int, num_heads: int, window_size: tuple = (14, 14)):
-        super().__init__(dim, num_heads, qkv_bias=False)
+        super().__init__(dim, num_heads)
         self.window_size = gh, gw = int(window_size[0]), int(window_size[1])
-        self.q_bias = nn.Parameter(torch.zeros(dim))
-        self.v_bias = nn.Parameter(torch.zeros(dim))
         self.relative_position_bias_table = nn.Parameter(torch.zeros((2 * gh - 1) * (2 * gw - 1) + 3, num_heads))
         self.register_buffer("relative_position_index", relative_position_index(gh, gw), persistent=False)
-
-    def _apply(self, fn, recurse=True):
-        """``.to(bf16)`` / ``.half()`` move the table with the module but leave its values in fp32: the kernel reads the
-        fp32 table, and a bias on fp32 logits gains nothing from a 16-bit copy"""
-        keep = self.relative_position_bias_table.data
-        super()._apply(fn, recurse)
-        table = self.relative_position_bias_table
-        if table.dtype in (torch.bfloat16, torch.float16):
-            table.data = keep.to(table.device)
-        return self
-
-    @torch.no_grad()
-    def materialize_qkv_bias(self) -> None:
-        """frozen teacher: ``cat(q_bias, 0, v_bias)`` becomes the bias of the ``qkv`` layer once, so that the projection
-        stays the one fused GEMM call (bias in the epilogue) of every other ViT"""
-        bias = torch.cat([self.q_bias, torch.zeros_like(self.q_bias), self.v_bias])
-        self.qkv.bias = nn.Parameter(bias.to(self.qkv.weight.dtype), requires_grad=False)
 
     def _dense_bias(self, t: int) -> torch.Tensor:
         """[heads, T, T] fp32 (torch path only)"""
@@ -98,9 +79,7 @@ class RelPosAttention(Attention):
         if t != gh * gw + 1:
             raise ValueError(f"RelPosAttention: {t} tokens, but the bias table is for a {gh} x {gw} grid + CLS "
                              f"({gh * gw + 1} tokens); tables are not resampled")
-        qkv_flat = self.qkv(x)
-        if self.qkv.bias is None:                    # not materialised (a model under training, a CPU check)
-            qkv_flat = qkv_flat + torch.cat([self.q_bias, torch.zeros_like(self.q_bias), self.v_bias]).to(qkv_flat.dtype)
+        qkv_flat = self._qkv(x)
         table = self.relative_position_bias_table
         ops = get_ops()
         on_device = ops.handles(qkv_flat)
@@ -108,18 +87,13 @@ class RelPosAttention(Attention):
         if (_FUSED_RELBIAS_ATTENTION and on_device and not torch.is_grad_enabled() and qkv_flat.dtype == torch.bfloat16
                 and table.dtype == torch.float32 and has_cls):
             # frozen block: fused attention with the bias gathered in the kernel, the tap as a by-product
-            # (csrc/attention.hip, RELBIAS; past its 272 tokens the tiled kernels of csrc/attention_long.hip, RELBIAS)
-            fused = None
-            if ops.attention_fwd_relbias_supported(gh, gw, self.head_dim):
-                fused = ops.attention_fwd_relbias
-            elif ops.attention_fwd_long_relbias_supported(gh, gw, self.head_dim):
-                fused = ops.attention_fwd_long_relbias
-            if fused is not None:
-                out_flat, imp = fused(qkv_flat, table, gh, gw, self.num_heads, self.head_dim, self.scale,
-                                      self.tap is not None)
-                if self.tap is not None:
-                    self.tap["out"] = imp
-                return self.proj(out_flat)
+            # (csrc/attention.hip; past its 272 tokens the tiled kernels of csrc/attention_long.hip)
+            out = self._fused_frozen(
+                ((ops.attention_fwd_relbias_supported(gh, gw, self.head_dim), ops.attention_fwd_relbias),
+                 (ops.attention_fwd_long_relbias_supported(gh, gw, self.head_dim), ops.attention_fwd_long_relbias)),
+                qkv_flat, table, gh, gw)
+            if out is not None:
+                return out
         if on_device:
             library_fallback("attention (relative bias)", f"grid={gh}x{gw} head_dim={self.head_dim} "
                                                           f"dtype={qkv_flat.dtype} grad={torch.is_grad_enabled()}")

@@ -49,7 +49,8 @@ REG_TOKENS = 4
 class Dinov3Attention(RopeAttention):
     """``SelfAttention`` of DINOv3 on ``RopeAttention``'s forward: a qkv layer WITH a bias (k third zero), q and k of
     the patch tokens rotated by the rows of ``rope`` (``dinov3_rope_table``; CLS and registers: identity rows).  The
-    forward is right once ``interleave_rope_pairs`` has run."""
+    forward is right once ``interleave_rope_pairs`` has run.  It skips ``QVBiasAttention.__init__`` and so has no
+    ``q_bias`` / ``v_bias``: its ``qkv.bias`` is never None, which is why ``_qkv`` never asks for them."""
 
     def __init__(self, dim: int, num_heads: int, grid: tuple = (14, 14), rope_base: float = 100.0,
                  prefix_tokens: int = 1 + REG_TOKENS):

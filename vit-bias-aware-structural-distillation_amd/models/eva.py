@@ -33,7 +33,7 @@ import torch.nn.functional as F
 from .._native import rope_table
 from ..losses._ops import get_ops, library_fallback
 from .linear import BasdLinear
-from .vit import CLIP_MEAN, CLIP_STD, Attention, Block, MixedLayerNorm, PatchEmbed
+from .vit import CLIP_MEAN, CLIP_STD, Block, MixedLayerNorm, PatchEmbed, QVBiasAttention
 
 # 0: torch rotation + library SDPA + separate tap, unfused SwiGLU, torch token assembly on the device too (A/B runs:
 # scripts/time_eva_teacher.py flips it inside one process)
@@ -50,35 +50,18 @@ def apply_rope(x: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
     return torch.stack([a * c - b * s, b * c + a * s], dim=-1).flatten(-2).to(x.dtype)
 
 
-class RopeAttention(Attention):
-    """timm ``EvaAttention``: ``qkv`` without a bias parameter, ``q_bias`` / ``v_bias`` separate (the k bias is zero),
-    q and k rotated by the rows of ``rope`` -- fp32 [prefix + gh gw, hd / 2, 2], a non-persistent buffer kept in fp32
-    whatever the model is cast to."""
+class RopeAttention(QVBiasAttention):
+    """timm ``EvaAttention`` (``QVBiasAttention``): q and k rotated by the rows of ``rope`` -- fp32
+    [prefix + gh gw, hd / 2, 2], a non-persistent buffer kept in fp32 whatever the model is cast to (the angles of a
+    16 x 16 grid do not survive 8 bits of mantissa)."""
+    _fp32_name = "rope"
 
     def __init__(self, dim: int, num_heads: int, grid: tuple = (16, 16), ref_grid: tuple | None = None,
                  prefix_tokens: int = 1):
-        super().__init__(dim, num_heads, qkv_bias=False)
+        super().__init__(dim, num_heads)
         self.grid = int(grid[0]), int(grid[1])
-        self.q_bias = nn.Parameter(torch.zeros(dim))
-        self.v_bias = nn.Parameter(torch.zeros(dim))
         self.register_buffer("rope", rope_table(*self.grid, self.head_dim, ref_grid=ref_grid,
                                                 prefix_tokens=prefix_tokens), persistent=False)
-
-    def _apply(self, fn, recurse=True):
-        """``.to(bf16)`` / ``.half()`` move the table with the module but leave its values in fp32: the kernel reads
-        an fp32 table, and the angles of a 16 x 16 grid do not survive 8 bits of mantissa"""
-        keep = self.rope
-        super()._apply(fn, recurse)
-        if self.rope.dtype in (torch.bfloat16, torch.float16):
-            self.rope = keep.to(self.rope.device)
-        return self
-
-    @torch.no_grad()
-    def materialize_qkv_bias(self) -> None:
-        """frozen teacher: ``cat(q_bias, 0, v_bias)`` becomes the bias of the ``qkv`` layer once, so that the projection
-        stays the one fused GEMM call (bias in the epilogue) of every other ViT"""
-        bias = torch.cat([self.q_bias, torch.zeros_like(self.q_bias), self.v_bias])
-        self.qkv.bias = nn.Parameter(bias.to(self.qkv.weight.dtype), requires_grad=False)
 
     def forward(self, x):
         b, t, c = x.shape
@@ -86,24 +69,20 @@ class RopeAttention(Attention):
         if t != rope.shape[0]:
             raise ValueError(f"RopeAttention: {t} tokens, but the rotary table is for a {self.grid[0]} x {self.grid[1]} "
                              f"grid + prefix ({rope.shape[0]} tokens)")
-        qkv_flat = self.qkv(x)
-        if self.qkv.bias is None:                    # not materialised (a model under training, a CPU check)
-            qkv_flat = qkv_flat + torch.cat([self.q_bias, torch.zeros_like(self.q_bias), self.v_bias]).to(qkv_flat.dtype)
+        qkv_flat = self._qkv(x)
         ops = get_ops()
         on_device = ops.handles(qkv_flat)
         has_cls = self.tap is None or bool(self.tap["has_cls"])
         if (_FUSED_EVA_DISPATCH and on_device and not torch.is_grad_enabled() and qkv_flat.dtype == torch.bfloat16
-                and rope.dtype == torch.float32 and has_cls
-                and (ops.attention_fwd_rope_supported(t, self.head_dim)
-                     or ops.attention_fwd_long_rope_supported(t, self.head_dim))):
+                and rope.dtype == torch.float32 and has_cls):
             # frozen block: fused attention with q and k rotated in the kernel, the tap as a by-product
-            # (csrc/attention.hip, ROPE; past its 272 tokens the tiled kernel of csrc/attention_long.hip, ROPE)
-            fwd = (ops.attention_fwd_rope if ops.attention_fwd_rope_supported(t, self.head_dim)
-                   else ops.attention_fwd_long_rope)
-            out_flat, imp = fwd(qkv_flat, rope, self.num_heads, self.head_dim, self.scale, self.tap is not None)
-            if self.tap is not None:
-                self.tap["out"] = imp
-            return self.proj(out_flat)
+            # (csrc/attention.hip; past its 272 tokens the tiled kernel of csrc/attention_long.hip)
+            out = self._fused_frozen(
+                ((ops.attention_fwd_rope_supported(t, self.head_dim), ops.attention_fwd_rope),
+                 (ops.attention_fwd_long_rope_supported(t, self.head_dim), ops.attention_fwd_long_rope)),
+                qkv_flat, rope)
+            if out is not None:
+                return out
         if on_device:
             library_fallback("attention (rope)", f"T={t} head_dim={self.head_dim} dtype={qkv_flat.dtype} "
                                                  f"grad={torch.is_grad_enabled()}")

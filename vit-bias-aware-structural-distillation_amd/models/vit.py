@@ -313,6 +313,59 @@ class Attention(nn.Module):
         attn = ((q.float() @ k.float().transpose(-2, -1)) * self.scale).softmax(dim=-1)
         return attn.mean(dim=(1, 2))
 
+    def _fused_frozen(self, entries, qkv_flat, *pos_args):
+        """Frozen block with a position scheme (``RelPosAttention``, ``RopeAttention``): ``entries`` are the eligible
+        ``(supported, entry)`` pairs in order, the short kernel first.  Runs the first supported entry on
+        ``(qkv_flat, *pos_args, heads, head_dim, scale, want_tap)``, sets the tap (a by-product of the kernel) and
+        returns the projected output; None on a miss (the caller counts the library fallback)."""
+        for supported, entry in entries:
+            if supported:
+                out_flat, imp = entry(qkv_flat, *pos_args, self.num_heads, self.head_dim, self.scale,
+                                      self.tap is not None)
+                if self.tap is not None:
+                    self.tap["out"] = imp
+                return self.proj(out_flat)
+        return None
+
+
+class QVBiasAttention(Attention):
+    """The attention of timm's Beit / Eva: ``qkv`` without a bias parameter, ``q_bias`` / ``v_bias`` separate (the k bias
+    is zero), and one fp32 position tensor -- the parameter or buffer named ``_fp32_name`` -- that keeps its fp32 values
+    whatever the model is cast to: the kernels read fp32 tables, which gain nothing from (or do not survive) a 16-bit
+    copy."""
+    _fp32_name: str                                  # set by every subclass
+
+    def __init__(self, dim: int, num_heads: int):
+        if not getattr(type(self), "_fp32_name", ""):
+            raise TypeError("QVBiasAttention is a base: a subclass names its fp32 tensor in _fp32_name")
+        super().__init__(dim, num_heads, qkv_bias=False)
+        self.q_bias = nn.Parameter(torch.zeros(dim))
+        self.v_bias = nn.Parameter(torch.zeros(dim))
+
+    def _apply(self, fn, recurse=True):
+        """``.to(bf16)`` / ``.half()`` move the tensor with the module but leave its values in fp32"""
+        keep = getattr(self, self._fp32_name).data
+        super()._apply(fn, recurse)
+        moved = getattr(self, self._fp32_name)
+        if moved.dtype in (torch.bfloat16, torch.float16):
+            moved.data = keep.to(moved.device)
+        return self
+
+    def _qkv_bias(self) -> torch.Tensor:
+        return torch.cat([self.q_bias, torch.zeros_like(self.q_bias), self.v_bias])
+
+    @torch.no_grad()
+    def materialize_qkv_bias(self) -> None:
+        """frozen teacher: ``cat(q_bias, 0, v_bias)`` becomes the bias of the ``qkv`` layer once, so that the projection
+        stays the one fused GEMM call (bias in the epilogue) of every other ViT"""
+        self.qkv.bias = nn.Parameter(self._qkv_bias().to(self.qkv.weight.dtype), requires_grad=False)
+
+    def _qkv(self, x):
+        """the packed projection, with the bias added here while it is not materialised (a model under training, a CPU
+        check)"""
+        qkv_flat = self.qkv(x)
+        return qkv_flat if self.qkv.bias is not None else qkv_flat + self._qkv_bias().to(qkv_flat.dtype)
+
 
 class QuickGELU(nn.Module):
     """x * sigmoid(1.702 x): the activation of the OpenAI-weight CLIP towers (timm ``quick_gelu``)"""
