@@ -1,7 +1,7 @@
 """forward_features of a frozen Swin teacher (default swin_tiny_patch4_window7_224 at 224 px), bf16: the fused trunk
 (csrc/swin.hip, csrc/swin_wide.hip for the window-12 presets + basd_gemm_bf16 + the LayerNorm kernels) against the
-plain-torch path of the same module (library GEMMs, torch softmax and index gathers), in one process.  The parent of this model does not exist, so the library path of the same box is
-the only baseline.
+plain-torch path of the same module (library GEMMs, torch softmax and index gathers), in one process.  The parent of
+this model does not exist, so the library path of the same box is the only baseline.
 
 Device events, warm-up, medians of N timed forwards per side; the two sides alternate for ``--rounds`` rounds and every
 round prints one JSON line (the raw lines of profiles/swin_trunk_ab.txt and profiles/swin_384_teacher_ab.txt).

@@ -4,6 +4,8 @@ roll / reshape formulation of ``tests/_swin_ref.py``, not on the index arithmeti
 surface, layouts and rounding points as ``basd_amd._native``.  Never imported by the package."""
 from __future__ import annotations
 
+from functools import partial
+
 import torch
 import torch.nn.functional as F
 
@@ -14,9 +16,13 @@ from tests._convnext_emul import handles  # noqa: F401
 WINDOW_SLOTS = 64
 
 
-def window_attention_supported(h, w, ws, shift, heads, c, ld_qkv, ld_out):
-    return (1 <= ws <= 8 and 0 <= shift < ws and h >= ws and w >= ws and h % ws == 0 and w % ws == 0 and heads >= 1
+def window_supported(lo, hi, h, w, ws, shift, heads, c, ld_qkv, ld_out):
+    """the gate of a window attention entry that takes the windows lo .. hi"""
+    return (lo <= ws <= hi and 0 <= shift < ws and h >= ws and w >= ws and h % ws == 0 and w % ws == 0 and heads >= 1
             and c == 32 * heads and ld_qkv % 8 == 0 and ld_out % 8 == 0 and ld_qkv >= 3 * c and ld_out >= c)
+
+
+window_attention_supported = partial(window_supported, 1, 8)
 
 
 def window_bias_image(bias):
@@ -26,17 +32,23 @@ def window_bias_image(bias):
     return img
 
 
-def window_attention(qkv, bias_img, ws, shift, heads, scale, ld_out=None):
-    assert qkv.dtype == torch.bfloat16 and qkv.dim() == 4 and qkv.is_contiguous() and bias_img.dtype == torch.float32
+def window_attention_rows(supported, qkv, bias, ws, shift, heads, scale, ld_out):
+    """what either entry returns, from the expanded bias [heads, ws^2, ws^2] and the entry's gate"""
+    assert qkv.dtype == torch.bfloat16 and qkv.dim() == 4 and qkv.is_contiguous() and bias.dtype == torch.float32
     b, h, w, ld_qkv = qkv.shape
-    c, n = 32 * heads, ws * ws
+    c = 32 * heads
     ld_out = c if ld_out is None else ld_out
-    assert window_attention_supported(h, w, ws, shift, heads, c, ld_qkv, ld_out)
-    assert bias_img.shape == (heads, WINDOW_SLOTS, WINDOW_SLOTS)
-    y = R.window_attention(qkv[..., :3 * c].float(), bias_img[:, :n, :n], ws, shift, heads, scale, round_p=True)
+    assert supported(h, w, ws, shift, heads, c, ld_qkv, ld_out)
+    y = R.window_attention(qkv[..., :3 * c].float(), bias, ws, shift, heads, scale, round_p=True)
     out = torch.zeros(b, h, w, ld_out, dtype=torch.bfloat16)
     out[..., :c] = y.to(torch.bfloat16)
     return out
+
+
+def window_attention(qkv, bias_img, ws, shift, heads, scale, ld_out=None):
+    assert bias_img.shape == (heads, WINDOW_SLOTS, WINDOW_SLOTS)
+    return window_attention_rows(window_attention_supported, qkv, bias_img[:, :ws * ws, :ws * ws], ws, shift, heads, scale,
+                                 ld_out)
 
 
 def patch_merge_ln_supported(c, ld_in, h=2, w=2):

@@ -1703,11 +1703,23 @@ def add_relu_(y: torch.Tensor, r: torch.Tensor, c: int | None = None) -> torch.T
 
 # --------------------------------------------------------------------------- Swin teacher trunk (csrc/swin.hip, csrc/swin_wide.hip)
 WINDOW_SLOTS = 64          # slots of a window tile: ws <= 8; also the row / column count of a bias image
+WINDOW_WIDE_MIN, WINDOW_WIDE_MAX = 9, 16      # windows of basd_window_attention_fwd_wide_bf16 (csrc/swin_wide.hip)
+_WINDOW, _WINDOW_WIDE = (1, 8), (WINDOW_WIDE_MIN, WINDOW_WIDE_MAX)       # (lo, hi) of the two entries; 8^2 = WINDOW_SLOTS
+
+
+def _window_supported(window, h: int, w: int, ws: int, shift: int, heads: int, c: int, ld_qkv: int, ld_out: int) -> bool:
+    """the refusals of both entries (window_attention_check, csrc/window_attn.h) for the windows lo .. hi"""
+    return (window[0] <= ws <= window[1] and 0 <= shift < ws and h >= ws and w >= ws and h % ws == 0 and w % ws == 0
+            and heads >= 1 and c == 32 * heads and ld_qkv % 8 == 0 and ld_out % 8 == 0 and ld_qkv >= 3 * c and ld_out >= c)
 
 
 def window_attention_supported(h: int, w: int, ws: int, shift: int, heads: int, c: int, ld_qkv: int, ld_out: int) -> bool:
-    return (1 <= ws <= 8 and 0 <= shift < ws and h >= ws and w >= ws and h % ws == 0 and w % ws == 0 and heads >= 1
-            and c == 32 * heads and ld_qkv % 8 == 0 and ld_out % 8 == 0 and ld_qkv >= 3 * c and ld_out >= c)
+    return _window_supported(_WINDOW, h, w, ws, shift, heads, c, ld_qkv, ld_out)
+
+
+def window_attention_wide_supported(h: int, w: int, ws: int, shift: int, heads: int, c: int, ld_qkv: int,
+                                    ld_out: int) -> bool:
+    return _window_supported(_WINDOW_WIDE, h, w, ws, shift, heads, c, ld_qkv, ld_out)
 
 
 def window_bias_image(bias: torch.Tensor) -> torch.Tensor:
@@ -1720,38 +1732,32 @@ def window_bias_image(bias: torch.Tensor) -> torch.Tensor:
     return img
 
 
+def _window_attention(entry: str, window, qkv, bias, bias_shape, refusal: str, ws, shift, heads, scale, ld_out):
+    """the body of both wrappers; ``window`` = (lo, hi), ``refusal`` the message with {call} and {shape} left open"""
+    _need_cuda(qkv, bias)
+    assert qkv.dtype == torch.bfloat16 and qkv.dim() == 4 and qkv.is_contiguous()
+    assert bias.dtype == torch.float32 and bias.is_contiguous()
+    b, h, w, ld_qkv = qkv.shape
+    c = 32 * heads
+    ld_out = c if ld_out is None else ld_out
+    if not (_window_supported(window, h, w, ws, shift, heads, c, ld_qkv, ld_out) and bias.shape == bias_shape):
+        raise BasdNativeError(refusal.format(call=f"grid {h}x{w} ws={ws} shift={shift} heads={heads} ld_qkv={ld_qkv} "
+                                                  f"ld_out={ld_out}", shape=tuple(bias.shape)))
+    out = torch.empty(b, h, w, ld_out, dtype=torch.bfloat16, device=qkv.device)
+    _check(getattr(lib(), entry)(_ptr(qkv), _ptr(bias), b, h, w, heads, c, ws, shift, ld_qkv, ld_out, ctypes.c_float(scale),
+                                 _ptr(out), _stream()), entry)
+    return out
+
+
 def window_attention(qkv: torch.Tensor, bias_img: torch.Tensor, ws: int, shift: int, heads: int, scale: float,
                      ld_out: int | None = None) -> torch.Tensor:
     """qkv [B, H, W, ld_qkv] bf16 rows (q | k | v in the first 3 C columns, each [heads, 32]), bias_img from
     ``window_bias_image`` -> (shifted-)window attention [B, H, W, ld_out] bf16, columns C .. ld_out zero.  Token
     (y, x) sits in slot ((y - shift) mod H, (x - shift) mod W) of the window partition; the mask of a shifted block is
     computed from the slot coordinates."""
-    _need_cuda(qkv, bias_img)
-    assert qkv.dtype == torch.bfloat16 and qkv.dim() == 4 and qkv.is_contiguous()
-    assert bias_img.dtype == torch.float32 and bias_img.is_contiguous()
-    b, h, w, ld_qkv = qkv.shape
-    c = 32 * heads
-    ld_out = c if ld_out is None else ld_out
-    if not (window_attention_supported(h, w, ws, shift, heads, c, ld_qkv, ld_out)
-            and bias_img.shape == (heads, WINDOW_SLOTS, WINDOW_SLOTS)):
-        raise BasdNativeError(f"window_attention: grid {h}x{w} ws={ws} shift={shift} heads={heads} ld_qkv={ld_qkv} "
-                              f"ld_out={ld_out} bias={tuple(bias_img.shape)} is not tiled (ws <= 8, head dim 32, grid a "
-                              "multiple of ws, bias image [heads, 64, 64])")
-    out = torch.empty(b, h, w, ld_out, dtype=torch.bfloat16, device=qkv.device)
-    _check(lib().basd_window_attention_fwd_bf16(_ptr(qkv), _ptr(bias_img), b, h, w, heads, c, ws, shift, ld_qkv, ld_out,
-                                                ctypes.c_float(scale), _ptr(out), _stream()),
-           "basd_window_attention_fwd_bf16")
-    return out
-
-
-WINDOW_WIDE_MIN, WINDOW_WIDE_MAX = 9, 16      # windows of basd_window_attention_fwd_wide_bf16 (csrc/swin_wide.hip)
-
-
-def window_attention_wide_supported(h: int, w: int, ws: int, shift: int, heads: int, c: int, ld_qkv: int,
-                                    ld_out: int) -> bool:
-    return (WINDOW_WIDE_MIN <= ws <= WINDOW_WIDE_MAX and 0 <= shift < ws and h >= ws and w >= ws and h % ws == 0
-            and w % ws == 0 and heads >= 1 and c == 32 * heads and ld_qkv % 8 == 0 and ld_out % 8 == 0
-            and ld_qkv >= 3 * c and ld_out >= c)
+    return _window_attention("basd_window_attention_fwd_bf16", _WINDOW, qkv, bias_img, (heads, WINDOW_SLOTS, WINDOW_SLOTS),
+                             "window_attention: {call} bias={shape} is not tiled (ws <= 8, head dim 32, grid a multiple "
+                             "of ws, bias image [heads, 64, 64])", ws, shift, heads, scale, ld_out)
 
 
 def window_attention_wide(qkv: torch.Tensor, table: torch.Tensor, ws: int, shift: int, heads: int, scale: float,
@@ -1759,22 +1765,9 @@ def window_attention_wide(qkv: torch.Tensor, table: torch.Tensor, ws: int, shift
     """``window_attention`` for windows 9 .. 16 (81 .. 256 slots; window 12 of the 384 px Swin checkpoints): the same
     rows, roll / partition arithmetic, mask and rounding points.  ``table`` is timm's ``relative_position_bias_table``
     itself, fp32 [(2 ws - 1)^2, heads]; the kernel computes the index per logit, no [N, N] image is built."""
-    _need_cuda(qkv, table)
-    assert qkv.dtype == torch.bfloat16 and qkv.dim() == 4 and qkv.is_contiguous()
-    assert table.dtype == torch.float32 and table.is_contiguous()
-    b, h, w, ld_qkv = qkv.shape
-    c = 32 * heads
-    ld_out = c if ld_out is None else ld_out
-    if not (window_attention_wide_supported(h, w, ws, shift, heads, c, ld_qkv, ld_out)
-            and table.shape == ((2 * ws - 1) ** 2, heads)):
-        raise BasdNativeError(f"window_attention_wide: grid {h}x{w} ws={ws} shift={shift} heads={heads} ld_qkv={ld_qkv} "
-                              f"ld_out={ld_out} table={tuple(table.shape)} is not tiled (9 <= ws <= 16, head dim 32, grid "
-                              "a multiple of ws, bias table [(2 ws - 1)^2, heads])")
-    out = torch.empty(b, h, w, ld_out, dtype=torch.bfloat16, device=qkv.device)
-    _check(lib().basd_window_attention_fwd_wide_bf16(_ptr(qkv), _ptr(table), b, h, w, heads, c, ws, shift, ld_qkv, ld_out,
-                                                     ctypes.c_float(scale), _ptr(out), _stream()),
-           "basd_window_attention_fwd_wide_bf16")
-    return out
+    return _window_attention("basd_window_attention_fwd_wide_bf16", _WINDOW_WIDE, qkv, table, ((2 * ws - 1) ** 2, heads),
+                             "window_attention_wide: {call} table={shape} is not tiled (9 <= ws <= 16, head dim 32, grid "
+                             "a multiple of ws, bias table [(2 ws - 1)^2, heads])", ws, shift, heads, scale, ld_out)
 
 
 def patch_merge_ln_supported(c: int, ld_in: int, h: int = 2, w: int = 2) -> bool:

@@ -3,38 +3,29 @@
 // Activations are the channels-last rows of csrc/convnext.hip: a token grid [B, H, W, C] is a [B H W, ld] bf16 matrix
 // (ld >= C, columns C .. ld zero; the 96-wide stage of Swin-T lives in rows of 128).
 //
-//   basd_window_attention_fwd_bf16   (shifted-)window attention straight from the packed qkv rows.  The cyclic roll, the
-//                                    window partition and their inverses are index arithmetic: slot (iy, ix) of window
-//                                    (wy, wx) IS token ((wy ws + iy + shift) mod H, (wx ws + ix + shift) mod W), for the
-//                                    loads and for the store; the shift mask is the label of the slot's rolled coordinate
-//                                    (wy ws + iy, wx ws + ix), computed inline.
+//   basd_window_attention_fwd_bf16   (shifted-)window attention straight from the packed qkv rows, windows up to 8 x 8.
+//                                    Layout, slot rule and everything behind the logits: window_attn.h.
 //   basd_patch_merge_ln_bf16         2 x 2 neighbour concatenation + LayerNorm over the 4 C channels, one pass.
-#include "basd_frag.h"
+#include "window_attn.h"
 
 namespace basd {
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Window attention.  One wave per (window, head), four per workgroup (consecutive heads of one window, so the waves of a
-// workgroup read neighbouring 64-byte pieces of the same rows).  N = ws^2 <= 64 slots fill up to four 16-slot tiles; head
-// dim 32 is exactly one k-step of v_mfma_f32_16x16x32_bf16.
-//   S^T = K Q^T   A = K rows, B = Q rows, both straight from global memory (slot 16 t + (lane & 15), d = 8 (lane >> 4) ..):
-//                 accumulator of key tile kt / query tile qt: keys 16 kt + 4 (lane >> 4) + {0..3}, query 16 qt + (lane & 15);
-//   logits        scale * s + bias[h][query][key] + (label[query] != label[key] ? -100 : 0) in fp32, padding keys -3e38;
-//   softmax       fp32, over the registers and the four lane groups of a query column (xor 16, 32);
-//   O = P V       the S^T accumulators of a 32-key step are the A fragment (attention.hip), B = V through the transposing
-//                 LDS read on the same eight keys; V of the head is the only operand staged in LDS;
-//   the 16 x 32 output tile goes through LDS so that every lane stores 16 contiguous bytes.
+// workgroup read neighbouring 64-byte pieces of the same rows).  N = ws^2 <= 64 slots fill up to four 16-slot tiles.
+//   S^T = K Q^T   A = K rows, B = Q rows, both straight from global memory (slot 16 t + (lane & 15), d = 8 (lane >> 4) ..);
+//   logits        the bias is bias[h][query][key] of the image, a padding key is one whose number is >= N;
+//   V of the head is the only operand staged in LDS.
 // Every global load of the wave is issued before its first LDS store.  Padding slots (>= N) load nothing (zero q, k, v),
 // are excluded from every softmax as keys and are never stored as queries.
 constexpr int WA_WAVES = 4;
-constexpr int WA_LD = 40;                             // LDS row stride in bf16: 32 + 8 (16-byte aligned, bank rotation)
 constexpr int WA_SLOTS = 64;                          // slots of a window tile = row / column count of a bias image
 
 __global__ __launch_bounds__(64 * WA_WAVES) void window_attention_kernel(
     const unsigned short* __restrict__ qkv, const float* __restrict__ bias, int H, int W, int heads, int C, int ws,
     int shift, int ld_qkv, int ld_out, float scale, unsigned short* __restrict__ out, int64_t problems) {
-  __shared__ __align__(16) unsigned short Vs[WA_WAVES][WA_SLOTS * WA_LD];
-  __shared__ __align__(16) unsigned short Os[WA_WAVES][16 * WA_LD];
+  __shared__ __align__(16) unsigned short Vs[WA_WAVES][WA_SLOTS * WIN_LD];
+  __shared__ __align__(16) unsigned short Os[WA_WAVES][16 * WIN_LD];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int li = lane & 15, g = lane >> 4;
   const int N = ws * ws, nt = (N + 15) >> 4;          // live slots, live 16-slot tiles
@@ -54,21 +45,7 @@ __global__ __launch_bounds__(64 * WA_WAVES) void window_attention_kernel(
   // slot = lane: its token row in [B H W) and the mask label of its rolled coordinate
   int64_t myrow = 0;
   int mylab = 0;
-  {
-    const int iy = lane / ws, ix = lane - iy * ws;
-    if (lane < N) {
-      const int ry = wy * ws + iy, rx = wx * ws + ix;                  // coordinate in the rolled grid
-      int y = ry + shift, x = rx + shift;
-      if (y >= H) y -= H;
-      if (x >= W) x -= W;
-      myrow = (b * H + y) * (int64_t)W + x;
-      if (shift > 0) {                                                 // slices [0, -ws), [-ws, -shift), [-shift, end)
-        const int ly = ry < H - ws ? 0 : (ry < H - shift ? 1 : 2);
-        const int lx = rx < W - ws ? 0 : (rx < W - shift ? 1 : 2);
-        mylab = 3 * ly + lx;
-      }
-    }
-  }
+  if (lane < N) myrow = window_slot(lane, ws, wy, wx, b, H, W, shift, mylab);
   const int rlo = (int)(myrow & 0xffffffff), rhi = (int)(myrow >> 32);
 
   // ---- all loads of the wave: q, k, v fragments of slot 16 t + li, d = 8 g .. 8 g + 7
@@ -90,7 +67,7 @@ __global__ __launch_bounds__(64 * WA_WAVES) void window_attention_kernel(
   unsigned short* Vw = Vs[wave];
   unsigned short* Ow = Os[wave];
 #pragma unroll
-  for (int t = 0; t < 4; ++t) *reinterpret_cast<uint4*>(Vw + (16 * t + li) * WA_LD + 8 * g) = vf[t];
+  for (int t = 0; t < 4; ++t) *reinterpret_cast<uint4*>(Vw + (16 * t + li) * WIN_LD + 8 * g) = vf[t];
   __syncthreads();
 
   // labels of this lane's keys 16 kt + 4 g + r
@@ -128,56 +105,15 @@ __global__ __launch_bounds__(64 * WA_WAVES) void window_attention_kernel(
         mx = fmaxf(mx, l);
       }
     }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    float sum = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float p = __builtin_amdgcn_exp2f((s[kt][r] - mx) * 1.4426950408889634f);   // padding keys: exp2(-huge) = 0
-        s[kt][r] = p;
-        sum += p;
-      }
-    sum += __shfl_xor(sum, 16, 64);
-    sum += __shfl_xor(sum, 32, 64);
-    const float inv = 1.f / sum;
-    // ---- O = P V over two 32-key steps (a step without live keys has P = 0 and V = 0)
+    const float inv = window_softmax<4, false>(s, mx, nt);
     f32x4 o[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      if (2 * ks < nt) {
-        uint4 pw;
-        pw.x = pack_bf16(s[2 * ks][0] * inv, s[2 * ks][1] * inv);
-        pw.y = pack_bf16(s[2 * ks][2] * inv, s[2 * ks][3] * inv);
-        pw.z = pack_bf16(s[2 * ks + 1][0] * inv, s[2 * ks + 1][1] * inv);
-        pw.w = pack_bf16(s[2 * ks + 1][2] * inv, s[2 * ks + 1][3] * inv);
-        const bf16x8 pa = *reinterpret_cast<const bf16x8*>(&pw);
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-          o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa, tr_split(Vw, WA_LD, 32 * ks + 4 * g, 16 * dt, lane), o[dt],
-                                                          0, 0, 0);
-      }
-    }
-    // ---- o[dt][r] = O[query 16 qt + 4 g + r][d = 16 dt + li]: through LDS, then one 16-byte store per lane
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int r = 0; r < 4; r += 2) {
-        const unsigned int w2 = pack_bf16(o[dt][r], o[dt][r + 1]);
-        Ow[(4 * g + r) * WA_LD + 16 * dt + li] = (unsigned short)(w2 & 0xffffu);
-        Ow[(4 * g + r + 1) * WA_LD + 16 * dt + li] = (unsigned short)(w2 >> 16);
-      }
+    window_pv<4>(s, inv, Vw, nt, lane, o);
+    window_tile_to_lds(o, Ow, lane);
     __syncthreads();
     {
-      const int r = lane >> 2, c8 = lane & 3, slot = 16 * qt + r;
+      const int slot = 16 * qt + (lane >> 2);
       const int64_t row = ((int64_t)__shfl(rhi, slot, 64) << 32) | (unsigned int)__shfl(rlo, slot, 64);
-      if (live && slot < N) {
-        unsigned short* orow = out + row * ld_out;
-        *reinterpret_cast<uint4*>(orow + h * 32 + c8 * 8) = *reinterpret_cast<const uint4*>(Ow + r * WA_LD + c8 * 8);
-        for (int j = h * 4 + c8; j < npad; j += heads * 4)             // the pad columns, shared out over the heads
-          *reinterpret_cast<uint4*>(orow + C + j * 8) = make_uint4(0, 0, 0, 0);
-      }
+      if (live && slot < N) window_store_row(out, row, ld_out, Ow, h, heads, C, npad, lane);
     }
     __syncthreads();
   }
@@ -262,21 +198,10 @@ extern "C" int basd_window_attention_fwd_bf16(const void* qkv, const float* bias
                                               void* stream) {
   using namespace basd;
   if (B <= 0) return BASD_OK;
-  if (ws < 1 || ws > 8 || shift < 0 || shift >= ws)
-    return fail(BASD_ERR_SHAPE, "window_attention_fwd: 1 <= ws <= 8 and 0 <= shift < ws (got ws=%d shift=%d)", ws, shift);
-  if (H < ws || W < ws || H % ws || W % ws)
-    return fail(BASD_ERR_SHAPE, "window_attention_fwd: H and W must be multiples of ws (got %d x %d, ws=%d)", H, W, ws);
-  if (heads < 1 || C != 32 * heads)
-    return fail(BASD_ERR_SHAPE, "window_attention_fwd: head dim 32 only, C = 32 heads (got C=%d heads=%d)", C, heads);
-  if (ld_qkv % 8 || ld_out % 8 || ld_qkv < 3 * C || ld_out < C)
-    return fail(BASD_ERR_SHAPE, "window_attention_fwd: row strides must be multiples of 8 with 3 C <= ld_qkv, C <= ld_out "
-                "(got C=%d ld_qkv=%d ld_out=%d)", C, ld_qkv, ld_out);
-  if (((uintptr_t)qkv | (uintptr_t)bias | (uintptr_t)out) & 15)
-    return fail(BASD_ERR_SHAPE, "window_attention_fwd: 16-byte aligned buffers required");
-  if (out == qkv) return fail(BASD_ERR_SHAPE, "window_attention_fwd: out must not alias qkv");
-  const int64_t problems = (int64_t)B * (H / ws) * (W / ws) * heads;
-  const int64_t grid = (problems + WA_WAVES - 1) / WA_WAVES;
-  if (grid > 0x7fffffffLL) return fail(BASD_ERR_SHAPE, "window_attention_fwd: %lld workgroups", (long long)grid);
+  int64_t problems, grid;
+  if (int rc = window_attention_check("window_attention_fwd", 1, 8, qkv, bias, out, B, H, W, heads, C, ws, shift, ld_qkv,
+                                      ld_out, WA_WAVES, problems, grid))
+    return rc;
   hipLaunchKernelGGL(window_attention_kernel, dim3((unsigned)grid), dim3(64 * WA_WAVES), 0, (hipStream_t)stream,
                      (const unsigned short*)qkv, bias, H, W, heads, C, ws, shift, ld_qkv, ld_out, scale,
                      (unsigned short*)out, problems);

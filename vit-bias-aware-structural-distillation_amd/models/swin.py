@@ -233,10 +233,10 @@ class SwinTransformer(FusedTrunk, nn.Module):
         ops = get_ops()
         return next((n for n in range((3 * c + 127) // 128 * 128, 3 * c + 513, 128) if ops.gemm_supported(n, ld)), None)
 
-    def _wide_window(self) -> bool:
-        """which attention entry the blocks take: windows up to 8 fill the 64-slot tile of ``window_attention`` (bias as
-        a [heads, 64, 64] image), larger ones go to ``window_attention_wide`` (the fp32 bias table itself)"""
-        return self.window_size > WINDOW_TILE
+    def _attend_entry(self) -> str:
+        """the entry every block takes (one window per model, ``_stage_window`` never changes it): ``window_attention``
+        with a [heads, 64, 64] bias image up to window 8, ``window_attention_wide`` with the fp32 bias table above"""
+        return "window_attention_wide" if self.window_size > WINDOW_TILE else "window_attention"
 
     def fused_refusal(self) -> str | None:
         """Why the kernels do not take this architecture (None: they do)."""
@@ -246,10 +246,10 @@ class SwinTransformer(FusedTrunk, nn.Module):
         if self.patch_embed.proj.weight.shape[1] != 3:
             return f"the patch embedding takes 3 input channels (got {self.patch_embed.proj.weight.shape[1]})"
         ws = self.window_size                     # the window every block uses on any grid (``_stage_window``)
-        wide = self._wide_window()
-        if wide and not hasattr(ops, "window_attention_wide"):
+        entry = self._attend_entry()
+        if not hasattr(ops, entry):
             return f"stage 0: window {ws} needs the wide window attention entry, which the kernel provider does not have"
-        supported = ops.window_attention_wide_supported if wide else ops.window_attention_supported
+        supported = getattr(ops, entry + "_supported")
         for i, (c, nh) in enumerate(zip(self.dims, self.heads)):
             ld = row_width(c)
             nq = self._qkv_width(c, ld)
@@ -276,14 +276,14 @@ class SwinTransformer(FusedTrunk, nn.Module):
         windows up to 8, the fp32 table itself for ``basd_window_attention_fwd_wide_bf16`` (an expanded image of a
         window-12 model would be [heads, 144, 144] per block)."""
         ops = get_ops()
-        wide = self._wide_window()
+        entry = self._attend_entry()
         proj = self.patch_embed.proj
         lds = [row_width(c) for c in self.dims]
 
         def linear(m, n_ld, k_ld):
             return padded_image(m.weight, m.bias, n_ld, k_ld)
 
-        fused = {"lds": lds, "stages": [],
+        fused = {"lds": lds, "stages": [], "attend": entry,
                  "ident": {c: centre_tap_identity(c, proj.weight.device) for c, ld in zip(self.dims, lds) if ld != c},
                  "embed": padded_image(patch_image(proj.weight), proj.bias, lds[0], 64),
                  "embed_norm": norm_params(self.patch_embed.norm), "norm": norm_params(self.norm)}
@@ -297,17 +297,17 @@ class SwinTransformer(FusedTrunk, nn.Module):
             for blk in stage.blocks:
                 rec["blocks"].append({
                     "norm1": norm_params(blk.norm1), "qkv": linear(blk.attn.qkv, nq, ld),
-                    "bias": (blk.attn.relative_position_bias_table.to(torch.float32).contiguous() if wide
-                             else ops.window_bias_image(blk.attn.bias())), "scale": blk.attn.scale, "shift": blk.shift,
-                    "proj": linear(blk.attn.proj, ld, ld), "norm2": norm_params(blk.norm2),
-                    "fc1": linear(blk.mlp.fc1, 4 * c, ld), "fc2": linear(blk.mlp.fc2, ld, 4 * c)})
+                    "bias": (ops.window_bias_image(blk.attn.bias()) if entry == "window_attention"
+                             else blk.attn.relative_position_bias_table.to(torch.float32).contiguous()),
+                    "scale": blk.attn.scale, "shift": blk.shift, "proj": linear(blk.attn.proj, ld, ld),
+                    "norm2": norm_params(blk.norm2), "fc1": linear(blk.mlp.fc1, 4 * c, ld), "fc2": linear(blk.mlp.fc2, ld, 4 * c)})
             fused["stages"].append(rec)
         return fused
 
     def _forward_fused(self, x):
         """x [B, 3, H, W] bf16 (any strides) -> [B, H/32, W/32, C_last] bf16, a view of the last rows"""
         ops, fz = get_ops(), self._fused
-        lds, ws = fz["lds"], self.window_size
+        lds, ws, attend = fz["lds"], self.window_size, getattr(ops, fz["attend"])
         b, _, h, w = x.shape
         h, w = h // 4, w // 4
         t = ops.gemm_bf16(ops.patchify(x, 4, 64), *fz["embed"])                          # [B h w, ld0]
@@ -323,7 +323,6 @@ class SwinTransformer(FusedTrunk, nn.Module):
                 win, shift = _stage_window(h, w, ws, blk["shift"])
                 y = self._norm_rows(ops, t, c, *blk["norm1"])
                 qkv = ops.gemm_bf16(y, *blk["qkv"])
-                attend = ops.window_attention_wide if win > WINDOW_TILE else ops.window_attention
                 a = attend(qkv.view(b, h, w, qkv.shape[1]), blk["bias"], win, shift, nh, blk["scale"], ld_out=ld)
                 p = ops.gemm_bf16(a.view(b * h * w, ld), *blk["proj"])
                 if ld == c:
